@@ -7,7 +7,19 @@ env-steps trigger (update every `update_after_actions` env-steps with batch B, r
 = 8 samples per env-step as in the reference: B 32 every 4 steps).  Each update = sample + gather, target
 forward, online forward, Huber, backward, [RCCL all-reduce], clip_by_norm + Adam.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up (below), W untimed training vector steps, K
+timed ones, the outputs of the last timed step written to DIR when --dump-outputs is given, one JSON line.  Everything
+else the benchmark measures - the event-timed per-kernel pass, roofline, per-layer MFMA and HBM rates, the skipped
+fractions, the runs beside the headline (per-batch targets, dense frames, reference work, single-rank DP, C5 shard, the
+other precision) and the CPU baseline - runs with --full, which prints the same headline keys plus those figures.
+
+--dump-outputs DIR writes what a caller of the timed loop holds after its last timed vector step, as DIR/<name>.npy
+(float32 / float64, at most 64 MB in all): that step's actions, rewards, dones, per-update losses, sampled replay
+indices and Bellman targets (qlx_learner_last), the online net's ten variables, the env mechanics, the acting frames of
+a fixed seeded sample of envs and the learner's counters.  Seeds, sizes and the number of vector steps before the timed
+window depend on the arguments only, so two builds run with the same arguments can be compared array for array.
 
 Default workload (N = 1): config C3 of SURVEY.md §8(d) - 8,192 envs per GPU, replay 1,000,000 in HBM, B = 1024,
 fp32 Q-net (the reference's arithmetic).  Steady state regardless of --warmup: before anything is timed the replay
@@ -17,9 +29,9 @@ ends are spread over the steps as in a long run (all envs launch together and th
 nearly one length, so their ends come in waves): after the first wave the envs' next episodes are started at staggered
 steps (Run._steady), then one mean episode length of vector steps must each hold within +-50 % of the expected
 n_envs / mean-length episode ends.  Then W untimed training vector steps, then K timed ones (asserted to contain
-episode ends).  Beside the headline, measured in the same run: the same loop with the frozen target net evaluated per
-sampled batch as the reference does (value_no_target_memo), fp32 with the exact zero skips off (value_dense_frames:
-every conv1 step and conv2 / conv3 row computed), the per-step fractions those skips leave out (skipped_fractions), and
+episode ends).  Beside the headline, measured in the same run with --full: the same loop with the frozen target net
+evaluated per sampled batch as the reference does (value_no_target_memo), fp32 with the exact zero skips off
+(value_dense_frames: every conv1 step and conv2 / conv3 row computed), the per-step fractions those skips leave out (skipped_fractions), and
 the bf16 fast path (labelled, not the headline).
 
 Multi-GPU: with --gpus N > 1 and no WORLD_SIZE in the environment, this process starts
@@ -46,6 +58,10 @@ PEAK_TFLOPS = {"fp32": 157.3, "bf16": 2500.0}   # MI355X dense MFMA peaks (MI355
 # stream of independent ends: ~1 / sqrt(n_envs / T))
 STEADY_MEAN_TOL, STEADY_MAX_CV, MAX_STEADY = 0.1, 0.5, 4000
 PEAK_HBM_GBS = 8000.0                            # HBM3E
+# --dump-outputs: at most 64 MB in all; the acting frames of 64 envs (fixed seed); the learner counters written as "stats"
+DUMP_MAX_BYTES, DUMP_ENVS, DUMP_SEED = 64_000_000, 64, 20
+DUMP_STATS = ("step_count", "vec_steps", "update_count", "episode_count", "replay_len", "epsilon", "running_reward",
+              "last_loss")
 # per-sample algorithmic FLOPs of the Q-net: forward 18,689,024; per trained sample 68,202,496
 FWD_FLOP, TRAIN_FLOP = 18_689_024, 68_202_496
 TRANSITION_BYTES = 56_454          # logical (a, s, s', r, done) of one sampled transition
@@ -76,6 +92,12 @@ def parse():
     ap.add_argument("--replay-ratio", type=int, default=8, help="samples per env-step (reference: 32 per 4 steps)")
     ap.add_argument("--replay", type=int, default=1_000_000, help="replay capacity per GPU (C3: 1M; C2: 100k)")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="headline Q-net arithmetic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed vector step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the event-timed per-kernel pass, roofline and "
+                         "per-layer rates, skipped fractions, the runs beside the headline and the CPU baseline (what "
+                         "--beside / nomemo / dense / refwork / dp1 / c5 / sparsity-steps and --cpu-sample size)")
     ap.add_argument("--beside-steps", type=int, default=5, help="timed vector steps of the other precision (0 = skip)")
     ap.add_argument("--nomemo-steps", type=int, default=5,
                     help="timed vector steps of the headline precision with the target net evaluated per sampled batch "
@@ -240,7 +262,8 @@ def rate(work, us, div):
 class Run:
     """One learner measured on the steady-state workload."""
 
-    def __init__(self, args, ctl, precision, steps, warmup, flags, sparsity_steps=0, dp1=False):
+    def __init__(self, args, ctl, precision, steps, warmup, flags, sparsity_steps=0, dp1=False, profiled=True,
+                 dump_dir=None):
         import qlx
         self.args, self.ctl, self.precision = args, ctl, precision
         N, B = args.envs, args.batch
@@ -273,11 +296,18 @@ class Run:
             assert s["replay_len"] == args.replay and s["episode_count"] > 0, s
             assert s["step_count"] >= p.epsilon_pure_random_steps, s
             self.prefill = prefill
-            log(f"{precision}: profile pass")
-            self.comps = self._profile()
+            if profiled:
+                log(f"{precision}: profile pass")
+                self.comps = self._profile()
+            else:
+                # the same vector steps without the events, so a plain and a --full run time (and dump) the same steps
+                self.comps = None
+                L.run(args.profile_steps)
             log(f"{precision}: timed {steps} vector steps")
             self._timed(steps)
             log(f"{precision}: {self.value():.1f} env-steps/s")
+            if dump_dir:
+                self._dump(dump_dir)
             self.sparsity = self._sparsity(sparsity_steps) if sparsity_steps > 0 else None
         finally:
             L.close()
@@ -355,10 +385,12 @@ class Run:
 
     def _timed(self, steps):
         L, ctl, gemm = self.L, self.ctl, GEMM_SCOPES[self.precision]
-        self.dominant = max((c for c in self.comps if c in gemm), key=lambda c: self.comps[c]["total_us_per_step"])
-        # events only around the dominant kernel, on every 7th launch (keeps the event cost off the clock)
-        L.profile(True)
-        L.profile_filter(self.dominant, stride=7)
+        profiled = self.comps is not None
+        if profiled:
+            self.dominant = max((c for c in self.comps if c in gemm), key=lambda c: self.comps[c]["total_us_per_step"])
+            # events only around the dominant kernel, on every 7th launch (keeps the event cost off the clock)
+            L.profile(True)
+            L.profile_filter(self.dominant, stride=7)
         s0 = L.stats()
         ctl.barrier()
         L.sync()
@@ -368,8 +400,9 @@ class Run:
         ctl.barrier()
         dt = ctl.max(time.perf_counter() - t0)
         s1 = L.stats()
-        self.dom_us, self.dom_work, self.dom_launches = L.profile_get(self.dominant)
-        L.profile(False)
+        if profiled:
+            self.dom_us, self.dom_work, self.dom_launches = L.profile_get(self.dominant)
+            L.profile(False)
         self.steps, self.dt = steps, dt
         self.env_steps = self.args.envs * steps * ctl.world
         self.updates = s1["update_count"] - s0["update_count"]
@@ -379,6 +412,44 @@ class Run:
         self.last_loss = s1["last_loss"]
         self.running_reward = s1["running_reward"]
         self.epsilon = s1["epsilon"]
+
+    def _dump(self, out_dir):
+        """--dump-outputs: what a caller of the timed loop holds after its last timed vector step, as float32 / float64
+        .npy files (rank r > 0 of a multi-GPU run writes <name>.rank<r>.npy).  Kept under DUMP_MAX_BYTES in all: the
+        acting frames are those of DUMP_ENVS envs drawn with a fixed seed, and an array that still would not fit is cut
+        to a fixed seeded sample of its elements (in index order)."""
+        import numpy as np
+        import qlx
+        L, N = self.L, self.args.envs
+        out = {}
+        # the step's actions / rewards / dones [n_envs], losses [U], indices / targets [U, B]
+        for k, v in L.last(max_updates=N // self.ua + 2).items():
+            out[f"last_{k}"] = np.asarray(v, np.float64 if k == "indices" else np.float32)
+        for i, name in enumerate(qlx.VAR_NAMES):
+            out[f"online_{i}_" + name.replace("/", "_")] = L.model.get(i)
+        mech = L.environment.mechanics()
+        cols = [mech[k].astype(np.float64) for k in qlx.STATE_DTYPE.names if k != "bricks"]
+        cols += [(mech["bricks"] & np.uint64(0xFFFFFFFF)).astype(np.float64),
+                 (mech["bricks"] >> np.uint64(32)).astype(np.float64)]
+        out["env_mechanics"] = np.stack(cols, axis=1)   # STATE_DTYPE's fields in order, bricks as its low and high 32 bits
+        envs = np.sort(np.random.default_rng(DUMP_SEED).choice(N, min(N, DUMP_ENVS), replace=False))
+        out["acting_frames_envs"] = envs.astype(np.float64)
+        out["acting_frames"] = L.environment.state()[envs].astype(np.float32)
+        s = L.stats()
+        out["stats"] = np.array([float(s[k]) for k in DUMP_STATS], np.float64)
+        share = DUMP_MAX_BYTES // len(out)
+        for j, k in enumerate(sorted(out)):
+            if out[k].nbytes > share and sum(a.nbytes for a in out.values()) > DUMP_MAX_BYTES:
+                flat = out[k].reshape(-1)
+                rng = np.random.default_rng(DUMP_SEED + 1 + j)
+                pick = np.sort(rng.choice(flat.size, share // flat.itemsize, replace=False))
+                out[k] = flat[pick]
+        assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+        os.makedirs(out_dir, exist_ok=True)
+        suffix = f".rank{self.ctl.rank}" if self.ctl.rank else ""
+        for k, a in out.items():
+            np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
+        log(f"{self.precision}: wrote {len(out)} arrays, {sum(a.nbytes for a in out.values()) / 1e6:.1f} MB, to {out_dir}")
 
     def _sparsity(self, n):
         """Per vector step (untimed, after the timed window): the fractions of the fp32 conv work the exact zero skips
@@ -562,6 +633,48 @@ def run_with_env(env, *a, **kw):
                 os.environ[k] = v
 
 
+def headline(args, ctl, head, flags):
+    """The result line of a plain run: the headline figure, its workload and the steady state it was measured in."""
+    N, B = args.envs, args.batch
+    label = config_label(N, args.replay, flags, ctl.world)
+    return {
+        "metric": METRIC,
+        "value": round(head.value(), 1),
+        "unit": "env-steps/s",
+        "n_gpus": ctl.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(head.dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.precision,
+        "data": "synthetic: frames rendered by the batched Breakout env kernel from live play; random-init "
+                "(GlorotUniform) Nature-DQN; replay prefilled to capacity before timing",
+        "config": {"workload": f"{label}: {N} Breakout envs per GPU, replay {args.replay} per GPU in HBM (prefilled), "
+                               f"Nature-DQN (3 conv + 2 dense) in {args.precision}, B={B}, update every {head.ua} "
+                               f"env-steps per GPU (replay ratio {args.replay_ratio} samples/env-step), epsilon-greedy "
+                               f"acting" + (" + double-DQN" if args.double_dqn else "")
+                               + (" + prioritized replay" if args.per else ""),
+                   "envs_per_gpu": N, "batch": B, "replay_capacity": args.replay, "update_after_actions": head.ua,
+                   "parallelism": f"dp{ctl.world}" if ctl.world > 1 else "single", "rccl_world": head.rccl_world,
+                   "global_batch_per_update": B * head.rccl_world,
+                   "env_dtype": "fp32 physics, u8 frames",
+                   "qnet_dtype": "fp32 (exact-fp32 MFMA v_mfma_f32_16x16x4_f32)" if args.precision == "fp32"
+                   else "bf16 MFMA operands, fp32 accumulate + master weights"},
+        "grad_updates_per_sec": round(head.updates / head.dt, 2),
+        "samples_per_sec": round(head.updates * B * ctl.world / head.dt, 1),
+        "replay_ratio": args.replay_ratio,
+        "steady_state": {"prefill_vector_steps": head.prefill, "episodes_in_window": head.episodes,
+                         "episode_ends_per_step": round(head.ends_per_step, 2),
+                         "expected_ends_per_step": round(head.expect_ends * ctl.world, 2),
+                         "mean_episode_env_steps": round(head.mean_len, 1), "steady": head.steady_ok,
+                         "steady_window": head.steady_window,
+                         "episodes_total": head.episodes_total, "epsilon": round(head.epsilon, 4),
+                         "running_reward": head.running_reward, "last_loss": head.last_loss},
+    }
+
+
 def main():
     args = parse()
     if args.no_target_memo:
@@ -577,7 +690,14 @@ def main():
     import qlx
     flags = (qlx.DOUBLE_DQN if args.double_dqn else 0) | (qlx.PER if args.per else 0)
     f32 = args.precision == "fp32"
-    head = Run(args, ctl, args.precision, args.steps, args.warmup, flags, args.sparsity_steps if f32 else 0)
+    head = Run(args, ctl, args.precision, args.steps, args.warmup, flags, args.sparsity_steps if f32 and args.full else 0,
+               profiled=args.full, dump_dir=args.dump_outputs)
+    # the measured window is the steady-state loop: episode ends inside it
+    assert head.episodes > 0, "no episode ended inside the timed window"
+    if not args.full:
+        if ctl.rank == 0:
+            print(json.dumps(headline(args, ctl, head, flags)), flush=True)
+        return
     nomemo = None
     if args.nomemo_steps > 0 and "target_memo" in head.comps:
         # the reference's per-batch target work (same values, tests/test_gpu_learner.py), measured in this run
@@ -603,55 +723,16 @@ def main():
     other = "bf16" if args.precision == "fp32" else "fp32"
     beside = Run(args, ctl, other, args.beside_steps, 1, flags, args.sparsity_steps if other == "fp32" else 0) \
         if args.beside_steps > 0 else None
-    # the measured window is the steady-state loop: greedy acting and episode ends inside it
+    # ... and the greedy acting forward
     assert "act_forward" in head.comps, "acting forward missing from the measured loop"
-    assert head.episodes > 0, "no episode ended inside the timed window"
     if ctl.rank != 0:
         return
     N, B = args.envs, args.batch
-    label = config_label(N, args.replay, flags, ctl.world)
     comps = {k: {kk: round(vv, 3) for kk, vv in v.items() if kk != "work"}
              for k, v in sorted(head.comps.items(), key=lambda kv: -kv[1]["total_us_per_step"])}
-    line = {
-        "metric": METRIC,
-        "value": round(head.value(), 1),
-        "unit": "env-steps/s",
-        "n_gpus": ctl.world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(head.dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.precision,
-        "data": "synthetic: frames rendered by the batched Breakout env kernel from live play; random-init "
-                "(GlorotUniform) Nature-DQN; replay prefilled to capacity before timing",
-        "config": {"workload": f"{label}: {N} Breakout envs per GPU, replay {args.replay} per GPU in HBM (prefilled), "
-                               f"Nature-DQN (3 conv + 2 dense) in {args.precision}, B={B}, update every {head.ua} "
-                               f"env-steps per GPU (replay ratio {args.replay_ratio} samples/env-step), epsilon-greedy "
-                               f"acting" + (" + double-DQN" if args.double_dqn else "")
-                               + (" + prioritized replay" if args.per else ""),
-                   "envs_per_gpu": N, "batch": B, "replay_capacity": args.replay, "update_after_actions": head.ua,
-                   "parallelism": f"dp{ctl.world}" if ctl.world > 1 else "single", "rccl_world": head.rccl_world,
-                   "global_batch_per_update": B * head.rccl_world,
-                   "target_memo": "target_memo" in head.comps,
-                   "env_dtype": "fp32 physics, u8 frames",
-                   "qnet_dtype": "fp32 (exact-fp32 MFMA v_mfma_f32_16x16x4_f32)" if args.precision == "fp32"
-                   else "bf16 MFMA operands, fp32 accumulate + master weights"},
-        "grad_updates_per_sec": round(head.updates / head.dt, 2),
-        "samples_per_sec": round(head.updates * B * ctl.world / head.dt, 1),
-        "replay_ratio": args.replay_ratio,
-        "roofline": head.roofline(),
-        **head.report(),
-        "steady_state": {"prefill_vector_steps": head.prefill, "episodes_in_window": head.episodes,
-                         "episode_ends_per_step": round(head.ends_per_step, 2),
-                         "expected_ends_per_step": round(head.expect_ends * ctl.world, 2),
-                         "mean_episode_env_steps": round(head.mean_len, 1), "steady": head.steady_ok,
-                         "steady_window": head.steady_window,
-                         "episodes_total": head.episodes_total, "epsilon": round(head.epsilon, 4),
-                         "running_reward": head.running_reward, "last_loss": head.last_loss},
-        "components_event_timed": comps,
-    }
+    line = headline(args, ctl, head, flags)
+    line["config"]["target_memo"] = "target_memo" in head.comps
+    line.update({"roofline": head.roofline(), **head.report(), "components_event_timed": comps})
     if nomemo is not None:
         line["value_no_target_memo"] = round(nomemo.value(), 1)
         line["no_target_memo"] = {

@@ -15,7 +15,7 @@ SHORT="--steps 3 --warmup 1 --beside-steps 0 --nomemo-steps 0 --dense-steps 0 --
 if [[ $PART == *a* ]]; then
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/gputest.log" 2>&1 || exit 1
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit 1
-timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- \
   python3 bench.py $SHORT > "$OUT/stats.json" 2> "$OUT/stats.err" || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_bf16" -o s -- \
