@@ -570,21 +570,6 @@ static int conv_adam_blocks() {
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-#ifndef QLX_PB_OFF
-#define QLX_PB_OFF 0   // (timing only: the conv2 backward without conv1's bias partials - the conv1 bias is then wrong)
-#endif
-constexpr int kSC1 = QLX_F32_WGRAD_CHUNK_CONV1, kSC2 = QLX_F32_WGRAD_CHUNK_CONV2, kSC3 = QLX_F32_WGRAD_CHUNK_CONV3;
-// weight-gradient chunk tiles 64 x 64 on 1 x 4 waves (each wave 64 rows x 16 channels): conv3 / conv2 pairs 73.0 -> 72.3 /
-// 102.2 -> 101.2 us in place against 2 x 2 (4 x 1: no change; gpurun_out/w14)
-// conv3's offset table after the images (3 blocks per CU: pair 72.1 us; in the images' pads, 4 per CU: 76.1 us, held to 3
-// by a 44 KB LDS request: 73.1 us - gpurun_out/w22, w31); conv2's in the pads (4 blocks per CU: pair 99.6 -> 96.8 us)
-using PConv3Wgrad = PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, kSC3, 64, 64, 1, 4, 16, false, true>;   // (compacted)
-using PConv3WgradD = PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, kSC3, 64, 64, 1, 4, 16, false>;         // (every row: QLX_F32_BG=0)
-static_assert(kSC3 == 16, "conv3 weight-gradient chunks are the fc1 backward's 16-row fragments (pbg)");
-using PConv2Wgrad = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2, 64, 64, 1, 4, 16, true, true>;   // (compacted)
-using PConv2WgradD = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2, 64, 64, 1, 4>;                  // (every row: QLX_F32_BG=0)
-static_assert(kSC2 == 16, "conv2 weight-gradient chunks are the conv3 backward's 16-row fragments (pbg)");
-
 static int segs_of(int v) { return (kVarSize[v] + kNormSeg - 1) / kNormSeg; }
 static_assert((1605632 + kNormSeg - 1) / kNormSeg <= kNormSegMax, "norm partials per variable");
 static_assert((36864 + kNormSeg - 1) / kNormSeg <= 4 * kConvSegsPerGroup && (32768 + kNormSeg - 1) / kNormSeg <= 4 * kConvSegsPerGroup,
@@ -599,21 +584,7 @@ static int num_cus();
 constexpr int kC1MaxIt = 64;
 static int c1_blocks(int n) { return std::max(std::min(n, 2 * num_cus()), (n + kC1MaxIt - 1) / kC1MaxIt); }
 // the training-batch forward (n <= 2,048: not a chunk pass) runs one sample per block (k_conv1_fwd32 ONE)
-#ifndef QLX_C1_ONE
-#define QLX_C1_ONE 1
-#endif
-#ifndef QLX_C2_FWD_KS
-#define QLX_C2_FWD_KS 2   // training-batch conv2 / conv3 list forwards: chains in wave groups (2) or in turn (1)
-#endif
-#ifndef QLX_C3_FWD_KS
-#define QLX_C3_FWD_KS 2
-#endif
-constexpr int kC2FwdKs = QLX_C2_FWD_KS <= kConvFwdChains ? QLX_C2_FWD_KS : 1;
-constexpr int kC3FwdKs = QLX_C3_FWD_KS <= kConvFwdChains ? QLX_C3_FWD_KS : 1;
-static bool c1_one(int n) {
-  static const bool all = [] { const char* e = std::getenv("QLX_C1_ONE_ALL"); return e && e[0] == '1'; }();   // (A/B)
-  return QLX_C1_ONE && (n <= 2048 || all);
-}
+static bool c1_one(int n) { return n <= 2048; }
 static int c1_grid(int n) { return c1_one(n) ? n : c1_blocks(n); }
 
 void f32_workspace(qlx_model* m, int B) {
@@ -640,7 +611,6 @@ void f32_workspace(qlx_model* m, int B) {
   // G >= min(n, 2 CUs) and G <= max(2 CUs, C / kC1MaxIt + 1) (one sample per block, c1_one: G = n, n + kListSlots)
   const int frl_cap = C + kListSlots * (C / std::max(1, std::min(C, 2 * num_cus())) + 1) +
                       std::max(2 * num_cus(), C / kC1MaxIt + 1) + kListSlots;
-  static_assert(2048 + kListSlots <= 2048 + kListSlots * 2, "c1_one list capacity");
   const size_t o_rl2 = take((size_t)frl_cap * 81 * 4), o_rl3 = take((size_t)frl_cap * 49 * 4);
   const size_t o_rcnt = take(2 * 2 * kListSlots * kCntStride * 8), o_bgc = take(160 * 4), o_steps = take((size_t)C * 4 * 4);
   const int need_ld = (C + 63) / 64 * 64;   // (the conv2 backward-data tiles read 64-row blocks of it)
@@ -780,9 +750,6 @@ static bool bg_rows(const qlx_model* m) { return m->f32_bg_rows; }
 
 // the conv1 step masks of the training forward (written with its row lists) select the dz1 rows the conv2 backward
 // stores and the conv1 weight gradient fetches; without zero-step skipping every row is multiplied, so every row
-#ifndef QLX_DZ1_SKIP
-#define QLX_DZ1_SKIP 1   // 0: the conv2 backward stores every dz1 row (the weight gradient still fetches the set steps' only)
-#endif
 static bool c1_sparse_dz(const qlx_model* m) { return bg_rows(m) && c1_skip(m); }
 template <class PW, class PR, class PF>
 static void conv_fwd(qlx_model* m, int M, const float* in, const float* wt, const float* bias, float* out, const char* scope,
@@ -825,7 +792,7 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
       const char* sc = big ? "f32_conv1_fwd_big" : "f32_conv1_fwd";
       hipEvent_t ea = nullptr, eb = nullptr;
       if (m->prof) m->prof->ext(sc, 2.0 * n * 400 * 32 * 256, &ea, &eb);
-      auto kern = big ? k_conv1_fwd32<1> : one ? k_conv1_fwd32<0, true> : k_conv1_fwd32<0>;
+      auto kern = one ? k_conv1_fwd32<0, true> : k_conv1_fwd32<1>;   // (one == !big)
       QLX_CHECK((n + G - 1) / G <= (one ? 1 : kC1MaxIt), QLX_E_STATE, "conv1 forward: too many samples per block");
       const size_t frames = (one ? 1 : 2) * kC1Frames;
       const size_t lds = frames + 3 * kC1RmDw * 4 + (size_t)((n + G - 1) / G) * 6 * 8 + 8;   // frames, row masks, flags, claim
@@ -846,9 +813,9 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
       auto run = [&](auto t2, auto t3, const char* sc2, const char* sc3) {
         using P2 = decltype(t2);
         using P3 = decltype(t3);
-        // the constant rows' chains in the conv2 launch's blocks: the same K split form as its list tiles (block size)
-        using PC2 = PConv2FwdL<16, 64, 1, 4, P2::KSPLIT>;
-        using PC3 = PConv3FwdL<16, 64, 1, 4, P2::KSPLIT>;
+        // the constant rows' chains in the conv2 launch's first block
+        using PC2 = PConv2FwdL<16, 64, 1, 4>;
+        using PC3 = PConv3FwdL<16, 64, 1, 4>;
         const ConstRows<PC2, PC3> cr{PC2{Grid{1, 1, 1}, w.fa1, p + voff(2), p + voff(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, c2},
                                      PC3{Grid{1, 1, 1}, w.fa2, p + voff(4), p + voff(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, c3}};
         // (the list tiles start at row tile 1; row tile 0, the constant row, is ConstRows' work: its blocks return)
@@ -867,8 +834,7 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
       } else {
         // (on the stream core, in place: conv2 64 x 64 24.3 us against 27.9 us for 64 x 32 and 28.7 for 32 x 64; conv3 32 x 64
         // 27.6 us against 28.5 / 29.8 for 64 x 32 / 64 x 64 - gpurun_out/w10)
-        // round 6: the two k chains (§6) in two wave groups per block (KSPLIT): twice the waves for the same tiles
-        run(PConv2FwdL<64, 64, 2, 2, kC2FwdKs>{}, PConv3FwdL<32, 64, 2, 2, kC3FwdKs>{}, "f32_conv2_fwd", "f32_conv3_fwd");
+        run(PConv2FwdL<64, 64, 2, 2>{}, PConv3FwdL<32, 64, 2, 2>{}, "f32_conv2_fwd", "f32_conv3_fwd");
         model_dense_join(m, s);
         launch(m, PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), w.fa3, p + voff(6), p + voff(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd",
                2.0 * n * 3136 * 512, s);
@@ -988,14 +954,12 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
   // algorithmic FLOPs (backward-data + weight gradient of the layer; the pixel-major dgrad tiles multiply only the
   // valid taps, so MFMA work = algorithmic work)
   // pixel-major backward data, one pixel per tile.  On the operand-stream core (no per-slab address arithmetic) the
-  // one-pixel conv3 tiles beat the balanced pixel groups (chained sub-tiles: scripts/ubench32.hip bwd, B = 1024: pair 84.4
-  // vs 93.4 us; on the ldA / ldB core the groups had won, 97.1 vs 105.6 us); conv2 groups were slower on both cores
+  // one-pixel conv3 tiles beat balanced pixel groups chained in one block (B = 1024: pair 84.4 vs 93.4 us; on the ldA / ldB
+  // core the groups had won, 97.1 vs 105.6 us); conv2 groups were slower on both cores (removed)
   {  // conv3: dz2 pixel tiles + weight-gradient chunk tiles
     PConv3Wgrad Pw{grid(576, 64, 64, 64, z3), w.fa2, w.fdz3, w.fslab3, B, w.frows3};
     PConv3WgradD Pw_dense{grid(576, 64, 64, 64, z3), w.fa2, w.fdz3, w.fslab3, B};
-    // 64 x 64 pixel tiles on the stream core: pair 73.2 vs 75.0 us in place for 32 x 64 (gpurun_out/w3)
-    using PD3 = PConv3DgradPx<64, 64, 2, 2>;
-    PD3 Pd{Grid{(B + PD3::BM - 1) / PD3::BM, 1, 81}, w.fdz3, p + voff(4), w.fa2, w.fdz2, B};
+    PConv3DgradP Pd{Grid{(B + PConv3DgradP::BM - 1) / PConv3DgradP::BM, 1, 81}, w.fdz3, p + voff(4), w.fa2, w.fdz2, B};
     if (bg_rows(m)) {   // conv2's background-row dz2 sums (the compacted conv2 weight gradient)
       Pd.pbg = w.fpbg2;
       Pd.bg2 = w.fbg2;
@@ -1010,8 +974,8 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
     // over every row on the dense-frame path
     PConv2Wgrad Pw{grid(512, 64, 64, 64, z2), w.fa1, w.fdz2, w.fslab2, B, w.frows2};
     PConv2WgradD Pw_dense{grid(512, 64, 64, 64, z2), w.fa1, w.fdz2, w.fslab2, B};
-    PConv2DgradPx<64, 64, 2, 2> Pd{Grid{(B + 63) / 64, 2, 100}, w.fdz2, p + voff(2), w.fa1, w.fdz1, B, QLX_PB_OFF ? nullptr : w.fpb1};
-    if (QLX_DZ1_SKIP && c1_sparse_dz(m)) {   // dz1 rows of clear conv1 steps are neither stored here nor fetched by the conv1 weight gradient
+    PConv2DgradP Pd{Grid{(B + 63) / 64, 2, 100}, w.fdz2, p + voff(2), w.fa1, w.fdz1, B, w.fpb1};
+    if (c1_sparse_dz(m)) {   // dz1 rows of clear conv1 steps are neither stored here nor fetched by the conv1 weight gradient
       Pd.need = w.fneed;
       Pd.need_ld = w.fneed_ld;
     }

@@ -24,26 +24,20 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 32;   // reduction depth staged per LDS slab
 // background-row lists (C1Lists): regions per list (one per XCD) and the counter stride (128 bytes)
-#ifndef QLX_LIST_SLOTS
-#define QLX_LIST_SLOTS 8   // (A/B builds only: scripts/build_variant.sh -DQLX_LIST_SLOTS=n)
-#endif
-constexpr int kListSlots = QLX_LIST_SLOTS;
+constexpr int kListSlots = 8;
 constexpr int kCntStride = 16;   // [region][layer] at (region * 2 + layer) * kCntStride
 
-// Operand tile in LDS for MFMA shape MF (16: v_mfma_f32_16x16x4_f32, 32: v_mfma_f32_32x32x2_f32).  RMAJ: t[row][k]
-// (pitch BK + 4); KMAJ: t[k][row] (pitch = rows padded to MF mod 64, so the MF rows x (64 / MF) k of a fragment read
-// hit distinct banks).  Writes are 16-byte float4 along the operand's contiguous source dimension.
-// MF 16: the four lane groups of a fragment read k rows 0..3 of the image, i.e. offsets 0, p, 2p, 3p: any p = 16 or
+// Operand tile in LDS for v_mfma_f32_16x16x4_f32.  RMAJ: t[row][k] (the P8 image below); KMAJ: t[k][row] (pitch = rows
+// padded to 16 or 48 mod 64, so the 16 rows x 4 k of a fragment read hit distinct banks).  KMAJ writes are 16-byte float4
+// along the operand's contiguous source dimension.
+// The four lane groups of a KMAJ fragment read k rows 0..3 of the image, i.e. offsets 0, p, 2p, 3p: any p = 16 or
 // 48 mod 64 puts them on four disjoint 16-bank ranges; the smallest such p >= rows (32 rows: 48, not 80, which lets
-// one more block per CU fit).  MF 32: two lane groups, p = 32 mod 64.
-__host__ __device__ constexpr int kmaj_pitch_min(int rows, int mf) { return rows + (((mf - rows % 64) % 64) + 64) % 64; }
-__host__ __device__ constexpr int kmaj_pitch(int rows, int mf) {
-  return mf == 16 && rows + ((48 - rows % 64) % 64 + 64) % 64 < kmaj_pitch_min(rows, mf)
-             ? rows + ((48 - rows % 64) % 64 + 64) % 64
-             : kmaj_pitch_min(rows, mf);
+// one more block per CU fit).
+__host__ __device__ constexpr int kmaj_pad(int rows, int r) { return rows + ((r - rows % 64) % 64 + 64) % 64; }   // >= rows, = r mod 64
+__host__ __device__ constexpr int kmaj_pitch(int rows) {
+  return kmaj_pad(rows, 48) < kmaj_pad(rows, 16) ? kmaj_pad(rows, 48) : kmaj_pad(rows, 16);
 }
-static_assert(kmaj_pitch(32, 16) == 48 && kmaj_pitch(64, 16) == 80 && kmaj_pitch(128, 16) == 144 && kmaj_pitch(64, 32) == 96,
-              "KMAJ pitches");
+static_assert(kmaj_pitch(32) == 48 && kmaj_pitch(64) == 80 && kmaj_pitch(128) == 144, "KMAJ pitches");
 
 // RMAJ images of the 16x16x4 MFMA (P8, round 6): lane l of a fragment read needs (row r0 + l % 16, k = 4 kk + l / 16) at
 // k step kk, so over one slab a lane reads k = g, g + 4, .., g + 28 (g = l / 16).  The image stores a row's 32 k at the
@@ -52,18 +46,14 @@ static_assert(kmaj_pitch(32, 16) == 48 && kmaj_pitch(64, 16) == 80 && kmaj_pitch
 // as before - the chains, and so every result, are unchanged.  The chunk index is XORed with row & 1 and the pitch is
 // 40 floats: with the ds_read_b128 lane groups of MI355X_MICROARCH.md §LDS every fragment read is conflict-free, and so
 // are the stores, which become four ds_write_b32 per float4 of k (positions 8 q + j, q = 0..3, for the float4 j of a row)
-// (scripts/p8_layout_search.py checks both).  Before: pitch 36 and one ds_read_b32 per k step and fragment, 2-way
-// conflicted (rows i and i + 8 share a bank; a k-pair swap for rows 8..15 that removed it measured slower in round 3).
-#ifndef QLX_Q32_P8
-#define QLX_Q32_P8 1   // (A/B builds: -DQLX_Q32_P8=0 restores the round-5 pitch-36 image and ds_read_b32 fragments)
-#endif
-template <int ROWS, bool KMAJ, int MF = 16>
+// (scripts/p8_layout_search.py checks both).  (Until round 5: pitch 36 and one ds_read_b32 per k step and fragment, 2-way
+// conflicted - rows i and i + 8 share a bank; DESIGN.md has the numbers.)
+template <int ROWS, bool KMAJ>
 struct Opnd {
-  static constexpr bool P8 = QLX_Q32_P8 && !KMAJ && MF == 16;
-  static constexpr int PITCH = KMAJ ? kmaj_pitch(ROWS, MF) : P8 ? BK + 8 : BK + 4;
+  static constexpr bool P8 = !KMAJ;
+  static constexpr int PITCH = KMAJ ? kmaj_pitch(ROWS) : BK + 8;
   static constexpr int FLOATS = KMAJ ? BK * PITCH : ROWS * PITCH;
   static constexpr int F4 = ROWS * BK / 4;   // float4 per slab
-  static constexpr int KG = 64 / MF;         // k per MFMA (lane groups)
   __host__ __device__ static void coord(int idx, int& row, int& k) {
     if (KMAJ) { k = idx / (ROWS / 4); row = (idx % (ROWS / 4)) * 4; }
     else { row = idx >> 3; k = (idx & 7) * 4; }
@@ -78,15 +68,15 @@ struct Opnd {
 #pragma unroll
       for (int q = 0; q < 4; ++q) t[o + 4 * ((2 * q + (j >> 2)) ^ x)] = v[q];
     } else {
-      *reinterpret_cast<f32x4*>(t + (KMAJ ? k * PITCH + row : row * PITCH + k)) = v;
+      *reinterpret_cast<f32x4*>(t + (k * PITCH + row)) = v;
     }
   }
   __device__ static float at(const float* t, int row, int k) {
     if constexpr (P8) return t[p8_off(row, k)];
-    return KMAJ ? t[k * PITCH + row] : t[row * PITCH + k];
+    return t[k * PITCH + row];
   }
-  // MFMA operand of the MF rows from r0, k step kk: lane l holds (r0 + l % MF, KG kk + l / MF)
-  __device__ static float frag(const float* t, int r0, int kk, int lane) { return at(t, r0 + (lane & (MF - 1)), KG * kk + lane / MF); }
+  // MFMA operand of the 16 rows from r0, k step kk: lane l holds (r0 + l % 16, 4 kk + l / 16)
+  __device__ static float frag(const float* t, int r0, int kk, int lane) { return at(t, r0 + (lane & 15), 4 * kk + lane / 16); }
   // P8: the operands of k steps 4 h .. 4 h + 3 of the slab (element q = k step 4 h + q): one ds_read_b128
   __device__ static f32x4 frag4(const float* t, int r0, int h, int lane) {
     const int row = r0 + (lane & 15);
@@ -95,7 +85,7 @@ struct Opnd {
 };
 
 // One slab's MFMA chains of a wave's TM x TN fragments (k steps in ascending order; P8 operands read four k steps per
-// ds_read_b128, the others one ds_read_b32 per k step).  bsum (DB): the B fragments' running column sums (bias chains).
+// ds_read_b128, KMAJ operands one ds_read_b32 per k step).  bsum (DB): the B fragments' running column sums (bias chains).
 template <class OA, class OB, int TM, int TN, bool DB, class Acc>
 __device__ __forceinline__ void slab_mfma16(const float* a, const float* b, int wm, int wn, int lane, Acc (&acc)[TM][TN],
                                             float (&bsum)[TN], bool do_bias = true) {
@@ -149,18 +139,6 @@ struct KSeqOf : std::integral_constant<int, 1> {};
 template <class P>
 struct KSeqOf<P, std::void_t<decltype(P::KSEQ)>> : std::integral_constant<int, P::KSEQ> {};
 
-// MFMA shape of a policy: its member MF when it has one, else 16
-template <class P, class = void>
-struct MfOf : std::integral_constant<int, 16> {};
-template <class P>
-struct MfOf<P, std::void_t<decltype(P::MF)>> : std::integral_constant<int, P::MF> {};
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int MF>
-struct MfAcc { typedef f32x4 type; };
-template <>
-struct MfAcc<32> { typedef f32x16 type; };
-
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // Masked operand load for the policies: masked lanes load 16 zero bytes from q32_zero4, so the load is issued on every
@@ -209,11 +187,9 @@ __device__ __forceinline__ int xcd_logical(int b, int G) {
 // conv2 / conv3 forward 61.5 / 46.1 -> 58.0 / 43.7 us, the fc1 / conv2 backward pairs 73.3 / 117.1 -> 69.5 / 112.9 us,
 // the chunk-size conv3 forward 281.5 -> 272 us (strategy 0 for all: 1-4 % slower than 1 on these); the fc1 forward runs
 // slower with strategy 1 and best with 0 (PFc1FwdT); the conv1 kernels' MFMA loops gain nothing from either.
-#ifndef QLX_IGLP_DEFAULT
-#define QLX_IGLP_DEFAULT 1   // (A/B builds: the strategy of the policies without an IGLP member)
-#endif
+constexpr int kIglpDefault = 1;   // the strategy of the policies without an IGLP member
 template <class P, class = void>
-struct IglpOf : std::integral_constant<int, QLX_IGLP_DEFAULT> {};
+struct IglpOf : std::integral_constant<int, kIglpDefault> {};
 template <class P>
 struct IglpOf<P, std::void_t<decltype(P::IGLP)>> : std::integral_constant<int, P::IGLP> {};
 
@@ -244,7 +220,7 @@ struct ACtxOf { using type = NoCtx; };
 template <class P>
 struct ACtxOf<P, true> { using type = typename P::ACtx; };
 
-// Optional early epilogue operands (MF 16 policies): a policy with epi_pre(z, row, col) -> f32x4 (e.g. the ReLU mask
+// Optional early epilogue operands: a policy with epi_pre(z, row, col) -> f32x4 (e.g. the ReLU mask
 // values of its four rows) and epi_post(z, row, col, acc, pre) has epi_pre's loads issued before the slab loop, so the
 // epilogue waits on nothing (a load issued after the loop would wait behind every slab load still in flight).
 template <class P, class = void>
@@ -272,10 +248,10 @@ struct HasActive<P, std::void_t<decltype(std::declval<const P&>().active(0, 0))>
 // through LDS before its epilogue (ns must be a multiple of G).
 template <class P>
 __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
-  constexpr int MF = MfOf<P>::value;
-  using OA = Opnd<P::BM, P::A_KMAJ, MF>;
-  using OB = Opnd<P::BN, P::B_KMAJ, MF>;
-  using Acc = typename MfAcc<MF>::type;
+  constexpr int MF = 16;
+  using OA = Opnd<P::BM, P::A_KMAJ>;
+  using OB = Opnd<P::BN, P::B_KMAJ>;
+  using Acc = f32x4;
   constexpr int G = KSplitOf<P>::value;
   static_assert(G == 1 || !P::BIAS, "K-split groups: no bias chains");
   constexpr int T = P::WM * P::WN * 64;   // threads of one K group
@@ -283,7 +259,7 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
   static_assert(TM >= 1 && TN >= 1 && TM * P::WM * MF == P::BM && TN * P::WN * MF == P::BN, "tile shape");
   constexpr int NA = (OA::F4 + T - 1) / T, NB = (OB::F4 + T - 1) / T;
   constexpr int GROUP_LDS = 2 * (OA::FLOATS + OB::FLOATS);
-  static_assert(G == 1 || TM * TN * (MF * MF / 64) * T <= GROUP_LDS, "K-split hand-off fits the group's LDS");
+  static_assert(G == 1 || TM * TN * 4 * T <= GROUP_LDS, "K-split hand-off fits the group's LDS");
   const int kg = G > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6) / (P::WM * P::WN)) : 0;
   const int tid = threadIdx.x - kg * T, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -296,7 +272,7 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
   }
   const int ns = p.nslabs(z) / G, s_base = kg * ns;   // this group's slabs: s_base + [0, ns)
   constexpr int Q = KSeqOf<P>::value;   // (KSEQ: see gemm_body_s)
-  static_assert(Q == 1 || (Q == 2 && G == 1 && MF == 16 && !P::BIAS), "sequential K split: two chains, 16x16x4, no bias");
+  static_assert(Q == 1 || (Q == 2 && G == 1 && !P::BIAS), "sequential K split: two chains, no bias");
   const int s_half = Q > 1 ? ns / 2 : -1;
   typename ACtxOf<P>::type actx{};
   if constexpr (HasACtx<P>::value) actx = p.a_ctx(z, row0, tid);
@@ -357,10 +333,10 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int e = 0; e < MF * MF / 64; ++e) acc[i][j][e] = 0.0f;
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
   Acc first[Q > 1 ? TM : 1][Q > 1 ? TN : 1];   // KSEQ: the finished first chain
-  // bias (BIAS policies, row-tile 0): column sums of B as KG interleaved chains - lane group q of the wave's B fragments
-  // chains the k = q mod KG rows - combined in group order at the end
+  // bias (BIAS policies, row-tile 0): column sums of B as four interleaved chains - lane group q of the wave's B fragments
+  // chains the k = q mod 4 rows - combined in group order at the end
   float bsum[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) bsum[j] = 0.0f;
@@ -380,25 +356,7 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
       }
     }
     if constexpr (IglpOf<P>::value >= 0) __builtin_amdgcn_iglp_opt(IglpOf<P>::value);
-    if constexpr (MF == 16) {
-      slab_mfma16<OA, OB, TM, TN, P::BIAS>(a, b, wm, wn, lane, acc, bsum, do_bias);
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < BK / OA::KG; ++kk) {
-        float af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = OA::frag(a, (wm * TM + i) * MF, kk, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = OB::frag(b, (wn * TN + j) * MF, kk, lane);
-        if (P::BIAS && do_bias)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) bsum[j] = __fadd_rn(bsum[j], bf[j]);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-    }
+    slab_mfma16<OA, OB, TM, TN, P::BIAS>(a, b, wm, wn, lane, acc, bsum, do_bias);
   };
   // iteration s: x holds slab s + 1, y is free.  Every iteration issues its loads unconditionally (the last slab again
   // past the end), so the number of loads in flight is the same on every path and the store of slab s + 1 waits only
@@ -410,7 +368,7 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
     store(s + 1, xa, xb);   // unconditional, as in gemm_body_s (past the last slab: the idle buffer, never read)
     lds_barrier();
   };
-  constexpr bool PRE = HasEpiPre<P>::value && MF == 16;
+  constexpr bool PRE = HasEpiPre<P>::value;
   typename PreOf<P>::type pre[TM][TN];
   if constexpr (PRE) {
     if (kg == 0) {   // (K groups: group 0 runs the epilogue)
@@ -442,7 +400,7 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
         for (int e = 0; e < 4; ++e) acc[i][j][e] = __fadd_rn(ns > s_half ? first[i][j][e] : acc[i][j][e], ns > s_half ? acc[i][j][e] : 0.0f);
   }
   if constexpr (G > 1) {   // groups 1 .. G - 1 hand their accumulators to group 0 through their own LDS (free now)
-    constexpr int E = MF * MF / 64;
+    constexpr int E = 4;
     if (kg > 0) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -462,216 +420,24 @@ __device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
 #pragma unroll
           for (int e = 0; e < E; ++e) acc[i][j][e] = __fadd_rn(acc[i][j][e], lds[g * GROUP_LDS + ((i * TN + j) * E + e) * T + tid]);
   }
-  // accumulator layout: MF 16: lane l holds rows 4 (l / 16) .. + 3 of column l % 16; MF 32: element 4 q + e is row
-  // 8 q + 4 (l / 32) + e of column l % 32
+  // accumulator layout: lane l holds rows 4 (l / 16) .. + 3 of column l % 16
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       if constexpr (PRE) {
         p.epi_post(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), acc[i][j], pre[i][j]);
-      } else if constexpr (MF == 16) {
-        p.epi(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), acc[i][j]);
       } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          p.epi(z, row0 + (wm * TM + i) * 32 + 8 * q + 4 * (lane >> 5), col0 + (wn * TN + j) * 32 + (lane & 31),
-                f32x4{acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]});
+        p.epi(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), acc[i][j]);
       }
     }
   if constexpr (P::BIAS) {
     if (do_bias) {
-      static_assert(MF == 16, "bias chains: 16x16x4 fragments");
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const float c1 = __shfl(bsum[j], lane + 16), c2 = __shfl(bsum[j], lane + 32), c3 = __shfl(bsum[j], lane + 48);
         if (lane < 16) p.epi_bias(z, col0 + (wn * TN + j) * 16 + lane, __fadd_rn(__fadd_rn(__fadd_rn(bsum[j], c1), c2), c3));
       }
-    }
-  }
-}
-
-// Chained sub-tiles: one block runs the tiles (tm, tn, z_0), (tm, tn, z_1), .. of its group zg = the z grid index
-// (P::sub_count(zg) <= P::NSUB sub-tiles, z_i = P::sub_z(zg, i)) as ONE slab pipeline over the concatenated slabs: the
-// loads of a sub-tile's first slabs are in flight while the previous sub-tile's last slabs are multiplied, and at a
-// sub-tile's last slab its accumulators go through P::epi and restart from zero.  Each output is still one chain over its
-// own tile's slabs in order, so the results equal gemm_body's on the same tiles bit for bit.  For short-K tiles (pixel-major
-// backward data: 1..9 valid taps) this removes the per-tile pipeline ramp and epilogue wait that dominate a short tile.
-// The sub-tile queue is kept as shifting scalars (no runtime-indexed arrays or captured references: those end up in
-// scratch memory): a load cursor and an epilogue cursor each advance through (z_i, end slab e_i) in order.
-// (gemm_body_chain) the streams type of a policy, or an empty placeholder
-template <class P, class = void>
-struct HasStreamsC : std::false_type {};
-#ifndef QLX_Q32_NO_STREAMS
-template <class P>
-struct HasStreamsC<P, std::void_t<typename P::Streams>> : std::bool_constant<!std::is_void_v<typename P::Streams>> {};
-#endif
-struct NoStreams { struct Regs {}; };
-template <class P, bool = HasStreamsC<P>::value>
-struct StreamsOf { using type = NoStreams; };
-template <class P>
-struct StreamsOf<P, true> { using type = typename P::Streams; };
-template <class P>
-struct StreamsRegsOf { using type = typename StreamsOf<P>::type::Regs; };
-
-struct ChainQ {
-  int z0, e0, z1, e1, z2, e2, z3, e3;
-  __device__ __forceinline__ void pop() { z0 = z1; e0 = e1; z1 = z2; e1 = e2; z2 = z3; e2 = e3; }
-};
-template <class P>
-__device__ __forceinline__ void gemm_body_chain(const P& p, int lb, float* lds) {
-  constexpr int MF = 16;
-  using OA = Opnd<P::BM, P::A_KMAJ, MF>;
-  using OB = Opnd<P::BN, P::B_KMAJ, MF>;
-  static_assert(KSplitOf<P>::value == 1 && !P::BIAS && !HasACtx<P>::value, "chained tiles: plain policies");
-  static_assert(P::NSUB == 4, "chained tiles: up to four sub-tiles");
-  constexpr int T = P::WM * P::WN * 64;
-  constexpr int TM = P::BM / (P::WM * MF), TN = P::BN / (P::WN * MF);
-  static_assert(TM >= 1 && TN >= 1 && TM * P::WM * MF == P::BM && TN * P::WN * MF == P::BN, "tile shape");
-  constexpr int NA = (OA::F4 + T - 1) / T, NB = (OB::F4 + T - 1) / T;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave % P::WM, wn = wave / P::WM;
-  int tm, tn, zg;
-  p.decode(lb, tm, tn, zg);
-  const int row0 = tm * P::BM, col0 = tn * P::BN;
-  const int nsub = p.sub_count(zg);
-  ChainQ q;
-  q.z0 = p.sub_z(zg, 0);
-  q.z1 = nsub > 1 ? p.sub_z(zg, 1) : q.z0;
-  q.z2 = nsub > 2 ? p.sub_z(zg, 2) : q.z0;
-  q.z3 = nsub > 3 ? p.sub_z(zg, 3) : q.z0;
-  q.e0 = p.nslabs(q.z0);
-  q.e1 = q.e0 + (nsub > 1 ? p.nslabs(q.z1) : 0);
-  q.e2 = q.e1 + (nsub > 2 ? p.nslabs(q.z2) : 0);
-  q.e3 = q.e2 + (nsub > 3 ? p.nslabs(q.z3) : 0);
-  const int ns = q.e3;
-  ChainQ lq = q, fq = q;   // load cursor, epilogue cursor
-  int lbase = 0;           // first slab of lq's current sub-tile
-  float* As0 = lds;
-  float* As1 = lds + OA::FLOATS;
-  float* Bs0 = lds + 2 * OA::FLOATS;
-  float* Bs1 = Bs0 + OB::FLOATS;
-  // slab staging: the policy's streams (lane offsets per block; a sub-tile's slab offsets on the scalar unit) or ldA / ldB
-  constexpr bool STR = HasStreamsC<P>::value;
-  using St = typename StreamsOf<P>::type;
-  St st{};
-  if constexpr (STR) st = p.streams(0, row0, col0, tid);
-  struct RegsL { f32x4 a[NA], b[NB]; };
-  using Regs = std::conditional_t<STR, typename StreamsRegsOf<P>::type, RegsL>;
-  Regs x0, x1;
-  // slab s of the concatenation (s never decreases between calls; past the end the last slab again)
-  auto load = [&](int s, Regs& x) {
-    if (s >= lq.e0 && s < ns) {
-      lbase = lq.e0;
-      lq.pop();
-    }
-    const int z = lq.z0, sl = s - lbase;
-    if constexpr (STR) {
-      st.load_z(z, sl, x);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int idx = tid + i * T;
-        if (OA::F4 % T == 0 || idx < OA::F4) {
-          int r, k;
-          OA::coord(idx, r, k);
-          x.a[i] = p.ldA(z, sl, row0 + r, k);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int idx = tid + i * T;
-        if (OB::F4 % T == 0 || idx < OB::F4) {
-          int r, k;
-          OB::coord(idx, r, k);
-          x.b[i] = p.ldB(z, sl, col0 + r, k);
-        }
-      }
-    }
-  };
-  auto store = [&](int s, const Regs& x) {
-    float* as = (s & 1) ? As1 : As0;
-    float* bs = (s & 1) ? Bs1 : Bs0;
-    if constexpr (STR) {
-      st.store(as, bs, x);
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int idx = tid + i * T;
-        if (OA::F4 % T == 0 || idx < OA::F4) {
-          int r, k;
-          OA::coord(idx, r, k);
-          OA::put(as, r, k, x.a[i]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int idx = tid + i * T;
-        if (OB::F4 % T == 0 || idx < OB::F4) {
-          int r, k;
-          OB::coord(idx, r, k);
-          OB::put(bs, r, k, x.b[i]);
-        }
-      }
-    }
-  };
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = zero4();
-  auto compute = [&](int s) {
-    const float* a = (s & 1) ? As1 : As0;
-    const float* b = (s & 1) ? Bs1 : Bs0;
-    if constexpr (IglpOf<P>::value >= 0) __builtin_amdgcn_iglp_opt(IglpOf<P>::value);
-    float nobias[TN];
-    slab_mfma16<OA, OB, TM, TN, false>(a, b, wm, wn, lane, acc, nobias);
-  };
-  constexpr bool PRE = HasEpiPre<P>::value;
-  f32x4 pre[TM][TN];
-  auto fetch_pre = [&](int z) {
-    if constexpr (PRE) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          pre[i][j] = p.epi_pre(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15));
-    }
-  };
-  // after slab s: the epilogue of a sub-tile ending there, fresh accumulators (and the next sub-tile's early operands)
-  auto flush = [&](int s) {
-    if (s + 1 != fq.e0) return;
-    const int z = fq.z0;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col = col0 + (wn * TN + j) * 16 + (lane & 15);
-        if constexpr (PRE) p.epi_post(z, row, col, acc[i][j], pre[i][j]);
-        else p.epi(z, row, col, acc[i][j]);
-        acc[i][j] = zero4();
-      }
-    fq.pop();
-    if (s + 1 < ns) fetch_pre(fq.z0);
-  };
-  auto iter = [&](int s, Regs& xs, Regs& ys) {
-    load(s + 2 < ns ? s + 2 : ns - 1, ys);
-    if constexpr (LoadFenceOf<P>::value) __builtin_amdgcn_sched_barrier(0);
-    compute(s);
-    flush(s);
-    if (s + 1 < ns) store(s + 1, xs);
-    lds_barrier();
-  };
-  fetch_pre(q.z0);
-  if (ns > 0) {
-    load(0, x1);
-    store(0, x1);
-    load(ns > 1 ? 1 : 0, x0);
-    lds_barrier();
-    for (int s = 0; s < ns; s += 2) {
-      iter(s, x0, x1);
-      if (s + 1 < ns) iter(s + 1, x1, x0);
     }
   }
 }
@@ -730,7 +496,7 @@ __device__ __forceinline__ float buf_ld1(__amdgpu_buffer_rsrc_t r, uint32_t voff
 // k is at or past the slab's valid count read zeros (a partial last slab of a reduction along k).
 template <int ROWS, bool KMAJ, int T, bool KMASK = false>
 struct AffineStream {
-  using O = Opnd<ROWS, KMAJ, 16>;
+  using O = Opnd<ROWS, KMAJ>;
   static constexpr int N = (O::F4 + T - 1) / T;
   using Regs = f32x4[N];
   __amdgpu_buffer_rsrc_t rs;
@@ -807,7 +573,7 @@ struct PairStreams {
 template <int T, bool PADS = true, int SHIFT = 0, uint32_t MASK = 0xFFFFFFFFu, uint32_t MUL = 1u>
 struct TableK4Stream {
   static_assert(T == 256, "table gather stream: four waves");
-  using O = Opnd<64, true, 16>;
+  using O = Opnd<64, true>;
   static constexpr int N = 2;   // float4 loads per thread per slab
   using Regs = f32x4[N];
   __amdgpu_buffer_rsrc_t rs;
@@ -817,7 +583,7 @@ struct TableK4Stream {
   // entry r of the table: 16-entry segment r / 16 in the pad columns 64 .. 79 of k-row (r / 16) % 32 of image r / 512 (the
   // four 64-row KMAJ images - A and B, two buffers each - are contiguous, 2,560 floats each; no fragment read or slab store
   // touches a pad), so the table costs no LDS and the launch keeps four blocks per CU
-  static constexpr int IMG = Opnd<64, true, 16>::FLOATS, PITCH = Opnd<64, true, 16>::PITCH;
+  static constexpr int IMG = Opnd<64, true>::FLOATS, PITCH = Opnd<64, true>::PITCH;
   static_assert(PITCH == 80, "table stream: 16 pad columns per k-row");
   // (PADS = false: the table follows the four images, entry r at 4 IMG + r - the launch then needs EXTRA_LDS)
   __host__ __device__ static int slot(int r) { return PADS ? (r >> 9) * IMG + ((r >> 4) & 31) * PITCH + 64 + (r & 15) : 4 * IMG + r; }
@@ -853,7 +619,7 @@ struct HasPrepare<S, std::void_t<decltype(std::declval<S&>().prepare((float*)nul
 template <class P>
 constexpr size_t gemm_lds_bytes() {
   return (size_t)KSplitOf<P>::value * 2 *
-             (size_t)(Opnd<P::BM, P::A_KMAJ, MfOf<P>::value>::FLOATS + Opnd<P::BN, P::B_KMAJ, MfOf<P>::value>::FLOATS) * sizeof(float) +
+             (size_t)(Opnd<P::BM, P::A_KMAJ>::FLOATS + Opnd<P::BN, P::B_KMAJ>::FLOATS) * sizeof(float) +
          ExtraLdsOf<P>::value;
 }
 
@@ -861,12 +627,11 @@ constexpr size_t gemm_lds_bytes() {
 // and epilogue, with the slab staging done by the policy's streams:
 //   typename P::Streams st = p.streams(z, row0, col0, tid);   per tile
 //   st.load(s, x) / st.store(s, x, As, Bs)                    x: a P::Streams::Regs register set
+// (a policy whose Streams is void - a tile shape its streams do not cover - stays on the ldA / ldB core)
 template <class P, class = void>
 struct HasStreams : std::false_type {};
-#ifndef QLX_Q32_NO_STREAMS   // (A/B builds of the measurement harnesses: every policy on the ldA / ldB core)
 template <class P>
 struct HasStreams<P, std::void_t<typename P::Streams>> : std::bool_constant<!std::is_void_v<typename P::Streams>> {};
-#endif
 
 // K split (round 6, policies with KSPLIT = G > 1 or KSEQ = Q > 1): the reduction is G (Q) chains over consecutive equal
 // slab ranges, combined ((C0 + C1) + ..) before the epilogue - the same value either way: KSPLIT runs the chains in G
@@ -875,8 +640,8 @@ struct HasStreams<P, std::void_t<typename P::Streams>> : std::bool_constant<!std
 template <class P>
 __device__ __forceinline__ void gemm_body_s(const P& p, int lb, float* lds) {
   constexpr int MF = 16;
-  using OA = Opnd<P::BM, P::A_KMAJ, MF>;
-  using OB = Opnd<P::BN, P::B_KMAJ, MF>;
+  using OA = Opnd<P::BM, P::A_KMAJ>;
+  using OB = Opnd<P::BN, P::B_KMAJ>;
   using Acc = f32x4;
   constexpr int TM = P::BM / (P::WM * MF), TN = P::BN / (P::WN * MF);
   static_assert(TM >= 1 && TN >= 1 && TM * P::WM * MF == P::BM && TN * P::WN * MF == P::BN, "tile shape");
@@ -1031,15 +796,9 @@ __device__ __forceinline__ void gemm_body_s(const P& p, int lb, float* lds) {
   }
 }
 
-// a policy with NSUB (chained sub-tiles per block) runs gemm_body_chain
-template <class P, class = void>
-struct HasChain : std::false_type {};
-template <class P>
-struct HasChain<P, std::void_t<decltype(P::NSUB)>> : std::true_type {};
 template <class P>
 __device__ __forceinline__ void body(const P& p, int lb, float* lds) {
-  if constexpr (HasChain<P>::value) gemm_body_chain(p, lb, lds);
-  else if constexpr (HasStreams<P>::value) gemm_body_s(p, lb, lds);
+  if constexpr (HasStreams<P>::value) gemm_body_s(p, lb, lds);
   else gemm_body(p, lb, lds);
 }
 
@@ -1051,13 +810,11 @@ __global__ __launch_bounds__(threads_of<P>()) void k_gemm32(const P p) {
 
 // two independent GEMMs in one grid (hardware blocks [side.blocks(), side.blocks() + G1) run P1), plus `side` leading
 // blocks running S and `tail` trailing blocks running T (independent work that fills CU slots beside / after the tiles)
-// Occupancy floor of a pair launch (waves per SIMD the register allocation must allow): the larger of QLX_PAIR_MINW and
+// Occupancy floor of a pair launch (waves per SIMD the register allocation must allow): kPairMinW, or the larger of
 // the policies' MINW members.  Round 6: the P8 fragments' b128 reads let the compiler hoist a whole slab's operands; at
 // the default allocation the conv2 pair grew 112 -> 154 VGPRs (3 waves / SIMD, 95.0 -> 98.0 us); held to 4 waves it
 // takes 106 VGPRs (93.4 us).
-#ifndef QLX_PAIR_MINW
-#define QLX_PAIR_MINW 4
-#endif
+constexpr int kPairMinW = 4;
 template <class P, class = void>
 struct MinWOf : std::integral_constant<int, 1> {};
 template <class P>
@@ -1066,12 +823,12 @@ template <class P, class = void>
 struct HasMinW : std::false_type {};
 template <class P>
 struct HasMinW<P, std::void_t<decltype(P::MINW)>> : std::true_type {};
-// the policies' own floors when either declares one (the larger), else QLX_PAIR_MINW
+// the policies' own floors when either declares one (the larger), else kPairMinW
 template <class P1, class P2>
 constexpr int pair_minw() {
   return (HasMinW<P1>::value || HasMinW<P2>::value)
              ? (MinWOf<P1>::value > MinWOf<P2>::value ? MinWOf<P1>::value : MinWOf<P2>::value)
-             : QLX_PAIR_MINW;
+             : kPairMinW;
 }
 template <class P1, class P2, class S, class T>
 __global__ __launch_bounds__(256, (pair_minw<P1, P2>())) void k_gemm32_pair(const P1 p1, const P2 p2, const S side, const T tail) {
@@ -1136,21 +893,17 @@ struct NoSide {
 //   conv dgrad      k = (kh, kw, oc) over the valid taps                                   fc1 dgrad   k = n
 //   weight grads    r = (b, oh, ow) ascending inside a sample chunk; fc1 / fc2 over b ascending, no chunks
 
-// conv2 / conv3 forward chains: z = C0 + C1, Ch = chain over the k = (kh, kw, c) half h (conv2: taps
-// 0..7 / 8..15; conv3: k < 288 / the rest), so that the training-batch list launch can run the two chains in two wave groups
-// of a block (KSPLIT); the chunk-batch launches run them one after the other (KSEQ)
-#ifndef QLX_CONV_FWD_CHAINS
-#define QLX_CONV_FWD_CHAINS 1   // (2 measured slower, round 6: conv3 forward 26.4 -> 29.5 us in wave groups, the chunk pass 166 -> 175 us in turn; the oracle follows this value)
-#endif
+// conv2 / conv3 forward chains: one chain over k = (kh, kw, c), the value the oracle follows.  (Two chains
+// over the k halves, in wave groups or in turn, measured slower in round 6: conv3 forward 26.4 -> 29.5 us, the chunk pass
+// 166 -> 175 us; DESIGN.md.)  The conv forward policies below carry no K split.
+#define QLX_CONV_FWD_CHAINS 1
 constexpr int kConvFwdChains = QLX_CONV_FWD_CHAINS;
+static_assert(kConvFwdChains == 1, "conv forward policies: one chain per output");
 // conv2 / conv3 forward on fp32 NHWC input: out = relu(conv + bias); slab s: tap = 32 s / C, c0 = 32 s % C
-template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2,
-          int MF_ = 16>
+template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2>
 struct PConvFwd {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
-  static constexpr int KSEQ = kConvFwdChains;
-  static constexpr int MINW = 3;   // (pair launches of the dense forward: the finished first chain's registers, no spill)
-  static_assert(MF_ == 16, "conv forward chains: 16x16x4");
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+  static constexpr int MINW = 3;   // (pair launches of the dense forward)
   static constexpr bool LOAD_FENCE = !(H == 20 && BN_ == 64);   // the chunk-size conv2 forward runs without it
   static constexpr bool A_KMAJ = false, B_KMAJ = true, BIAS = false;
   Grid g;
@@ -1213,17 +966,15 @@ using PConv3FwdR = RowShift<PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 16, 64, 1, 4>>;
 // background in the layer below (list entry bits 20..28, written by conv1) read cx = that layer's constant row instead of
 // `in` (those rows are written by this launch's side blocks).
 template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2,
-          bool SEL = false, int KS_ = 1>
+          bool SEL = false>
 struct PConvFwdL {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
-  static constexpr int KSPLIT = KS_, KSEQ = kConvFwdChains / KS_;   // the two chains in wave groups (KS_ = 2) or in turn
-  static_assert(KSPLIT * KSEQ == kConvFwdChains, "conv forward: the chain definition");
   static constexpr bool A_KMAJ = false, B_KMAJ = true, BIAS = false, RAW_ORDER = true;
   // (with the slab loop's wait fixed, round 5: the fence on for conv2 too - the 8,192-sample pass 131 -> 127 us)
   static constexpr bool LOAD_FENCE = true;
   static constexpr int R = OH * OW;
-  using OA = Opnd<BM, false, 16>;
-  static constexpr int T = WM * WN * 64, NA = (OA::F4 + T - 1) / T;   // (T: threads of one K group)
+  using OA = Opnd<BM, false>;
+  static constexpr int T = WM * WN * 64, NA = (OA::F4 + T - 1) / T;
   Grid g;            // tiles_m = 1 + kListSlots * tiles per region
   const float* in;
   const float* w;    // [KS][KS][C][OC]
@@ -1316,9 +1067,6 @@ struct PConvFwdL {
   __device__ void epi_post(int, int, int col, f32x4 v, const Pre& q) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#ifdef QLX_LIST_CHECK
-      if (q.o[r] >= 0 && (q.o[r] & 0xFFFFF) >= kListSlots * cap) printf("LISTCHK epi o %d cap %d\n", q.o[r], cap);
-#endif
       if (q.o[r] >= 0) out[(size_t)(q.o[r] & 0xFFFFF) * OC + col] = relu(v[r] + q.b);
       else if (q.o[r] == -2) cbuf[col] = relu(v[r] + q.b);
     }
@@ -1396,10 +1144,10 @@ struct PConvFwdL {
     return st;
   }
 };
-template <int BM, int BN, int WM, int WN, int KS_ = 1>
-using PConv2FwdL = PConvFwdL<20, 20, 32, 4, 2, 9, 9, 64, BM, BN, WM, WN, false, KS_>;
-template <int BM, int BN, int WM, int WN, int KS_ = 1>
-using PConv3FwdL = PConvFwdL<9, 9, 64, 3, 1, 7, 7, 64, BM, BN, WM, WN, true, KS_>;
+template <int BM, int BN, int WM, int WN>
+using PConv2FwdL = PConvFwdL<20, 20, 32, 4, 2, 9, 9, 64, BM, BN, WM, WN, false>;
+template <int BM, int BN, int WM, int WN>
+using PConv3FwdL = PConvFwdL<9, 9, 64, 3, 1, 7, 7, 64, BM, BN, WM, WN, true>;
 
 // The constant rows as the first block of the conv2 launch: the conv2 constant row (input relu(0 + b0) -> c2), then, from
 // c2, the conv3 constant row (-> c3), each as the constant-row tile of a 16 x 64 list policy (4 waves x 16 channels, the
@@ -1436,10 +1184,6 @@ struct BgRows {
     const f32x4 v = ld4(c_in + 4 * q);
     for (int x = 0; x < kListSlots; ++x) {
       const int nbg = (int)(uint32_t)cnt[x * 2 * kCntStride];
-#ifdef QLX_LIST_CHECK
-      if (tid == 0 && blk == 0 && (nbg > cap || (int)(cnt[x * 2 * kCntStride] >> 32) + nbg > cap))
-        printf("LISTCHK bgrows region %d nbg %d non %d cap %d\n", x, nbg, (int)(cnt[x * 2 * kCntStride] >> 32), cap);
-#endif
       const int* back = list + (size_t)(x + 1) * cap - 1;
       for (int i0 = blk * RB * U + (tid >> 4); i0 < nbg; i0 += nblk * RB * U) {
         int e[U];
@@ -1447,12 +1191,7 @@ struct BgRows {
         for (int u = 0; u < U; ++u) e[u] = i0 + RB * u < nbg ? back[-(i0 + RB * u)] : -1;
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (e[u] >= 0) {
-#ifdef QLX_LIST_CHECK
-            if (e[u] >= kListSlots * cap && q == 0) printf("LISTCHK bgrows e %d cap %d region %d i %d\n", e[u], cap, x, i0 + RB * u);
-#endif
-            *reinterpret_cast<f32x4*>(out + (size_t)e[u] * 64 + 4 * q) = v;
-          }
+          if (e[u] >= 0) *reinterpret_cast<f32x4*>(out + (size_t)e[u] * 64 + 4 * q) = v;
       }
     }
   }
@@ -1470,15 +1209,13 @@ struct BgRows2 {   // two background-row jobs (a2 and a3) in one launch's leadin
 // fc1 forward: a4 [B][512] = relu(a3 [B][3136] W3 + b3), the reduction as kFc1Chains chains over consecutive k halves
 // (C0 + C1; round 6): at the training batch the two chains run in two wave groups of a block at once (KS_ =
 // 2: twice the waves on the chip for the same 512 output tiles), at chunk batches one after the other (KQ_ = 2)
-#ifndef QLX_FC1_CHAINS
-#define QLX_FC1_CHAINS 2   // (A/B timing builds only: 1 = the round-5 single chain, which the oracle no longer follows)
-#endif
+#define QLX_FC1_CHAINS 2   // (the oracle follows this value)
 constexpr int kFc1Chains = QLX_FC1_CHAINS;
-template <int BM_ = 32, int BN_ = 64, int WM_ = 2, int WN_ = 2, int MF_ = 16, int KS_ = 1, int KQ_ = kFc1Chains>
+template <int BM_, int BN_, int WM_, int WN_, int KS_ = 1, int KQ_ = kFc1Chains>
 struct PFc1FwdT {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr int KSPLIT = KS_, KSEQ = KQ_;
-  static_assert(KS_ * KQ_ == kFc1Chains && MF_ == 16, "fc1 forward: the chain definition");
+  static_assert(KS_ * KQ_ == kFc1Chains, "fc1 forward: the chain definition");
   static constexpr bool LOAD_FENCE = false;   // (round 5: with it 35.3 / 209.8 us against 33.8 / 203.4)
   // strategy 0 at the training batch (default scheduler 40.4, strategy 1 42.2, 0 39.8 us at B = 1024; round 5: 1 39.3 against
   // 33.8), strategy 1 for the chunk-batch tiles (round 5: 196.7 against 203.4 us)
@@ -1510,14 +1247,13 @@ struct PFc1FwdT {
     for (int r = 0; r < 4; ++r)
       if (row + r < M) a4[(size_t)(row + r) * 512 + col] = relu(v[r] + b[r]);
   }
-  // streams (gemm_body_s; MF 16): a3 rows (rows past M read zeros), W3 k rows
+  // streams (gemm_body_s): a3 rows (rows past M read zeros), W3 k rows
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, false, T>;
   using SB = AffineStream<BN_, true, T>;
-  using Streams = std::conditional_t<MF_ == 16, PairStreams<SA, SB, BK * 4u, BK * 512u * 4u>, void>;
-  template <class S = Streams>
-  __device__ S streams(int, int row0, int col0, int tid) const {
-    S st;
+  using Streams = PairStreams<SA, SB, BK * 4u, BK * 512u * 4u>;
+  __device__ Streams streams(int, int row0, int col0, int tid) const {
+    Streams st;
     const int m = M;
     st.a.init(a3, (uint32_t)M * 3136u * 4u, tid,
               [row0, m](int r, int k) { return row0 + r < m ? (uint32_t)((row0 + r) * 3136 + k) * 4u : kOob; });
@@ -1526,41 +1262,32 @@ struct PFc1FwdT {
     return st;
   }
 };
-using PFc1Fwd = PFc1FwdT<32, 64, 2, 2, 16, 1, kFc1Chains>;
 // chunk-size batches: 64 x 128 tiles on the stream core (in place: 208 us against 228 us for 64 x 64 on
 // v_mfma_f32_32x32x2_f32, 212 / 215 us for 64 x 64 / 128 x 64; gpurun_out/w12)
-using PFc1FwdB = PFc1FwdT<64, 128, 2, 2, 16, 1, kFc1Chains>;
+using PFc1FwdB = PFc1FwdT<64, 128, 2, 2, 1, kFc1Chains>;
 // (re-checked on the stream core in place: 32 x 64 / 64 x 32 / 16 x 64 ran 35.3 / 35.9 / 40.4 us against 34.1 us, w9)
-using PFc1FwdS = PFc1FwdT<32, 32, 2, 2, 16, kFc1Chains, 1>;   // (round 5, after the slab-loop fix: 64 x 32 / 32 x 64 38.4 / 38.9 us against 33.8)
+using PFc1FwdS = PFc1FwdT<32, 32, 2, 2, kFc1Chains, 1>;   // (round 5, after the slab-loop fix: 64 x 32 / 32 x 64 38.4 / 38.9 us against 33.8)
 
-// fc1 backward-data: dz3 [B][3136] = (dz4 [B][512] W3^T) * (a3 > 0); k = n
-#ifndef QLX_PB_XCH
-#define QLX_PB_XCH 1   // conv1 bias partials: lane exchanges by v_permlane16/32_swap (1) or ds_bpermute (0)
-#endif
 // (Q0 + Q1) + (Q2 + Q3) of a 16-row MFMA fragment column, Qg = ((d0 + d1) + d2) + d3 of lane group g's four rows, in every
 // lane (PConv2DgradPx::pb)
 #ifndef QLX_Q32_POLICIES_ONLY
 __device__ __forceinline__ float pb_sum16(const float (&d)[4]) {
   float s = __fadd_rn(__fadd_rn(__fadd_rn(d[0], d[1]), d[2]), d[3]);
-#if QLX_PB_XCH
   // VALU lane swaps (gfx950): with both operands s, the pair holds the lower and the upper row's (half's) value in every
   // lane, so both partners form the same sum (an fp32 sum of two does not depend on the order)
   const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
   s = __fadd_rn(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
   const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
   return __fadd_rn(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-#else
-  s = __fadd_rn(s, __shfl_xor(s, 16));
-  return __fadd_rn(s, __shfl_xor(s, 32));
-#endif
 }
 #else
 inline float pb_sum16(const float (&d)[4]) { return ((d[0] + d[1]) + d[2]) + d[3]; }   // (host address replay)
 #endif
 
-template <int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2, int MF_ = 16>
+// fc1 backward-data: dz3 [B][3136] = (dz4 [B][512] W3^T) * (a3 > 0); k = n
+template <int BM_, int BN_, int WM_, int WN_>
 struct PFc1DgradT {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr bool A_KMAJ = false, B_KMAJ = false, BIAS = false;
   Grid g;
   const float* dz4;
@@ -1610,10 +1337,9 @@ struct PFc1DgradT {
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, false, T>;
   using SB = AffineStream<BN_, false, T>;
-  using Streams = std::conditional_t<MF_ == 16, PairStreams<SA, SB, BK * 4u, BK * 4u>, void>;
-  template <class S = Streams>
-  __device__ S streams(int, int row0, int col0, int tid) const {
-    S st;
+  using Streams = PairStreams<SA, SB, BK * 4u, BK * 4u>;
+  __device__ Streams streams(int, int row0, int col0, int tid) const {
+    Streams st;
     const int m = M;
     st.a.init(dz4, (uint32_t)M * 512u * 4u, tid,
               [row0, m](int r, int k) { return row0 + r < m ? (uint32_t)((row0 + r) * 512 + k) * 4u : kOob; });
@@ -1622,19 +1348,15 @@ struct PFc1DgradT {
     return st;
   }
 };
-using PFc1Dgrad = PFc1DgradT<>;
 // (64 x 32 on the stream core: 61.4 vs 66.0 us alone in scripts/ubench32.hip sweep, but 67.0 vs 65.2 us in place)
 using PFc1DgradS = PFc1DgradT<32, 64, 2, 2>;
 
 // fc1 weight gradient: dW3 [3136][512] = a3^T dz4 over b ascending; db3 = column sums of dz4 (row-tile 0 blocks)
-template <int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2, int MF_ = 16>
+template <int BM_, int BN_, int WM_, int WN_>
 struct PFc1WgradT {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   // the pair at >= 6 waves per SIMD (78 VGPRs; at the default allocation the P8 fragments took it to 86, 5 waves)
-#ifndef QLX_FC1_MINW
-#define QLX_FC1_MINW 6
-#endif
-  static constexpr int MINW = QLX_FC1_MINW;
+  static constexpr int MINW = 6;
   static constexpr bool A_KMAJ = true, B_KMAJ = true, BIAS = true;
   Grid g;
   const float* a3;
@@ -1663,58 +1385,20 @@ struct PFc1WgradT {
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, true, T, true>;
   using SB = AffineStream<BN_, true, T, true>;
-  using Streams = std::conditional_t<MF_ == 16, PairStreams<SA, SB, BK * 3136u * 4u, BK * 512u * 4u, true>, void>;
-  template <class S = Streams>
-  __device__ S streams(int, int row0, int col0, int tid) const {
-    S st;
+  using Streams = PairStreams<SA, SB, BK * 3136u * 4u, BK * 512u * 4u, true>;
+  __device__ Streams streams(int, int row0, int col0, int tid) const {
+    Streams st;
     st.a.init(a3, (uint32_t)B * 3136u * 4u, tid, [row0](int r, int k) { return (uint32_t)(k * 3136 + row0 + r) * 4u; });
     st.b.init(dz4, (uint32_t)B * 512u * 4u, tid, [col0](int r, int k) { return (uint32_t)(k * 512 + col0 + r) * 4u; });
     st.kmax = B;
     return st;
   }
 };
-using PFc1Wgrad = PFc1WgradT<>;
 // training batch: 64 x 64 tiles (392 + the fc1 backward-data tiles; in place at C3: 68.6 -> 65.1 us per fc1 backward
 // against 64 x 32, 128 x 64 75.3, 64 x 128 77.3, 128 x 128 91.1 - gpurun_out/fc1b, fc1c)
 // (on the stream core: 64 x 32, 784 tiles - fc1 backward pair 64.8 -> 61.6 us in place, gpurun_out/w7; with it, backward
 // data 64 x 32 / 32 x 32 / 64 x 64 ran 62.6 / 63.2 / 64.3 us against 61.5 us for 32 x 64, w8)
 using PFc1WgradS = PFc1WgradT<64, 32, 2, 2>;
-
-// conv3 backward-data: dz2 [B][9][9][64] = convT(dz3, W2) * (a2 > 0); rows (b, ih, iw), k = (kh, kw, oc)
-template <int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2, int MF_ = 16>
-struct PConv3DgradT {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
-  static constexpr bool A_KMAJ = false, B_KMAJ = false, BIAS = false;
-  Grid g;
-  const float* dz3;   // [B][7][7][64]
-  const float* w2;    // [3][3][64][64]
-  const float* a2;
-  float* dz2;
-  int M;              // B * 81
-  __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
-  __host__ __device__ int nslabs(int) const { return 18; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    const int tap = s >> 1, kh = tap / 3, kw = tap - kh * 3, oc0 = (s & 1) * 32;
-    const int rr = row < M ? row : 0;
-    const int b = rr / 81, p = rr - b * 81, ih = p / 9, iw = p - ih * 9;
-    const int oh = ih - kh, ow = iw - kw;
-    const bool ok = row < M && oh >= 0 && oh < 7 && ow >= 0 && ow < 7;
-    return ld4m(dz3 + (ok ? ((size_t)(b * 7 + oh) * 7 + ow) * 64 + oc0 + k : 0), ok);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const {   // W2[kh][kw][c = col][oc]
-    return ld4(w2 + ((size_t)(s >> 1) * 64 + col) * 64 + (s & 1) * 32 + k);
-  }
-  __device__ void epi(int, int row, int col, f32x4 v) const {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (row + r < M) {
-        const size_t o = (size_t)(row + r) * 64 + col;
-        dz2[o] = a2[o] > 0.0f ? v[r] : 0.0f;
-      }
-  }
-};
-using PConv3Dgrad = PConv3DgradT<>;
-using PConv3DgradS = PConv3DgradT<32, 64, 2, 2>;
 
 // Pixel-major backward data.  A block owns one input pixel (all samples of a row tile): its valid taps are uniform, so
 // the k loop runs over those taps only - the same chain (valid (kh, kw, oc) lexicographic) as the row-major policies
@@ -1725,12 +1409,8 @@ __host__ __device__ inline int px3_order(int z) { return z < 5 ? z + 2 : (z == 5
 // ... and of the 10 class rows of conv2 dgrad (valid th: 2 for i 1..8, 1 for 0 and 9)
 __host__ __device__ inline int px2_order(int z) { return z < 8 ? z + 1 : (z == 8 ? 0 : 9); }
 
-
-#ifndef QLX_BG2_POST
-#define QLX_BG2_POST 0
-#endif
 // conv3 backward-data, pixel-major: z = pixel (ih, iw) of the 9 x 9 grid; rows b; k = valid (kh, kw) x oc
-template <int BM_ = 32, int BN_ = 64, int WM_ = 2, int WN_ = 2, bool DIRECT = false>
+template <int BM_, int BN_, int WM_, int WN_>
 struct PConv3DgradPx {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr bool LOAD_FENCE = false;
@@ -1757,8 +1437,8 @@ struct PConv3DgradPx {
   };
   __host__ __device__ static Px px(int z) {
     Px q;
-    q.ih = DIRECT ? z / 9 : px3_order(z / 9);   // DIRECT: z = ih * 9 + iw
-    q.iw = DIRECT ? z % 9 : px3_order(z % 9);
+    q.ih = px3_order(z / 9);
+    q.iw = px3_order(z % 9);
     q.kh0 = q.ih > 6 ? q.ih - 6 : 0;
     q.kw0 = q.iw > 6 ? q.iw - 6 : 0;
     const int kh1 = q.ih < 2 ? q.ih : 2, kw1 = q.iw < 2 ? q.iw : 2;
@@ -1784,17 +1464,11 @@ struct PConv3DgradPx {
 #pragma unroll
     for (int r = 0; r < 4; ++r) pr.m[r] = a2[((size_t)((row + r < B ? row + r : 0) * 9 + q.ih) * 9 + q.iw) * 64 + col];
     // (row is a multiple of 4 and row + 3 < bg2_ld: the four samples' bytes are one aligned dword)
-#if !QLX_BG2_POST
     pr.bg = pbg ? *reinterpret_cast<const uint32_t*>(bg2 + (size_t)(q.ih * 9 + q.iw) * bg2_ld + row) : 0u;
-#endif
     return pr;
   }
-  __device__ void epi_post(int z, int row, int col, f32x4 v, const Pre& pr0) const {
+  __device__ void epi_post(int z, int row, int col, f32x4 v, const Pre& pr) const {
     const Px q = px(z);
-    Pre pr = pr0;
-#if QLX_BG2_POST   // (the background bytes loaded in the epilogue: no register held across the slab loop)
-    pr.bg = pbg ? *reinterpret_cast<const uint32_t*>(bg2 + (size_t)(q.ih * 9 + q.iw) * bg2_ld + row) : 0u;
-#endif
     float d[4], e[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1807,8 +1481,8 @@ struct PConv3DgradPx {
       if ((row & 15) == 0 && row < B) pbg[((size_t)(row >> 4) * 81 + q.ih * 9 + q.iw) * 64 + col] = s;
     }
   }
-  // streams (gemm_body_s, gemm_body_chain): dz3 rows of the tile's samples (rows past B read zeros), W2 rows of the tile's
-  // channels; a slab's pixel tap (kh, kw) and oc half are wave-uniform offsets (per sub-tile z in a chained group)
+  // streams (gemm_body_s): dz3 rows of the tile's samples (rows past B read zeros), W2 rows of the tile's channels; a
+  // slab's pixel tap (kh, kw) and oc half are wave-uniform offsets
   static constexpr int T = WM_ * WN_ * 64;
   struct Streams {
     AffineStream<BM_, false, T> a;
@@ -1817,10 +1491,9 @@ struct PConv3DgradPx {
       typename AffineStream<BM_, false, T>::Regs a;
       typename AffineStream<BN_, false, T>::Regs b;
     };
-    int z0;   // (gemm_body_s: the tile's pixel)
-    __device__ void load(int s, Regs& x) const { load_z(z0, s, x); }
-    __device__ void load_z(int z, int s, Regs& x) const {
-      const Px q = px(z);
+    int z0;   // the tile's pixel
+    __device__ void load(int s, Regs& x) const {
+      const Px q = px(z0);
       const int t = s >> 1, kh = q.kh0 + t / q.nkw, kw = q.kw0 + t % q.nkw, h = (s & 1) * 32;
       a.load((uint32_t)(((q.ih - kh) * 7 + q.iw - kw) * 64 + h) * 4u, 0, x.a);
       b.load((uint32_t)((kh * 3 + kw) * 4096 + h) * 4u, 0, x.b);
@@ -1844,7 +1517,7 @@ struct PConv3DgradPx {
 // conv2 backward-data, pixel-major over the class grid: z = (i, j) of 10 x 10; rows b; cols (py, px, c) = 128 (the four
 // output parity classes share the A operand: dz2[b][i - th][j - tw]); k = valid (th, tw) x oc, which is the valid
 // (kh = py + 2 th, kw = px + 2 tw, oc) lexicographic order of every class
-template <int BM_ = 32, int BN_ = 128, int WM_ = 2, int WN_ = 2, bool DIRECT = false>
+template <int BM_, int BN_, int WM_, int WN_>
 struct PConv2DgradPx {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr bool LOAD_FENCE = false;   // (stream core, in place: conv2 pair -1.0 us without it, gpurun_out/w18)
@@ -1873,8 +1546,8 @@ struct PConv2DgradPx {
   };
   __host__ __device__ static Px px(int z) {
     Px q;
-    q.i = DIRECT ? z / 10 : px2_order(z / 10);   // DIRECT: z = i * 10 + j
-    q.j = DIRECT ? z % 10 : px2_order(z % 10);
+    q.i = px2_order(z / 10);
+    q.j = px2_order(z % 10);
     q.th0 = q.i == 9 ? 1 : 0;
     q.tw0 = q.j == 9 ? 1 : 0;
     const int th1 = q.i == 0 ? 0 : 1, tw1 = q.j == 0 ? 0 : 1;
@@ -1930,11 +1603,6 @@ struct PConv2DgradPx {
       typename AffineStream<BM_, false, T>::Regs a;
       typename AffineStream<BN_, false, T>::Regs b;
     };
-    __device__ void load_z(int z, int s, Regs& x) const {   // (chained sub-tiles, PConv2DgradPxG)
-      Streams o = *this;
-      o.q = px(z);
-      o.load(s, x);
-    }
     __device__ void load(int s, Regs& x) const {
       const int t = s >> 1, th = q.th0 + t / q.ntw, tw = q.tw0 + t % q.ntw, h = (s & 1) * 32;
       a.load((uint32_t)(((q.i - th) * 9 + q.j - tw) * 64 + h) * 4u, 0, x.a);
@@ -1959,136 +1627,6 @@ struct PConv2DgradPx {
   }
 };
 
-// Pixel-major backward data with balanced pixel groups (chained sub-tiles, gemm_body_chain): a block runs a group of
-// pixels whose valid taps add up to a full tile's - conv3: 9 taps (interior pixels alone; a 6-tap edge pixel with its
-// 3-tap neighbour; per corner quadrant the 4 + 2 + 2 + 1 taps), 49 groups of 18 slabs; conv2: 4 taps over the 10 x 10 class
-// grid (interior alone; 2-tap edge pixels in pairs; the four 1-tap corners together), 81 groups of 8 slabs.  Every pixel
-// keeps its own chain (valid taps lexicographic), so dz is bit-identical to the one-pixel tiles.
-template <int BM_ = 32, int BN_ = 64, int WM_ = 2, int WN_ = 2>
-struct PConv3DgradPxG : PConv3DgradPx<BM_, BN_, WM_, WN_, true> {
-  static constexpr int NSUB = 4, GROUPS = 49;
-  static constexpr bool RAW_ORDER = false;   // groups are equal: XCD-grouped order (a group's tiles share W2 taps in L2)
-  __host__ __device__ static int sub_count(int g) { return g < 25 ? 1 : (g < 45 ? 2 : 4); }
-  __host__ __device__ static int sub_z(int g, int i) {
-    int ih, iw;
-    if (g < 25) {
-      ih = 2 + g / 5; iw = 2 + g % 5;
-    } else if (g < 35) {   // (ih, 1) + (ih, 0) or (ih, 7) + (ih, 8)
-      const int t = g - 25;
-      ih = 2 + t / 2;
-      iw = (t & 1) ? 7 + i : 1 - i;
-    } else if (g < 45) {   // (1, iw) + (0, iw) or (7, iw) + (8, iw)
-      const int t = g - 35;
-      iw = 2 + t / 2;
-      ih = (t & 1) ? 7 + i : 1 - i;
-    } else {               // quadrant (a, b), (edge, b), (a, edge), (edge, edge)
-      const int q = g - 45, a = (q & 2) ? 7 : 1, b = (q & 1) ? 7 : 1;
-      ih = (i & 1) ? (a == 1 ? 0 : 8) : a;
-      iw = (i & 2) ? (b == 1 ? 0 : 8) : b;
-    }
-    return ih * 9 + iw;
-  }
-};
-template <int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2>
-struct PConv2DgradPxG : PConv2DgradPx<BM_, BN_, WM_, WN_, true> {
-  static constexpr int NSUB = 4, GROUPS = 81;
-  static constexpr bool RAW_ORDER = false;
-  __host__ __device__ static int sub_count(int g) { return g < 64 ? 1 : (g < 80 ? 2 : 4); }
-  __host__ __device__ static int sub_z(int g, int i) {
-    int ci, cj;
-    if (g < 64) {
-      ci = 1 + g / 8; cj = 1 + g % 8;
-    } else if (g < 80) {
-      const int t = g - 64, u = t >> 1, side = t & 1;
-      if (u < 4) { ci = side ? 9 : 0; cj = 1 + 2 * u + i; }
-      else { cj = side ? 9 : 0; ci = 1 + 2 * (u - 4) + i; }
-    } else {
-      ci = (i & 2) ? 9 : 0; cj = (i & 1) ? 9 : 0;
-    }
-    return ci * 10 + cj;
-  }
-};
-
-// conv2 backward-data, all four parity classes in one GEMM: rows (b, i, j) of the 10 x 10 class grid, cols (py, px, c),
-// k = (th, tw, oc) with zero taps (the row-major form of PConv2DgradPx)
-template <int BM_ = 64, int BN_ = 128, int WM_ = 2, int WN_ = 2>
-struct PConv2DgradAll {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
-  static constexpr bool A_KMAJ = false, B_KMAJ = false, BIAS = false;
-  Grid g;             // {ceil(100 B / BM), 128 / BN, 1}
-  const float* dz2;
-  const float* w1;
-  const float* a1;
-  float* dz1;
-  int M;              // B * 100
-  __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
-  __host__ __device__ int nslabs(int) const { return 8; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    const int t = s >> 1, th = t >> 1, tw = t & 1;
-    const int rr = row < M ? row : 0;
-    const int b = rr / 100, p = rr - b * 100, i = p / 10, j = p - i * 10;
-    const int oh = i - th, ow = j - tw;
-    const bool ok = row < M && oh >= 0 && oh < 9 && ow >= 0 && ow < 9;
-    return ld4m(dz2 + (ok ? ((size_t)(b * 9 + oh) * 9 + ow) * 64 + (s & 1) * 32 + k : 0), ok);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const {
-    const int t = s >> 1, cls = col >> 5, kh = (cls >> 1) + 2 * (t >> 1), kw = (cls & 1) + 2 * (t & 1);
-    return ld4(w1 + ((size_t)(kh * 4 + kw) * 32 + (col & 31)) * 64 + (s & 1) * 32 + k);
-  }
-  __device__ void epi(int, int row, int col, f32x4 v) const {
-    const int cls = col >> 5;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (row + r < M) {
-        const int rr = row + r, b = rr / 100, p = rr - b * 100, i = p / 10, j = p - i * 10;
-        const size_t o = ((size_t)(b * 20 + 2 * i + (cls >> 1)) * 20 + 2 * j + (cls & 1)) * 32 + (col & 31);
-        dz1[o] = a1[o] > 0.0f ? v[r] : 0.0f;
-      }
-  }
-};
-
-// conv2 backward-data by output parity class z = (py, px): rows (b, i, j) with ih = 2 i + py, iw = 2 j + px
-// (10 x 10 per class); taps t = (th, tw): kh = py + 2 th, kw = px + 2 tw, source dz2[b][i - th][j - tw];
-// k = (t, oc): the valid taps of the lexicographic (kh, kw, oc) order
-template <int BM_ = 128, int BN_ = 32, int WM_ = 4, int WN_ = 1, int MF_ = 16>
-struct PConv2DgradT {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
-  static constexpr bool A_KMAJ = false, B_KMAJ = false, BIAS = false;
-  Grid g;
-  const float* dz2;   // [B][9][9][64]
-  const float* w1;    // [4][4][32][64]
-  const float* a1;
-  float* dz1;         // [B][20][20][32]
-  int M;              // B * 100
-  __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
-  __host__ __device__ int nslabs(int) const { return 8; }
-  __device__ f32x4 ldA(int z, int s, int row, int k) const {
-    const int t = s >> 1, th = t >> 1, tw = t & 1, oc0 = (s & 1) * 32;
-    const int rr = row < M ? row : 0;
-    const int b = rr / 100, p = rr - b * 100, i = p / 10, j = p - i * 10;
-    const int oh = i - th, ow = j - tw;
-    const bool ok = row < M && oh >= 0 && oh < 9 && ow >= 0 && ow < 9;
-    (void)z;
-    return ld4m(dz2 + (ok ? ((size_t)(b * 9 + oh) * 9 + ow) * 64 + oc0 + k : 0), ok);
-  }
-  __device__ f32x4 ldB(int z, int s, int col, int k) const {   // W1[kh][kw][c = col][oc]
-    const int t = s >> 1, kh = (z >> 1) + 2 * (t >> 1), kw = (z & 1) + 2 * (t & 1);
-    return ld4(w1 + ((size_t)(kh * 4 + kw) * 32 + col) * 64 + (s & 1) * 32 + k);
-  }
-  __device__ void epi(int z, int row, int col, f32x4 v) const {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (row + r < M) {
-        const int rr = row + r, b = rr / 100, p = rr - b * 100, i = p / 10, j = p - i * 10;
-        const int ih = 2 * i + (z >> 1), iw = 2 * j + (z & 1);
-        const size_t o = ((size_t)(b * 20 + ih) * 20 + iw) * 32 + col;
-        dz1[o] = a1[o] > 0.0f ? v[r] : 0.0f;
-      }
-  }
-};
-using PConv2Dgrad = PConv2DgradT<>;
-using PConv2DgradS = PConv2DgradT<64, 32, 4, 1>;
-
 // conv2 / conv3 weight gradient over sample chunk z (samples [z SC, min(B, (z + 1) SC))): rows m = (kh, kw, c),
 // cols oc, r = (b, oh, ow) ascending; partial slab[z][M + 1][OC] (row M = bias partial)
 // CMP (round 6, conv2): the reduction runs over the chunk's non-background rows only (rows: the forward's row flags,
@@ -2098,9 +1636,9 @@ using PConv2DgradS = PConv2DgradT<64, 32, 4, 1>;
 // pack the im2col row offset from the chunk's first sample (bits 0..19) and the chunk row r (bits 20..31), which
 // addresses the dz row: one table for both streams.
 template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int SC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2,
-          int MF_ = 16, bool TPADS = true, bool CMP = false>
+          bool TPADS = true, bool CMP = false>
 struct PConvWgrad {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MF = MF_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr bool LOAD_FENCE = false;   // (with the conv2 backward data's: conv2 pair 101.3 -> 99.8 us, w18)
   // (XCD-grouped block order kept: hardware order measured conv2 / conv3 pairs +2.3 / +1.0 us, w19)
   static constexpr bool A_KMAJ = true, B_KMAJ = true, BIAS = true;
@@ -2229,7 +1767,7 @@ struct PConvWgrad {
   // (the table stream stages 64-row tiles on four waves: other tile shapes keep the ldA / ldB core)
   // (in place against the ldA / ldB core: 262.3K vs 263.0K env-steps/s, conv2 pair 102.0 vs 102.2 us - neutral; kept as the
   // one path: the weight-gradient tiles then issue no per-slab address arithmetic)
-  static constexpr bool STREAMED = BM_ == 64 && MF_ == 16 && WM_ * WN_ == 4;
+  static constexpr bool STREAMED = BM_ == 64 && WM_ * WN_ == 4;
   static_assert(!CMP || STREAMED, "compacted weight gradient: streamed tiles");
   using Streams = std::conditional_t<STREAMED, std::conditional_t<CMP, StreamsCmp, StreamsImpl>, void>;
   static_assert(!TPADS || KMAX <= 4 * 32 * 16, "weight-gradient chunk: the offset table lives in the four images' pads");
@@ -2257,6 +1795,22 @@ struct PConvWgrad {
     return st;
   }
 };
+
+constexpr int kSC1 = QLX_F32_WGRAD_CHUNK_CONV1, kSC2 = QLX_F32_WGRAD_CHUNK_CONV2, kSC3 = QLX_F32_WGRAD_CHUNK_CONV3;
+// weight-gradient chunk tiles 64 x 64 on 1 x 4 waves (each wave 64 rows x 16 channels): conv3 / conv2 pairs 73.0 -> 72.3 /
+// 102.2 -> 101.2 us in place against 2 x 2 (4 x 1: no change; measurement run w14)
+// conv3's offset table after the images (3 blocks per CU: pair 72.1 us; in the images' pads, 4 per CU: 76.1 us, held to 3
+// by a 44 KB LDS request: 73.1 us - measurement runs w22, w31); conv2's in the pads (4 blocks per CU: pair 99.6 -> 96.8 us)
+using PConv3Wgrad = PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, kSC3, 64, 64, 1, 4, false, true>;   // (compacted)
+using PConv3WgradD = PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, kSC3, 64, 64, 1, 4, false>;         // (every row: QLX_F32_BG=0)
+static_assert(kSC3 == 16, "conv3 weight-gradient chunks are the fc1 backward's 16-row fragments (pbg)");
+using PConv2Wgrad = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2, 64, 64, 1, 4, true, true>;   // (compacted)
+using PConv2WgradD = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2, 64, 64, 1, 4>;              // (every row: QLX_F32_BG=0)
+static_assert(kSC2 == 16, "conv2 weight-gradient chunks are the conv3 backward's 16-row fragments (pbg)");
+// pixel-major backward data, one pixel per 64 x 64 tile (conv3 on the stream core: pair 73.2 vs 75.0 us in place for 32 x 64,
+// measurement run w3)
+using PConv3DgradP = PConv3DgradPx<64, 64, 2, 2>;
+using PConv2DgradP = PConv2DgradPx<64, 64, 2, 2>;
 
 // dW4[k][n] = fmaf chain over b of a4[b][k] dq[b][n]; db4[n] = sum over b of dq[b][n]; loss = (sum over b of h_b) / B.
 // Leading blocks of the fc1 backward launch (independent of its GEMM tiles), block t = one 16-row tile of the GEMM
@@ -2335,9 +1889,6 @@ struct SideFc2 {
 // LDS frame layout (rows): slot c, image row x, dword y / 4 holds pixels (x, y .. y + 3) at dword c * 1776 + x * 21 + y / 4.
 // Rows of 21 dwords make 16 consecutive output positions (oh, ow) hit 16 consecutive banks (84 = 20 mod 64 dwords per
 // oh step), and the slot stride 1,776 = 48 mod 64 puts the four slots (the MFMA lane groups) on disjoint bank ranges.
-#ifndef QLX_C1_EXP
-#define QLX_C1_EXP 0   // (timing experiments of the conv1 forward only, scripts/build_variant.sh: 1 no a1 stores, 2 no MFMA, 3 no list claims)
-#endif
 constexpr int kC1SlotDw = 1776;                 // 84 rows x 21 dwords + 12 (bank skew)
 constexpr int kC1Frames = 4 * kC1SlotDw * 4;    // 28,416 B of one sample's frames in LDS
 constexpr int kC1Chunks = 4 * kFramePix / 16;   // 1,764 s2d uint4 chunks in HBM
@@ -2530,7 +2081,7 @@ __device__ __forceinline__ void c1_flags(const uint32_t* rm, unsigned long long*
 // rows (round 6: with one sample per block - k_conv1_fwd32 ONE - the claims doubled, and a claim per wave put 256 of them
 // on each region's conv2 counter).
 __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int nit, int b0, int G, const C1Lists& L, int wave,
-                                               int tid, int B, unsigned long long* xch) {
+                                               int tid, unsigned long long* xch) {
   const int lane = tid & 63, R = wave < 2 ? 81 : 49, p = wave < 2 ? tid : tid - 128;
   int* rl = wave < 2 ? L.rl2 : L.rl3;
   auto wave_tot = [&](int wv) {   // (non-background << 32 | background) rows of wave wv's share over the block's samples
@@ -2543,10 +2094,6 @@ __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int
   unsigned long long old = 0;
   const int slot = blockIdx.x % kListSlots, cap = wave < 2 ? L.cap2 : L.cap3;
   rl += slot * cap;
-#if QLX_C1_EXP == 3   // (timing experiment: no claim - every block writes a fixed, overlapping range; wrong lists)
-  old = ((unsigned long long)((blockIdx.x / kListSlots) % 64) << 32) | (unsigned long long)((blockIdx.x / kListSlots) % 64);
-  __syncthreads();
-#else
   if ((wave == 0 || wave == 2) && lane == 0) {
     const unsigned long long tot = wave == 0 ? wave_tot(0) + wave_tot(1) : wave_tot(2);
     old = __hip_atomic_fetch_add(L.cnt + (slot * 2 + (wave < 2 ? 0 : 1)) * kCntStride, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2554,7 +2101,6 @@ __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int
   }
   __syncthreads();
   if (wave == 1) old = *xch + wave_tot(0);   // wave 1's rows follow wave 0's in the claimed range
-#endif
   if (wave >= 3) return;
   old = __shfl(old, 0);
   int on = (int)(old >> 32), og = (int)(uint32_t)old;
@@ -2572,13 +2118,6 @@ __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int
         tap |= (int)(((q < 64 ? g0 >> q : g1 >> (q - 64)) & 1ull) << t);
       }
     }
-#ifdef QLX_LIST_CHECK
-    {
-      const int i1 = on + __builtin_popcountll(bn & below), i2 = cap - 1 - (og + __builtin_popcountll(bb & below));
-      if ((((bn >> lane) & 1ull) && (i1 < 0 || i1 >= cap)) || (((bb >> lane) & 1ull) && (i2 < 0 || i2 >= cap)) || e >= B * R)
-        printf("LISTCHK flush blk %d wave %d it %d e %d B %d i1 %d i2 %d cap %d\n", (int)blockIdx.x, wave, it, e, B, i1, i2, cap);
-    }
-#endif
     if ((bn >> lane) & 1ull) rl[on + __builtin_popcountll(bn & below)] = e | (tap << 20);
     else if ((bb >> lane) & 1ull) rl[cap - 1 - (og + __builtin_popcountll(bb & below))] = e;
     on += __builtin_popcountll(bn);
@@ -2592,16 +2131,8 @@ __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int
 // tile's 16 frame dwords are read while this tile multiplies (against the kq-outer loop over all 13 accumulators: 49.1 ->
 // 47.9 us at B = 1024, 320 -> 309 us per 8,192-sample chunk, 256 -> 218 VGPRs; gpurun_out/w4).  One branch per (kq, tile)
 // with its four kw steps back to back (a branch per MFMA: 60 vs 46 us at C3)
-struct C1NoHook {
-  __device__ void operator()(int) const {}
-};
-// Hook (ONE, staged rows): called by every wave before its first tile of tile row R = 1 .. 4 (t / 5; every wave has tiles in
-// every row), so it may hold a block barrier; the next tile's frame dwords are not read ahead across a row boundary
-template <class Hook = C1NoHook>
 __device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t (&ob2)[7], int nt, int rp, int g, int col,
-                                              const float (&wf)[64], float bias, int skip, float* a1, int b,
-                                              const Hook& hook = Hook{}) {
-  constexpr bool HOOK = !std::is_same_v<Hook, C1NoHook>;
+                                              const float (&wf)[64], float bias, int skip, float* a1, int b) {
   {
     uint32_t dn[16];
     auto tile_dwords = [&](int j, uint32_t (&d)[16]) {
@@ -2613,13 +2144,6 @@ __device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t
 #pragma unroll
     for (int j = 0; j < 13; ++j)
       if (j < nt) {
-        if constexpr (HOOK) {
-          const int row = (rp + 2 * j) / 5;
-          if (j > 0 && row != (rp + 2 * (j - 1)) / 5) {   // (wave-uniform) the first tile of tile row `row`
-            hook(row);
-            tile_dwords(j, dn);
-          }
-        }
         uint32_t d[16];
 #pragma unroll
         for (int kq = 0; kq < 16; ++kq) d[kq] = dn[kq];
@@ -2629,19 +2153,14 @@ __device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t
         bool nz[16];
 #pragma unroll
         for (int kq = 0; kq < 16; ++kq) nz[kq] = (__builtin_amdgcn_ballot_w64(d[kq] != 0u) != 0) | (skip == 0);   // wave-uniform, no branch
-        if (j + 1 < nt && (!HOOK || (rp + 2 * (j + 1)) / 5 == (rp + 2 * j) / 5)) tile_dwords(j + 1, dn);
+        if (j + 1 < nt) tile_dwords(j + 1, dn);
         f32x4 acc = zero4();
-#if QLX_C1_EXP != 2   // (timing experiments only: 2 = no MFMA, 1 = no a1 stores)
 #pragma unroll
         for (int kq = 0; kq < 16; ++kq)
           if (nz[kq])
 #pragma unroll
             for (int kw = 0; kw < 4; ++kw) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ubyte(d[kq], kw), wf[kq * 4 + kw], acc, 0, 0, 0);
-#endif
         const int t = rp + 2 * j, r0 = (4 * (t / 5) + g) * 20 + 4 * (t % 5);   // rows (oh, ow .. ow + 3) of the patch
-#if QLX_C1_EXP == 1
-        if (acc[0] == 1234.5f)
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) a1[((size_t)b * 400 + r0 + i) * 32 + col] = relu(acc[i] + bias);
       }
@@ -2663,15 +2182,10 @@ __device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t
 // CU runs two samples at a time and a B = 1,024 batch is two samples deep per block: a sample's frame fetch, its
 // 13-tile chains and its a1 stores follow each other.  One sample per block needs one frame buffer (28 KB) and no prefetch
 // registers, so 4 blocks share a CU and all of a CU's samples run at once (VGPRs held to 128 by the launch bound).
-#ifndef QLX_C1_ROWS
-#define QLX_C1_ROWS 0   // ONE: stage the frames by tile rows (measured slower, round 6: 37.2 -> 48.1 us at B = 1024 - the four
-                        // row barriers cost more than the overlap wins, and the live load registers spill at 4 waves / SIMD)
-#endif
-#ifndef QLX_C1_ONE_MINW
-#define QLX_C1_ONE_MINW 4
-#endif
+// (Staging the frames by tile rows instead measured slower, round 6: 37.2 -> 48.1 us at B = 1024; DESIGN.md.)
+constexpr int kC1OneMinW = 4;   // ONE: 4 blocks per CU (128 VGPRs)
 template <int ROLE, bool ONE = false>
-__global__ __launch_bounds__(256, ONE ? QLX_C1_ONE_MINW : 2) void k_conv1_fwd32(const uint8_t* const* table, int B, const float* w0,
+__global__ __launch_bounds__(256, ONE ? kC1OneMinW : 2) void k_conv1_fwd32(const uint8_t* const* table, int B, const float* w0,
                                                                            const float* b0, float* a1, int skip, const C1Lists L) {
   extern __shared__ __attribute__((aligned(16))) uint32_t c1w[];   // [2 (ONE: 1)][4 slots][1776 dwords], rm [3][24], flags
   uint32_t* rm = c1w + (ONE ? 1 : 2) * 4 * kC1SlotDw;
@@ -2706,43 +2220,6 @@ __global__ __launch_bounds__(256, ONE ? QLX_C1_ONE_MINW : 2) void k_conv1_fwd32(
   int b = blockIdx.x;
   if (b >= B) return;
   if constexpr (ONE) {
-#if QLX_C1_ROWS
-    // Staged by tile rows (round 6): the sample's 1,764 frame chunks in row order (block row bx, slot, block column by), a
-    // thread's load j = chunk tid + 256 j; tile row R needs block rows <= 4 R + 4, i.e. loads j < 2, 3, 5, 6, 7 for R = 0..4.
-    // Loads 0..2 are issued first and 0, 1 staged; the hook before row R stages what R needs and issues the loads row R + 1
-    // needs, so the first tiles multiply while the later rows are in flight (all of a CU's blocks start together: with one
-    // stage up front their fetches and their MFMAs did not overlap)
-    const C1Ptrs f = c1_ptrs(table, b);
-    uint4 pf[7];
-    auto issue = [&](int j) {
-      const int q = tid + 256 * j;
-      const bool ok = q < kC1Chunks;
-      const int qq = ok ? q : 0, bx = qq / 84, rem = qq - bx * 84, slot = rem / 21, by = rem - slot * 21;
-      pf[j] = ldg_frame(ok ? c1_slot(f, slot) : nullptr, bx * 21 + by);
-    };
-    auto stage = [&](int j) {
-      const int q = tid + 256 * j;
-      if (q < kC1Chunks) {
-        const int bx = q / 84, rem = q - bx * 84, slot = rem / 21, by = rem - slot * 21;
-        c1_put(c1w, slot * 441 + bx * 21 + by, pf[j]);
-        if (marks && (pf[j].x | pf[j].y | pf[j].z | pf[j].w) != 0u) atomicOr(&rm[bx], 1u << by);
-      }
-    };
-    issue(0);
-    issue(1);
-    issue(2);
-    stage(0);
-    stage(1);
-    __syncthreads();
-    auto hook = [&](int R) {
-      if (R == 1) { stage(2); issue(3); issue(4); }
-      else if (R == 2) { stage(3); stage(4); issue(5); }
-      else if (R == 3) { stage(5); issue(6); }
-      else { stage(6); }
-      __syncthreads();
-    };
-    c1_fwd_sample(c1w, ob2, nt, rp, g, col, wf, bias, skip, a1, b, hook);
-#else
     {
       uint4 pf[7];
       c1_prefetch(c1_ptrs(table, b), pf);
@@ -2751,13 +2228,12 @@ __global__ __launch_bounds__(256, ONE ? QLX_C1_ONE_MINW : 2) void k_conv1_fwd32(
     }
     __syncthreads();
     c1_fwd_sample(c1w, ob2, nt, rp, g, col, wf, bias, skip, a1, b);
-#endif
     if (marks) {
       if (wave < 3) c1_flags(rm, cl + wave * 2, wave, L, b);
       else if (L.steps) c1_steps(rm, L.steps + (size_t)b * 4, L.need, L.need_ld, b, lane);
       if (lists) {
         __syncthreads();
-        c1_lists_flush(cl, 1, blockIdx.x, gridDim.x, L, wave, tid, B, cl + 6);
+        c1_lists_flush(cl, 1, blockIdx.x, gridDim.x, L, wave, tid, cl + 6);
       }
     }
     return;
@@ -2791,7 +2267,7 @@ __global__ __launch_bounds__(256, ONE ? QLX_C1_ONE_MINW : 2) void k_conv1_fwd32(
   }
   if (lists) {
     const int nit = (B - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    c1_lists_flush(cl, nit, blockIdx.x, gridDim.x, L, wave, tid, B, cl + nit * 6);
+    c1_lists_flush(cl, nit, blockIdx.x, gridDim.x, L, wave, tid, cl + nit * 6);
   }
 }
 

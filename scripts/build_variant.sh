@@ -1,6 +1,6 @@
 #!/bin/bash
-# Build an A/B variant of libqlx.so into abvar/<name>/libqlx.so: qnet32.hip recompiled with extra flags (e.g.
-# -DQLX_Q32_NO_SWZ), every other object taken from the main build.  Use with QLX_LIB_PATH=abvar/<name>/libqlx.so.
+# Build an A/B variant of libqlx.so into abvar/<name>/libqlx.so: qnet32.hip recompiled with extra flags (a -D switch
+# of the experiment at hand), every other object taken from the main build.  Use with QLX_LIB_PATH=abvar/<name>/libqlx.so.
 # VARIANT_SRC=qnet rebuilds qnet.hip (the bf16 Q-net) instead; VARIANT_SCHED replaces the scheduler flags.
 set -e
 cd "$(dirname "$0")/.."

@@ -16,30 +16,20 @@
 using namespace qlx;
 using namespace qlx::q32;
 
-constexpr int kSC1 = QLX_F32_WGRAD_CHUNK_CONV1, kSC2 = QLX_F32_WGRAD_CHUNK_CONV2, kSC3 = QLX_F32_WGRAD_CHUNK_CONV3;
-using PConv3Wgrad = PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, kSC3>;
-using PConv2Wgrad = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2>;
-
 static Grid grid(int M, int BM, int N, int BN, int nz) { return Grid{(M + BM - 1) / BM, (N + BN - 1) / BN, nz}; }
 
 static long checks = 0;
 
 template <class P>
 static void replay(const P& p, const char* name) {
-  constexpr int MF = MfOf<P>::value;
-  using OA = Opnd<P::BM, P::A_KMAJ, MF>;
-  using OB = Opnd<P::BN, P::B_KMAJ, MF>;
+  using OA = Opnd<P::BM, P::A_KMAJ>;
+  using OB = Opnd<P::BN, P::B_KMAJ>;
   constexpr int T = P::WM * P::WN * 64;
-  constexpr int TM = P::BM / (P::WM * MF), TN = P::BN / (P::WN * MF);
+  constexpr int TM = P::BM / (P::WM * 16), TN = P::BN / (P::WN * 16);
   volatile float sink = 0.0f;
   for (int lb = 0; lb < p.g.blocks(); ++lb) {
-    int tm, tn, zg;
-    p.decode(lb, tm, tn, zg);
-    int nsub = 1;
-    if constexpr (HasChain<P>::value) nsub = p.sub_count(zg);
-    for (int si = 0; si < nsub; ++si) {
-    int z = zg;
-    if constexpr (HasChain<P>::value) z = p.sub_z(zg, si);
+    int tm, tn, z;
+    p.decode(lb, tm, tn, z);
     const int row0 = tm * P::BM, col0 = tn * P::BN;
     if constexpr (HasActive<P>::value) {
       if (!p.active(z, row0)) continue;
@@ -68,48 +58,25 @@ static void replay(const P& p, const char* name) {
       for (int i = 0; i < TM; ++i)
         for (int j = 0; j < TN; ++j)
           for (int lane = 0; lane < 64; ++lane) {
-            if constexpr (HasEpiPre<P>::value && MF == 16) {
-              const int row = row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col = col0 + (wn * TN + j) * 16 + (lane & 15);
+            const int row = row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col = col0 + (wn * TN + j) * 16 + (lane & 15);
+            if constexpr (HasEpiPre<P>::value) {
               const auto m = p.epi_pre(z, row, col);
               p.epi_post(z, row, col, zero4(), m);
-            } else if (MF == 16) {
-              p.epi(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), zero4());
+            } else {
+              p.epi(z, row, col, zero4());
             }
-            else
-              for (int q = 0; q < 4; ++q)
-                p.epi(z, row0 + (wm * TM + i) * 32 + 8 * q + 4 * (lane >> 5), col0 + (wn * TN + j) * 32 + (lane & 31), zero4());
           }
     }
     if constexpr (P::BIAS) {
       if (tm == 0)
         for (int t = 0; t < P::BN; ++t) p.epi_bias(z, col0 + t, 0.0f);
     }
-    }
   }
-  printf("%-14s blocks %6d ok\n", name, p.g.blocks());
+  printf("%-24s blocks %6d ok\n", name, p.g.blocks());
 }
 
 template <class T>
 static T* buf(size_t n) { return static_cast<T*>(std::calloc(n, sizeof(T))); }
-
-// a grouped pixel policy covers every pixel exactly once, and each group's taps add up to `taps`
-template <class P>
-static void check_groups(int npx, int taps, const char* name) {
-  std::vector<int> hits(npx, 0);
-  for (int g = 0; g < P::GROUPS; ++g) {
-    int t = 0;
-    for (int i = 0; i < P::sub_count(g); ++i) {
-      const int z = P::sub_z(g, i);
-      if (z < 0 || z >= npx) { printf("%s: group %d pixel %d out of range\n", name, g, z); exit(1); }
-      hits[z] += 1;
-      t += P::px(z).ntap;
-    }
-    if (t != taps) { printf("%s: group %d has %d taps\n", name, g, t); exit(1); }
-  }
-  for (int z = 0; z < npx; ++z)
-    if (hits[z] != 1) { printf("%s: pixel %d covered %d times\n", name, z, hits[z]); exit(1); }
-  printf("%-14s groups %d cover %d pixels once, %d taps each\n", name, P::GROUPS, npx, taps);
-}
 
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 32;       // training batch
@@ -128,9 +95,17 @@ int main(int argc, char** argv) {
   const uint8_t* const* tab = table.data();
   float* a1 = buf<float>((size_t)C * 12800); float* a2 = buf<float>((size_t)C * 5184); float* a3 = buf<float>((size_t)C * 3136);
   float* a4 = buf<float>((size_t)n * 512);
-  // forward over n
+  // forward over n, every launch form of f32_forward.  Dense frames (no row lists): the 64 x 64 tiles of the chunk-size
+  // pass, the training batch's 64 x 32 tiles and its balanced grid's 16-row remainder tiles (RowShift)
   replay(PConv2Fwd{grid(n * 81, 64, 64, 64, 1), a1, w1, b1, a2, n * 81}, "conv2_fwd");
   replay(PConv3Fwd{grid(n * 49, 64, 64, 64, 1), a2, w2, b2, a3, n * 49}, "conv3_fwd");
+  replay(PConv2FwdS{grid(n * 81, 64, 64, 32, 1), a1, w1, b1, a2, n * 81}, "conv2_fwd S");
+  replay(PConv3FwdS{grid(n * 49, 64, 64, 32, 1), a2, w2, b2, a3, n * 49}, "conv3_fwd S");
+  {  // the last three whole tiles' rows and the rows after them as 16 x 64 tiles
+    const int M2 = n * 81, M3 = n * 49, whole2 = std::max(0, M2 / 64 - 3), whole3 = std::max(0, M3 / 64 - 3);
+    replay(PConv2FwdR{{Grid{(M2 - whole2 * 64 + 15) / 16, 1, 1}, a1, w1, b1, a2, M2}, whole2 * 4}, "conv2_fwd R");
+    replay(PConv3FwdR{{Grid{(M3 - whole3 * 64 + 15) / 16, 1, 1}, a2, w2, b2, a3, M3}, whole3 * 4}, "conv3_fwd R");
+  }
   {  // row-list forwards (background rows): per region a permutation of the rows, 2 / 3 of them non-background (or all),
      // conv3 entries carrying constant-tap masks; the constant-row tiles
     const int G = std::min(n, 512), per_slot = ((G + kListSlots - 1) / kListSlots) * ((n + G - 1) / G);
@@ -150,66 +125,63 @@ int main(int argc, char** argv) {
         cnt[(x * 2 + 1) * kCntStride] = k3 << 32 | (cap3 - k3);
       }
       auto lg = [&](int cap, int BM, int BN) { return Grid{1 + kListSlots * ((cap + BM - 1) / BM), 64 / BN, 1}; };
-      replay(PConv2FwdL<64, 64, 2, 2>{lg(cap2, 64, 64), a1, w1, b1, a2, rl2, cap2, cnt, cx, nullptr}, "conv2_fwd L");
-      replay(PConv3FwdL<64, 64, 2, 2>{lg(cap3, 64, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L");
-      replay(PConv2FwdL<64, 32, 2, 2>{lg(cap2, 64, 32), a1, w1, b1, a2, rl2, cap2, cnt, cx, nullptr}, "conv2_fwd LS");
-      replay(PConv3FwdL<64, 32, 2, 2>{lg(cap3, 64, 32), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd LS");
+      // conv2: one tile shape, the epilogue's list entries batched (chunk-size pass) or row by row (training batch)
+      PConv2FwdL<64, 64, 2, 2> p2{lg(cap2, 64, 64), a1, w1, b1, a2, rl2, cap2, cnt, cx, nullptr};
+      replay(p2, "conv2_fwd L big");
+      p2.pre_batched = false;
+      replay(p2, "conv2_fwd L");
+      replay(PConv3FwdL<64, 64, 2, 2>{lg(cap3, 64, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L big");
+      replay(PConv3FwdL<32, 64, 2, 2>{lg(cap3, 32, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L");
     }
     replay(PConv2FwdL<16, 64, 1, 4>{Grid{1, 1, 1}, a1, w1, b1, a2, rl2, cap2, cnt, cx, c2}, "const row c2");
     replay(PConv3FwdL<16, 64, 1, 4>{Grid{1, 1, 1}, a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, c3}, "const row c3");
   }
-  replay(PFc1Fwd{grid(n, PFc1Fwd::BM, 512, 64, 1), a3, w3, b3, a4, n}, "fc1_fwd");
-  replay(PFc1FwdB{grid(n, 64, 512, 64, 1), a3, w3, b3, a4, n}, "fc1_fwd B");
-  replay(PConv2FwdS{grid(n * 81, 64, 64, 32, 1), a1, w1, b1, a2, n * 81}, "conv2_fwd S");
-  replay(PConv3FwdS{grid(n * 49, 64, 64, 32, 1), a2, w2, b2, a3, n * 49}, "conv3_fwd S");
-  replay(PFc1FwdS{grid(n, 32, 512, 32, 1), a3, w3, b3, a4, n}, "fc1_fwd S");
-  // backward over B (activations of a B-sample forward)
+  replay(PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd B");
+  replay(PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd S");
+  // backward over B (activations of a B-sample forward), every launch form of f32_backward_dense / f32_backward_conv; the
+  // background buffers are those of the smallest workspace (need_ld = B rounded up to 64)
   float* dz1 = buf<float>((size_t)B * 12800); float* dz2 = buf<float>((size_t)B * 5184);
   float* dz3 = buf<float>((size_t)B * 3136); float* dz4 = buf<float>((size_t)B * 512);
-  float* s1 = buf<float>((size_t)((B + kSC1 - 1) / kSC1) * 257 * 32);
   float* s2 = buf<float>((size_t)((B + kSC2 - 1) / kSC2) * 513 * 64);
   float* s3 = buf<float>((size_t)((B + kSC3 - 1) / kSC3) * 577 * 64);
   float* gw3 = buf<float>(3136 * 512); float* gb3 = buf<float>(512);
-  replay(PFc1Wgrad{grid(3136, 64, 512, 64, 1), a3, dz4, gw3, gb3, B}, "fc1_wgrad");
-  replay(PFc1Dgrad{grid(B, 64, 3136, 64, 1), dz4, w3, a3, dz3, B}, "fc1_dgrad");
-  replay(PFc1WgradS{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), a3, dz4, gw3, gb3, B}, "fc1_wgrad S");
-  replay(PFc1DgradS{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), dz4, w3, a3, dz3, B}, "fc1_dgrad S");
-  replay(PConv3DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 1, 81}, dz3, w2, a2, dz2, B}, "conv3_dgrad px 64");
-  const int z3 = (B + kSC3 - 1) / kSC3, z2 = (B + kSC2 - 1) / kSC2, z1 = (B + kSC1 - 1) / kSC1;
-  replay(PConv3Dgrad{grid(B * 81, 64, 64, 64, 1), dz3, w2, a2, dz2, B * 81}, "conv3_dgrad");
-  replay(PConv3DgradS{grid(B * 81, 32, 64, 64, 1), dz3, w2, a2, dz2, B * 81}, "conv3_dgrad S");
-  replay(PConv3DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 1, 81}, dz3, w2, a2, dz2, B}, "conv3_dgrad px");
-  check_groups<PConv3DgradPxG<>>(81, 9, "conv3 groups");
-  replay(PConv3DgradPxG<32, 64, 2, 2>{{Grid{(B + 31) / 32, 1, 49}, dz3, w2, a2, dz2, B}}, "conv3_dgrad pxg");
-  replay(PConv3Wgrad{grid(576, 64, 64, 64, z3), a2, dz3, s3, B}, "conv3_wgrad");
-  replay(PConv2Dgrad{grid(B * 100, PConv2Dgrad::BM, 32, 32, 4), dz2, w1, a1, dz1, B * 100}, "conv2_dgrad");
-  replay(PConv2DgradS{grid(B * 100, 64, 32, 32, 4), dz2, w1, a1, dz1, B * 100}, "conv2_dgrad S");
-  replay(PConv2DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 2, 100}, dz2, w1, a1, dz1, B}, "conv2_dgrad px");
-  replay(PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, w1, a1, dz1, B}, "conv2_dgrad px 64");
-  replay(PConv2DgradPx<64, 128, 2, 2>{Grid{(B + 63) / 64, 1, 100}, dz2, w1, a1, dz1, B}, "conv2_dgrad px 64 x 128");
-  {  // the product form: conv1 bias partials and the step bytes of the smallest workspace (need_ld = B rounded up to 64)
-    const int need_ld = (B + 63) / 64 * 64;
-    PConv2DgradPx<64, 64, 2, 2> P{Grid{(B + 63) / 64, 2, 100}, dz2, w1, a1, dz1, B, buf<float>((size_t)(B + 15) / 16 * 400 * 32)};
-    P.need = buf<uint8_t>((size_t)100 * need_ld);
-    P.need_ld = need_ld;
-    replay(P, "conv2_dgrad px 64 pb need");
-  }
-  check_groups<PConv2DgradPxG<>>(100, 4, "conv2 groups");
-  replay(PConv2DgradPxG<64, 64, 2, 2>{{Grid{(B + 63) / 64, 2, 81}, dz2, w1, a1, dz1, B}}, "conv2_dgrad pxg");
-  replay(PConv2Wgrad{grid(512, 64, 64, 64, z2), a1, dz2, s2, B}, "conv2_wgrad");
-  {  // the compacted form (the product's): non-background row bits, a varying share per sample (all, none, every k-th)
+  const int z3 = (B + kSC3 - 1) / kSC3, z2 = (B + kSC2 - 1) / kSC2;
+  const int need_ld = (B + 63) / 64 * 64;
+  // non-background row bits of a layer's P rows per sample: a varying share (all, none, every k-th)
+  auto row_bits = [&](int P) {
     uint32_t* rows = buf<uint32_t>((size_t)B * 4);
     for (int b = 0; b < B; ++b)
-      for (int p = 0; p < 81; ++p)
+      for (int p = 0; p < P; ++p)
         if (b % 5 == 0 || (b % 5 != 1 && (p * 7 + b) % (2 + b % 3) == 0)) rows[(size_t)b * 4 + p / 32] |= 1u << (p % 32);
-    using PW2C = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, kSC2, 64, 64, 1, 4, 16, true, true>;
-    replay(PW2C{grid(512, 64, 64, 64, z2), a1, dz2, s2, B, rows}, "conv2_wgrad compacted");
-    const int need_ld = (B + 63) / 64 * 64;
-    PConv3DgradPx<64, 64, 2, 2> P3{Grid{(B + 63) / 64, 1, 81}, dz3, w2, a2, dz2, B};
-    P3.pbg = buf<float>((size_t)(B + 15) / 16 * 81 * 64);
-    P3.bg2 = buf<uint8_t>((size_t)81 * need_ld);
-    P3.bg2_ld = need_ld;
-    replay(P3, "conv3_dgrad px 64 pbg");
+    return rows;
+  };
+  replay(PFc1WgradS{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), a3, dz4, gw3, gb3, B}, "fc1_wgrad S");
+  {
+    PFc1DgradS Pd{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), dz4, w3, a3, dz3, B};
+    replay(Pd, "fc1_dgrad S");
+    Pd.pbg = buf<float>((size_t)(B + 15) / 16 * 49 * 64);
+    Pd.bg = buf<uint8_t>((size_t)49 * need_ld);
+    Pd.bg_ld = need_ld;
+    replay(Pd, "fc1_dgrad S pbg");
+  }
+  replay(PConv3Wgrad{grid(576, 64, 64, 64, z3), a2, dz3, s3, B, row_bits(49)}, "conv3_wgrad compacted");
+  replay(PConv3WgradD{grid(576, 64, 64, 64, z3), a2, dz3, s3, B}, "conv3_wgrad dense");
+  {
+    PConv3DgradP Pd{Grid{(B + PConv3DgradP::BM - 1) / PConv3DgradP::BM, 1, 81}, dz3, w2, a2, dz2, B};
+    replay(Pd, "conv3_dgrad px");
+    Pd.pbg = buf<float>((size_t)(B + 15) / 16 * 81 * 64);
+    Pd.bg2 = buf<uint8_t>((size_t)81 * need_ld);
+    Pd.bg2_ld = need_ld;
+    replay(Pd, "conv3_dgrad px pbg");
+  }
+  replay(PConv2Wgrad{grid(512, 64, 64, 64, z2), a1, dz2, s2, B, row_bits(81)}, "conv2_wgrad compacted");
+  replay(PConv2WgradD{grid(512, 64, 64, 64, z2), a1, dz2, s2, B}, "conv2_wgrad dense");
+  {  // conv1's bias partials always; the step bytes when the forward built row lists
+    PConv2DgradP Pd{Grid{(B + 63) / 64, 2, 100}, dz2, w1, a1, dz1, B, buf<float>((size_t)(B + 15) / 16 * 400 * 32)};
+    replay(Pd, "conv2_dgrad px pb");
+    Pd.need = buf<uint8_t>((size_t)100 * need_ld);
+    Pd.need_ld = need_ld;
+    replay(Pd, "conv2_dgrad px pb need");
   }
   printf("B %d n %d: %ld operand loads replayed, all in bounds\n", B, n, checks);
   return 0;

@@ -283,7 +283,7 @@ struct RowFast : Base {
   }
 };
 
-// K-split wave groups on any policy (gemm_body KSPLIT)
+// K-split wave groups on any policy (KSPLIT: gemm_body, gemm_body_s)
 template <class Base, int K>
 struct KSplit : Base {
   static constexpr int KSPLIT = K;
@@ -439,37 +439,29 @@ int main(int argc, char** argv) {
       run1(n, PConvFwd<9, 9, 64, 3, 1, 7, 7, 64>{grid(B * 49, 64, 64, 64, 1), a2, W2, W2, a3, B * 49}, 2.0 * B * 49 * 64 * 576);
       snprintf(n, sizeof n, "fc1_fwd t32x32 B%d", B);
       run1(n, PFc1FwdT<32, 32, 2, 2>{grid(B, 32, 512, 32, 1), a3, W3, W3, a4, B}, 2.0 * B * 3136 * 512);
-      snprintf(n, sizeof n, "conv3 pair pxg B%d", B);
-      run2(n, PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16>{grid(576, 64, 64, 64, (B + 15) / 16), a2, dz3, slab, B},
-           PConv3DgradPxG<32, 64, 2, 2>{{Grid{(B + 31) / 32, 1, 49}, dz3, W2, a2, dz2, B}}, 4.0 * B * 49 * 64 * 576);
+      snprintf(n, sizeof n, "conv3 pair px B%d", B);
+      run2(n, PConv3WgradD{grid(576, 64, 64, 64, (B + 15) / 16), a2, dz3, slab, B},
+           PConv3DgradP{Grid{(B + 63) / 64, 1, 81}, dz3, W2, a2, dz2, B}, 4.0 * B * 49 * 64 * 576);
       snprintf(n, sizeof n, "conv2 pair px B%d", B);
-      run2(n, PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, (B + 15) / 16), a1, dz2, slab, B},
-           PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, 4.0 * B * 81 * 64 * 512);
+      run2(n, PConv2WgradD{grid(512, 64, 64, 64, (B + 15) / 16), a1, dz2, slab, B},
+           PConv2DgradP{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, 4.0 * B * 81 * 64 * 512);
     }
     return 0;
   }
-  if (argc > 1 && std::string(argv[1]) == "bwd") {   // pixel-major backward data: one pixel per tile vs pixel groups
+  if (argc > 1 && std::string(argv[1]) == "bwd") {   // pixel-major backward data alone and paired with the weight gradient
     for (int B : {1024, 8192}) {
       const double f3 = 2.0 * B * 49 * 64 * 576, f2 = 2.0 * B * 81 * 64 * 512;
       const int z3 = B / 16, z2 = B / 16;
       printf("--- B = %d\n", B);
       run1("conv3_dgrad px t32x64", PConv3DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 1, 81}, dz3, W2, a2, dz2, B}, f3);
-      run1("conv3_dgrad pxg t32x64", PConv3DgradPxG<32, 64, 2, 2>{{Grid{(B + 31) / 32, 1, 49}, dz3, W2, a2, dz2, B}}, f3);
-      run1("conv3_dgrad pxg t64x64", PConv3DgradPxG<64, 64, 2, 2>{{Grid{(B + 63) / 64, 1, 49}, dz3, W2, a2, dz2, B}}, f3);
-      run1("conv3_dgrad pxg t32x32", PConv3DgradPxG<32, 32, 2, 2>{{Grid{(B + 31) / 32, 2, 49}, dz3, W2, a2, dz2, B}}, f3);
+      run1("conv3_dgrad px t64x64 (shipped)", PConv3DgradP{Grid{(B + 63) / 64, 1, 81}, dz3, W2, a2, dz2, B}, f3);
       run1("conv3_wgrad sc16", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16>{grid(576, 64, 64, 64, z3), a2, dz3, slab, B}, f3);
       run2("conv3 pair px", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16>{grid(576, 64, 64, 64, z3), a2, dz3, slab, B},
            PConv3DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 1, 81}, dz3, W2, a2, dz2, B}, 2 * f3);
-      run2("conv3 pair pxg", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16>{grid(576, 64, 64, 64, z3), a2, dz3, slab, B},
-           PConv3DgradPxG<32, 64, 2, 2>{{Grid{(B + 31) / 32, 1, 49}, dz3, W2, a2, dz2, B}}, 2 * f3);
       run1("conv2_dgrad px t64x64", PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, f2);
-      run1("conv2_dgrad pxg t64x64", PConv2DgradPxG<64, 64, 2, 2>{{Grid{(B + 63) / 64, 2, 81}, dz2, W1, a1, dz1, B}}, f2);
-      run1("conv2_dgrad pxg t32x64", PConv2DgradPxG<32, 64, 2, 2>{{Grid{(B + 31) / 32, 2, 81}, dz2, W1, a1, dz1, B}}, f2);
       run1("conv2_wgrad sc16", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, z2), a1, dz2, slab, B}, f2);
       run2("conv2 pair px", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, z2), a1, dz2, slab, B},
            PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, 2 * f2);
-      run2("conv2 pair pxg", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, z2), a1, dz2, slab, B},
-           PConv2DgradPxG<64, 64, 2, 2>{{Grid{(B + 63) / 64, 2, 81}, dz2, W1, a1, dz1, B}}, 2 * f2);
       if (B > 1024) break;
     }
     return 0;
@@ -481,7 +473,7 @@ int main(int argc, char** argv) {
     using Wg2 = PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>;
     for (int rep = 0; rep < 2; ++rep) {
       printf("--- rep %d\n", rep);
-      run2("fc1 W64x64 D32x64 (shipped)", PFc1WgradT<64, 64, 2, 2>{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B},
+      run2("fc1 W64x64 D32x64", PFc1WgradT<64, 64, 2, 2>{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<32, 64, 2, 2>{grid(B, 32, 3136, 64, 1), dz4, W3, a3, dz3, B}, ff);
       run2("fc1 W64x64 D64x64", PFc1WgradT<64, 64, 2, 2>{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<64, 64, 2, 2>{grid(B, 64, 3136, 64, 1), dz4, W3, a3, dz3, B}, ff);
@@ -489,20 +481,18 @@ int main(int argc, char** argv) {
            PFc1DgradT<32, 32, 2, 2>{grid(B, 32, 3136, 32, 1), dz4, W3, a3, dz3, B}, ff);
       run2("fc1 W64x64 D64x32", PFc1WgradT<64, 64, 2, 2>{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<64, 32, 2, 2>{grid(B, 64, 3136, 32, 1), dz4, W3, a3, dz3, B}, ff);
-      run2("fc1 W64x32 D32x64", PFc1WgradT<64, 32, 2, 2>{grid(3136, 64, 512, 32, 1), a3, dz4, gw, gw, B},
+      run2("fc1 W64x32 D32x64 (shipped)", PFc1WgradT<64, 32, 2, 2>{grid(3136, 64, 512, 32, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<32, 64, 2, 2>{grid(B, 32, 3136, 64, 1), dz4, W3, a3, dz3, B}, ff);
       run2("fc1 W128x64 D32x64", PFc1WgradT<128, 64, 2, 2>{grid(3136, 128, 512, 64, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<32, 64, 2, 2>{grid(B, 32, 3136, 64, 1), dz4, W3, a3, dz3, B}, ff);
-      run2("conv3 W64x64 Dpx32x64 (shipped)", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
+      run2("conv3 W64x64 Dpx32x64", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
            PConv3DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 1, 81}, dz3, W2, a2, dz2, B}, f3);
-      run2("conv3 W64x64 Dpx64x64", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
+      run2("conv3 W64x64 Dpx64x64 (shipped)", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
            PConv3DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 1, 81}, dz3, W2, a2, dz2, B}, f3);
       run2("conv3 W64x64 Dpx32x32", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
            PConv3DgradPx<32, 32, 2, 2>{Grid{(B + 31) / 32, 2, 81}, dz3, W2, a2, dz2, B}, f3);
       run2("conv3 W64x64 Dpx16x64", Wg3{grid(576, 64, 64, 64, z), a2, dz3, slab, B},
            PConv3DgradPx<16, 64, 1, 4>{Grid{(B + 15) / 16, 1, 81}, dz3, W2, a2, dz2, B}, f3);
-      run2("conv3 W64x32 Dpx32x64", Wg3{grid(576, 64, 64, 32, z), a2, dz3, slab, B},
-           PConv3DgradPx<32, 64, 2, 2>{Grid{(B + 31) / 32, 1, 81}, dz3, W2, a2, dz2, B}, f3);
       run2("conv2 W64x64 Dpx64x64 (shipped)", Wg2{grid(512, 64, 64, 64, z), a1, dz2, slab, B},
            PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, f2);
       run2("conv2 W64x64 Dpx32x64", Wg2{grid(512, 64, 64, 64, z), a1, dz2, slab, B},
@@ -517,8 +507,6 @@ int main(int argc, char** argv) {
            PConv3DgradPx<128, 64, 2, 2>{Grid{(B + 127) / 128, 1, 81}, dz3, W2, a2, dz2, B}, f3);
       run2("fc1 W64x64 D128x64", PFc1WgradT<64, 64, 2, 2>{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B},
            PFc1DgradT<128, 64, 2, 2>{grid(B, 128, 3136, 64, 1), dz4, W3, a3, dz3, B}, ff);
-      run2("conv2 W64x32 Dpx64x64", Wg2{grid(512, 64, 64, 32, z), a1, dz2, slab, B},
-           PConv2DgradPx<64, 64, 2, 2>{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, f2);
     }
     return 0;
   }
@@ -529,12 +517,13 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&ztab, ht.size() * sizeof(void*)));
     CK(hipMemset(ztab, 0, ht.size() * sizeof(void*)));
     const int B = 1024, G = 512, nz = B / 4, lds = (int)kC1WgradLds;
-    CK(hipFuncSetAttribute((const void*)k_conv1_fwd32<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kC1Frames));
+    // (the persistent form - the library's chunk-pass instantiation - at G blocks)
+    CK(hipFuncSetAttribute((const void*)k_conv1_fwd32<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kC1Frames));
     CK(hipFuncSetAttribute((const void*)k_conv1_wgrad32, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     for (int zero = 0; zero < 2; ++zero)
       for (int skip = 0; skip < 2; ++skip) {
         const uint8_t* const* t = zero ? ztab : table;
-        const double uf = time_us([&] { hipLaunchKernelGGL(k_conv1_fwd32<0>, dim3(G), dim3(256), 2 * kC1Frames, 0, t, B, W0, W0 + 8192, a1, skip, C1Lists{}); });
+        const double uf = time_us([&] { hipLaunchKernelGGL(k_conv1_fwd32<1>, dim3(G), dim3(256), 2 * kC1Frames, 0, t, B, W0, W0 + 8192, a1, skip, C1Lists{}); });
         const double uw = time_us([&] { hipLaunchKernelGGL(k_conv1_wgrad32, dim3(c1_wgrad_blocks(nz)), dim3(kC1WgradThreads), lds, 0, t, dz1, B, nz, slab, skip, nullptr, dz1); });
         printf("conv1 B=%d frames %-5s skip %d: forward %8.2f us  weight gradient %8.2f us\n", B, zero ? "zero" : "live", skip, uf, uw);
       }
@@ -552,11 +541,14 @@ int main(int argc, char** argv) {
   for (int B : Bs) {
     printf("--- B = %d\n", B);
     {
-      const int G = std::min(B, 512);
-      CK(hipFuncSetAttribute((const void*)k_conv1_fwd32<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kC1Frames));
-      const double us = time_us([&] { hipLaunchKernelGGL(k_conv1_fwd32<0>, dim3(G), dim3(256), 2 * kC1Frames, 0, table, B, W0, W0 + 8192, a1, 1, C1Lists{}); });
+      // as f32_forward launches it: one sample per block at the training batch, the persistent form at chunk batches
+      const bool one = B <= 2048;
+      const int G = one ? B : 512, lds = (one ? 1 : 2) * kC1Frames;
+      auto kern = one ? k_conv1_fwd32<0, true> : k_conv1_fwd32<1>;
+      CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      const double us = time_us([&] { hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, 0, table, B, W0, W0 + 8192, a1, 1, C1Lists{}); });
       const double f = 2.0 * B * 400 * 32 * 256;
-      printf("%-34s blocks %6d lds %6d  %9.2f us  %7.2f TF  %5.1f %%\n", "conv1_fwd (k_conv1_fwd32)", G, 2 * kC1Frames, us, f / us / 1e6,
+      printf("%-34s blocks %6d lds %6d  %9.2f us  %7.2f TF  %5.1f %%\n", "conv1_fwd (k_conv1_fwd32)", G, lds, us, f / us / 1e6,
              f / us / 1e6 / 157.3 * 100);
     }
     if (!only_c1) {
@@ -564,12 +556,13 @@ int main(int argc, char** argv) {
          2.0 * B * 81 * 64 * 512);
     run1("conv3_fwd", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64>{grid(B * 49, 64, 64, 64, 1), a2, W2, W2, a3, B * 49},
          2.0 * B * 49 * 64 * 576);
-    run1("fc1_fwd", PFc1Fwd{grid(B, PFc1Fwd::BM, 512, 64, 1), a3, W3, W3, a4, B}, 2.0 * B * 3136 * 512);
+    if (B > 2048) run1("fc1_fwd B", PFc1FwdB{grid(B, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), a3, W3, W3, a4, B}, 2.0 * B * 3136 * 512);
+    else run1("fc1_fwd S", PFc1FwdS{grid(B, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), a3, W3, W3, a4, B}, 2.0 * B * 3136 * 512);
     if (B > 1024) continue;
-    run1("fc1_wgrad", PFc1Wgrad{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B}, 2.0 * B * 3136 * 512);
-    run1("fc1_dgrad", PFc1Dgrad{grid(B, 64, 3136, 64, 1), dz4, W3, a3, dz3, B}, 2.0 * B * 3136 * 512);
-    run2("fc1_bwd pair", PFc1Wgrad{grid(3136, 64, 512, 64, 1), a3, dz4, gw, gw, B}, PFc1Dgrad{grid(B, 64, 3136, 64, 1), dz4, W3, a3, dz3, B},
-         4.0 * B * 3136 * 512);
+    run1("fc1_wgrad S", PFc1WgradS{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), a3, dz4, gw, gw, B}, 2.0 * B * 3136 * 512);
+    run1("fc1_dgrad S", PFc1DgradS{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), dz4, W3, a3, dz3, B}, 2.0 * B * 3136 * 512);
+    run2("fc1_bwd pair", PFc1WgradS{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), a3, dz4, gw, gw, B},
+         PFc1DgradS{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), dz4, W3, a3, dz3, B}, 4.0 * B * 3136 * 512);
     {
       uint8_t* act = nullptr;
       CK(hipMalloc(&act, B));
@@ -591,12 +584,10 @@ int main(int argc, char** argv) {
       });
       printf("%-34s %9.2f us\n", "SideFc2 alone", us);
     }
-    run1("conv3_dgrad", PConv3Dgrad{grid(B * 81, 64, 64, 64, 1), dz3, W2, a2, dz2, B * 81}, 2.0 * B * 49 * 64 * 576);
-    run1("conv3_wgrad", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16>{grid(576, 64, 64, 64, B / 16), a2, dz3, slab, B},
-         2.0 * B * 49 * 64 * 576);
-    run1("conv2_dgrad", PConv2Dgrad{grid(B * 100, PConv2Dgrad::BM, 32, 32, 4), dz2, W1, a1, dz1, B * 100}, 2.0 * B * 81 * 64 * 512);
-    run1("conv2_wgrad", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, B / 16), a1, dz2, slab, B},
-         2.0 * B * 81 * 64 * 512);
+    run1("conv3_dgrad px", PConv3DgradP{Grid{(B + 63) / 64, 1, 81}, dz3, W2, a2, dz2, B}, 2.0 * B * 49 * 64 * 576);
+    run1("conv3_wgrad (every row)", PConv3WgradD{grid(576, 64, 64, 64, B / 16), a2, dz3, slab, B}, 2.0 * B * 49 * 64 * 576);
+    run1("conv2_dgrad px", PConv2DgradP{Grid{(B + 63) / 64, 2, 100}, dz2, W1, a1, dz1, B}, 2.0 * B * 81 * 64 * 512);
+    run1("conv2_wgrad (every row)", PConv2WgradD{grid(512, 64, 64, 64, B / 16), a1, dz2, slab, B}, 2.0 * B * 81 * 64 * 512);
     }
     {
       const int nz = B / 4, lds = (int)kC1WgradLds;
@@ -628,19 +619,11 @@ int main(int argc, char** argv) {
     run1("conv2_fwd t32x64 w2x2", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 32, 64, 2, 2>{grid(B * 81, 32, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
     run1("conv2_fwd t128x64 w2x2", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 64, 2, 2>{grid(B * 81, 128, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
     run1("conv2_fwd t128x64 w4x1", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 64, 4, 1>{grid(B * 81, 128, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
-    run1("conv2_dgrad t64x32 w2x2", PConv2DgradT<64, 32, 2, 2>{grid(B * 100, 64, 32, 32, 4), dz2, W1, a1, dz1, B * 100}, flop);
-    run1("conv2_dgrad t64x32 w4x1", PConv2DgradT<64, 32, 4, 1>{grid(B * 100, 64, 32, 32, 4), dz2, W1, a1, dz1, B * 100}, flop);
-    run1("conv2_dgrad t32x32 w2x2", PConv2DgradT<32, 32, 2, 2>{grid(B * 100, 32, 32, 32, 4), dz2, W1, a1, dz1, B * 100}, flop);
-    run1("conv2_wgrad t64x32 w2x2", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16, 64, 32, 2, 2>{grid(512, 64, 64, 32, B / 16), a1, dz2, slab, B}, flop);
     run1("conv2_wgrad t128x64 w2x2", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16, 128, 64, 2, 2>{grid(512, 128, 64, 64, B / 16), a1, dz2, slab, B}, flop);
     flop = 2.0 * B * 49 * 64 * 576;
     run1("conv3_fwd t64x32 w2x2", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 64, 32, 2, 2>{grid(B * 49, 64, 64, 32, 1), a2, W2, W2, a3, B * 49}, flop);
     run1("conv3_fwd t32x64 w2x2", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 32, 64, 2, 2>{grid(B * 49, 32, 64, 64, 1), a2, W2, W2, a3, B * 49}, flop);
     run1("conv3_fwd t128x64 w2x2", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 128, 64, 2, 2>{grid(B * 49, 128, 64, 64, 1), a2, W2, W2, a3, B * 49}, flop);
-    run1("conv3_dgrad t64x32 w2x2", PConv3DgradT<64, 32, 2, 2>{grid(B * 81, 64, 64, 32, 1), dz3, W2, a2, dz2, B * 81}, flop);
-    run1("conv3_dgrad t32x64 w2x2", PConv3DgradT<32, 64, 2, 2>{grid(B * 81, 32, 64, 64, 1), dz3, W2, a2, dz2, B * 81}, flop);
-    run1("conv3_dgrad t128x64 w2x2", PConv3DgradT<128, 64, 2, 2>{grid(B * 81, 128, 64, 64, 1), dz3, W2, a2, dz2, B * 81}, flop);
-    run1("conv3_wgrad t64x32 w2x2", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 16, 64, 32, 2, 2>{grid(576, 64, 64, 32, B / 16), a2, dz3, slab, B}, flop);
     printf("--- block order: column-tile fastest (shipped) vs row-tile fastest, B = 1024\n");
     {
       const int BB = 1024;
@@ -665,21 +648,17 @@ int main(int argc, char** argv) {
       run1("conv2_wgrad sc16 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, BB / 16), a1, dz2, slab, BB}, f2);
       run1("conv2_wgrad sc8 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 8>{grid(512, 64, 64, 64, BB / 8), a1, dz2, slab, BB}, f2);
       run1("conv2_wgrad sc4 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 4>{grid(512, 64, 64, 64, BB / 4), a1, dz2, slab, BB}, f2);
-      run1("conv2_wgrad sc32 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 32>{grid(512, 64, 64, 64, BB / 32), a1, dz2, slab, BB}, f2);
       run1("conv2_wgrad sc8 t128x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 8, 128, 64, 2, 2>{grid(512, 128, 64, 64, BB / 8), a1, dz2, slab, BB}, f2);
-      run1("conv3_wgrad sc8 t64x32", PConvWgrad<9, 9, 64, 3, 1, 7, 7, 64, 8, 64, 32, 2, 2>{grid(576, 64, 64, 32, BB / 8), a2, dz3, slab, BB}, f3);
     }
     printf("--- K-split wave groups, B = 1024 and 8192\n");
     for (int BB : {1024, 8192}) {
       const double f1 = 2.0 * BB * 3136 * 512, f2 = 2.0 * BB * 81 * 64 * 512, f3 = 2.0 * BB * 49 * 64 * 576;
       printf("B = %d\n", BB);
-      run1("fc1_fwd t32x32 ks1", PFc1FwdT<32, 32, 2, 2>{grid(BB, 32, 512, 32, 1), a3, W3, W3, a4, BB}, f1);
-      run1("fc1_fwd t32x32 ks2", KSplit<PFc1FwdT<32, 32, 2, 2>, 2>{{grid(BB, 32, 512, 32, 1), a3, W3, W3, a4, BB}}, f1);
-      run1("fc1_fwd t64x32 ks2", KSplit<PFc1FwdT<64, 32, 2, 2>, 2>{{grid(BB, 64, 512, 32, 1), a3, W3, W3, a4, BB}}, f1);
-      run1("fc1_fwd t32x64 ks2", KSplit<PFc1FwdT<32, 64, 2, 2>, 2>{{grid(BB, 32, 512, 64, 1), a3, W3, W3, a4, BB}}, f1);
-      run1("fc1_fwd t64x64 ks2", KSplit<PFc1FwdT<64, 64, 2, 2>, 2>{{grid(BB, 64, 512, 64, 1), a3, W3, W3, a4, BB}}, f1);
-      run1("fc1_fwd t32x32 ks4", KSplit<PFc1FwdT<32, 32, 2, 2>, 4>{{grid(BB, 32, 512, 32, 1), a3, W3, W3, a4, BB}}, f1);
-      run1("fc1_fwd t64x64 ks4", KSplit<PFc1FwdT<64, 64, 2, 2>, 4>{{grid(BB, 64, 512, 64, 1), a3, W3, W3, a4, BB}}, f1);
+      run1("fc1_fwd t32x32 in turn", PFc1FwdT<32, 32, 2, 2>{grid(BB, 32, 512, 32, 1), a3, W3, W3, a4, BB}, f1);
+      run1("fc1_fwd t32x32 ks2", PFc1FwdT<32, 32, 2, 2, 2, 1>{grid(BB, 32, 512, 32, 1), a3, W3, W3, a4, BB}, f1);
+      run1("fc1_fwd t64x32 ks2", PFc1FwdT<64, 32, 2, 2, 2, 1>{grid(BB, 64, 512, 32, 1), a3, W3, W3, a4, BB}, f1);
+      run1("fc1_fwd t32x64 ks2", PFc1FwdT<32, 64, 2, 2, 2, 1>{grid(BB, 32, 512, 64, 1), a3, W3, W3, a4, BB}, f1);
+      run1("fc1_fwd t64x64 ks2", PFc1FwdT<64, 64, 2, 2, 2, 1>{grid(BB, 64, 512, 64, 1), a3, W3, W3, a4, BB}, f1);
       run1("conv2_fwd t64x32 ks1", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 64, 32, 2, 2>{grid(BB * 81, 64, 64, 32, 1), a1, W1, W1, a2, BB * 81}, f2);
       run1("conv2_fwd t64x32 ks2", KSplit<PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 64, 32, 2, 2>, 2>{{grid(BB * 81, 64, 64, 32, 1), a1, W1, W1, a2, BB * 81}}, f2);
       run1("conv2_fwd t64x64 ks2", KSplit<PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 64, 64, 2, 2>, 2>{{grid(BB * 81, 64, 64, 64, 1), a1, W1, W1, a2, BB * 81}}, f2);
@@ -704,29 +683,6 @@ int main(int argc, char** argv) {
       run1("conv2_dgrad px t64x64 w2x2", PConv2DgradPx<64, 64, 2, 2>{grid(BB, 64, 128, 64, 100), dz2, W1, a1, dz1, BB}, f2);
       run1("conv2_dgrad px t32x64 w2x2", PConv2DgradPx<32, 64, 2, 2>{grid(BB, 32, 128, 64, 100), dz2, W1, a1, dz1, BB}, f2);
       run1("conv2_dgrad px t64x128 w2x2", PConv2DgradPx<64, 128, 2, 2>{grid(BB, 64, 128, 128, 100), dz2, W1, a1, dz1, BB}, f2);
-      run1("conv2_dgrad all t64x128 w2x2", PConv2DgradAll<64, 128, 2, 2>{grid(BB * 100, 64, 128, 128, 1), dz2, W1, a1, dz1, BB * 100}, f2);
-      run1("conv2_dgrad all t64x64 w2x2", PConv2DgradAll<64, 64, 2, 2>{grid(BB * 100, 64, 128, 64, 1), dz2, W1, a1, dz1, BB * 100}, f2);
-      run1("conv2_dgrad all t128x64 w2x2", PConv2DgradAll<128, 64, 2, 2>{grid(BB * 100, 128, 128, 64, 1), dz2, W1, a1, dz1, BB * 100}, f2);
-      run1("conv2_dgrad (shipped S)", PConv2DgradS{grid(BB * 100, 64, 32, 32, 4), dz2, W1, a1, dz1, BB * 100}, f2);
-      run1("conv3_dgrad (shipped S)", PConv3DgradS{grid(BB * 81, 32, 64, 64, 1), dz3, W2, a2, dz2, BB * 81}, f3);
-    }
-    printf("--- MF 32 (v_mfma_f32_32x32x2_f32) variants\n");
-    for (int BB : {1024, 8192}) {
-      double f2 = 2.0 * BB * 81 * 64 * 512, f3 = 2.0 * BB * 49 * 64 * 576, f1 = 2.0 * BB * 3136 * 512;
-      printf("B = %d\n", BB);
-      run1("conv2_fwd t64x64 w2x2 mf32", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 64, 64, 2, 2, 32>{grid(BB * 81, 64, 64, 64, 1), a1, W1, W1, a2, BB * 81}, f2);
-      run1("conv2_fwd t128x32 w4x1 mf32", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 32, 4, 1, 32>{grid(BB * 81, 128, 64, 32, 1), a1, W1, W1, a2, BB * 81}, f2);
-      run1("conv2_fwd t128x64 w4x1 mf32", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 64, 4, 1, 32>{grid(BB * 81, 128, 64, 64, 1), a1, W1, W1, a2, BB * 81}, f2);
-      run1("conv3_fwd t64x64 w2x2 mf32", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 64, 64, 2, 2, 32>{grid(BB * 49, 64, 64, 64, 1), a2, W2, W2, a3, BB * 49}, f3);
-      run1("conv3_fwd t128x32 w4x1 mf32", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 128, 32, 4, 1, 32>{grid(BB * 49, 128, 64, 32, 1), a2, W2, W2, a3, BB * 49}, f3);
-      run1("fc1_fwd t64x64 w2x2 mf32", PFc1FwdT<64, 64, 2, 2, 32>{grid(BB, 64, 512, 64, 1), a3, W3, W3, a4, BB}, f1);
-      run1("fc1_fwd t32x128 w1x4 mf32", PFc1FwdT<32, 128, 1, 4, 32>{grid(BB, 32, 512, 128, 1), a3, W3, W3, a4, BB}, f1);
-      if (BB > 1024) continue;
-      run1("fc1_dgrad t64x64 w2x2 mf32", PFc1DgradT<64, 64, 2, 2, 32>{grid(BB, 64, 3136, 64, 1), dz4, W3, a3, dz3, BB}, f1);
-      run1("fc1_dgrad t128x32 w4x1 mf32", PFc1DgradT<128, 32, 4, 1, 32>{grid(BB, 128, 3136, 32, 1), dz4, W3, a3, dz3, BB}, f1);
-      run1("conv3_dgrad t64x64 w2x2 mf32", PConv3DgradT<64, 64, 2, 2, 32>{grid(BB * 81, 64, 64, 64, 1), dz3, W2, a2, dz2, BB * 81}, f3);
-      run1("conv3_dgrad t128x32 w4x1 mf32", PConv3DgradT<128, 32, 4, 1, 32>{grid(BB * 81, 128, 64, 32, 1), dz3, W2, a2, dz2, BB * 81}, f3);
-      run1("conv2_dgrad t128x32 w4x1 mf32", PConv2DgradT<128, 32, 4, 1, 32>{grid(BB * 100, 128, 32, 32, 4), dz2, W1, a1, dz1, BB * 100}, f2);
     }
 #undef V
   }
