@@ -1,5 +1,5 @@
 // bf16 GEMM core of the bf16 fast path (round 5): the dense layer fc1 (3136 <-> 512) forward, backward data and weight
-// gradient (qnet.hip), replacing the register-staged 128 x 128 core of gemm_kernels.h.
+// gradient (qnet.hip).
 //
 //   C[m][n] = sum_k A(m, k) B(n, k), fp32 accumulation on v_mfma_f32_16x16x32_bf16 (16 cycles per MFMA per SIMD).
 //   Operands in global memory: row-major  [rows][ld], k contiguous   (KM = false)
@@ -11,7 +11,7 @@
 //
 // Why this shape (MI355X_MICROARCH.md §LDS, cdna_hip_programming.md §5):
 // - operands reach LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`, 1 KB per wave instruction): no VGPR staging and no
-//   ds_write pass (ds_write_b128 moves ~79 B/clk per CU, which is what bounded the old core's k-steps), and the buffer
+//   ds_write pass (ds_write_b128 moves ~79 B/clk per CU, which is what bounded the register-staged round-1 core's k-steps), and the buffer
 //   descriptor's range check turns rows / k-rows past the operand into zeros (ragged M, N and K need no branches);
 // - a 3-stage LDS ring, BK = 32: k-step t + 2 is in flight while t is multiplied; one raw s_barrier per k-step and a
 //   counted `s_waitcnt vmcnt` (never __syncthreads, whose fence would drain the DMA in flight);
@@ -23,7 +23,7 @@
 //   belongs at its linear LDS slot; the permutation stays inside one row / k-row, so coalescing is unchanged) and the
 //   same XOR on the read (cdna_hip_programming.md §5.4 rule 21).  scripts/lds_banks.py checks both layouts;
 // - the MFMA computes C^T (B fragment as the A operand), so each lane ends with 4 consecutive n of one m: the epilogues
-//   of gemm_kernels.h (Epi4*) move 16 bytes (fp32) or 8 bytes (bf16) per access.
+//   (Epi4*) move 16 bytes (fp32) or 8 bytes (bf16) per access.
 // Requirements (host-checked): row-major operands have K % 32 == 0; every split's k range is a multiple of 32 but the last.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,11 +31,88 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "gemm_kernels.h"
 #include "qnet_kernels.h"
 
 namespace qlx {
 namespace qn {
+
+// Buffer-resource loads: an out-of-range tile element gets an offset past the descriptor's range and reads
+// as zero, so the loads are branch-free.
+constexpr int kOobOffset = 0x7FFFFFF0;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
+}
+
+// Epilogues: operator()(m, n, v, z) for C[m][n .. n+3] = v[0..3] of k split z (n % 4 == 0, n + 3 < N when n < N)
+// kSq: the epilogue also yields this tile's sum of squares of the stored values (split by the ones_m row),
+// the clip_by_norm partials of a weight gradient written straight to its final place (see bgemm_tile)
+struct Epi4Slab {   // split-K partial: slab[z][m][n] (fp32)
+  static constexpr bool kSq = false;
+  float* slab;
+  int ldo;
+  size_t zstride;
+  __device__ __forceinline__ void operator()(int m, int n, f32x4 v, int z) const {
+    *reinterpret_cast<f32x4*>(slab + z * zstride + (size_t)m * ldo + n) = v;
+  }
+};
+
+struct Epi4StoreF32 {   // out[m][n] = v (fp32); sq (optional): [tiles] partials of rows != ones_m, then [tiles] of row ones_m
+  static constexpr bool kSq = true;
+  float* out;
+  int ldo;
+  float* sq;
+  __device__ __forceinline__ void operator()(int m, int n, f32x4 v, int) const {
+    *reinterpret_cast<f32x4*>(out + (size_t)m * ldo + n) = v;
+  }
+};
+
+// sum of squares of 4 values with explicit roundings: a tile's clip_by_norm partial does not depend on where
+// the compiler chooses to contract into FMAs
+__device__ __forceinline__ float sq4(f32x4 v) {
+  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(v[0], v[0]), __fmul_rn(v[1], v[1])), __fmul_rn(v[2], v[2])),
+                   __fmul_rn(v[3], v[3]));
+}
+
+__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
+  typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+  const bf16x4v v = {(bf16)a, (bf16)b, (bf16)c, (bf16)d};
+  return __builtin_bit_cast(uint2, v);
+}
+
+struct Epi4BiasRelu {   // out[m][n] = relu(v + bias[n]) as bf16
+  static constexpr bool kSq = false;
+  bf16* out;
+  const float* bias;
+  int ldo;
+  __device__ __forceinline__ void operator()(int m, int n, f32x4 v, int) const {
+    const float4 b = *reinterpret_cast<const float4*>(bias + n);
+    auto r = [](float x) { return x > 0.0f ? x : 0.0f; };
+    *reinterpret_cast<uint2*>(out + (size_t)m * ldo + n) = pack4(r(v[0] + b.x), r(v[1] + b.y), r(v[2] + b.z), r(v[3] + b.w));
+  }
+};
+
+struct Epi4ReluMask {   // dz[m][n] = v * (act[m][n] > 0) as bf16 (act rows act_ld apart)
+  static constexpr bool kSq = false;
+  bf16* out;
+  const bf16* act;
+  int ldo;
+  int act_ld;
+  // every field named: a form without act_ld (the old three-field aggregate) does not compile
+  __host__ __device__ Epi4ReluMask(bf16* out_, const bf16* act_, int ldo_, int act_ld_) : out(out_), act(act_), ldo(ldo_), act_ld(act_ld_) {}
+  __device__ __forceinline__ void operator()(int m, int n, f32x4 v, int) const {
+    const size_t i = (size_t)m * ldo + n;
+    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+    const bf16x4v a = *reinterpret_cast<const bf16x4v*>(act + (size_t)m * act_ld + n);
+    *reinterpret_cast<uint2*>(out + i) = pack4((float)a[0] > 0.0f ? v[0] : 0.0f, (float)a[1] > 0.0f ? v[1] : 0.0f,
+                                               (float)a[2] > 0.0f ? v[2] : 0.0f, (float)a[3] > 0.0f ? v[3] : 0.0f);
+  }
+};
+
+// Blocks b and b + 8 share an XCD (round-robin dispatch, MI355X_MICROARCH.md): block b runs logical tile
+// (b % 8) * (grid / 8) + b / 8, so each XCD owns one contiguous range of the tile order and the operand
+// panels its tiles share are fetched into its own L2 once.  grid is a multiple of 8.
+__device__ __forceinline__ int xcd_tile(int b, int grid) { return (b & 7) * (grid >> 3) + (b >> 3); }
+__host__ __forceinline__ int xcd_grid(int tiles) { return (tiles + 7) / 8 * 8; }
 
 struct BOp {
   const bf16* p;
@@ -43,13 +120,8 @@ struct BOp {
   int rows;   // valid rows (M for A, N for B)
 };
 
-// DBG_ (development timing only, scripts/ubench_bgemm.hip): 1 = no MFMAs, 2 = no DMA in the k loop, 3 = DMA and barriers
-// only, 4 = no k loop (prologue DMA + epilogue), 5 = no epilogue stores
-// AG_: void, or the im2col geometry of a gathered A operand (ConvGather: A(m, k) = in[im2col row k][column m], k-major)
-template <int BM_, int BN_, int WM_, int WN_, bool AK_, bool BKM_, int S_ = 3, int DBG_ = 0, class AG_ = void>
+template <int BM_, int BN_, int WM_, int WN_, bool AK_, bool BKM_, int S_ = 3>
 struct BGemmCfg {
-  static constexpr int DBG = DBG_;
-  using AG = AG_;
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, NW = WM_ * WN_, T = NW * 64;
   static constexpr int BK = 32, S = S_;   // S LDS stages: S - 1 k-steps in flight ahead of the one multiplied
   static constexpr bool AK = AK_, BKM = BKM_;
@@ -62,7 +134,6 @@ struct BGemmCfg {
   static_assert(LA % NW == 0 && LB % NW == 0, "every wave issues the same DMA count per operand");
   static_assert(TM % 16 == 0 && TN % 16 == 0, "wave tile of whole 16 x 16 MFMA tiles");
   static_assert(!AK || BM == 64 || BM == 128, "k-major images are 64 or 128 rows");
-  static_assert(std::is_void<AG_>::value || (AK_ && BM_ == 128), "a gathered A operand is a 128-row k-major image");
   static_assert(!BKM || BN == 64 || BN == 128, "k-major images are 64 or 128 rows");
   static_assert(S >= 2 && S <= 8 && (S - 1) * (LPA + LPB) <= 63, "vmcnt counts to 63");
 };
@@ -131,63 +202,9 @@ struct BStage {
   }
 };
 
-// im2col geometry of a conv weight gradient's gathered operand: input in [B][IH][IW][C] (bf16), reduction index
-// k = b * P + oh * OW + ow (P = OH * OW output positions per sample), row m = (kh * KS + kw) * C + c (the HWIO row of dW).
-// Element offset of (m, k) = kbase(k) + roff(m); 8 consecutive rows (one 16-byte chunk, 8 | C) are contiguous.
-template <int IH_, int IW_, int C_, int KS_, int S_, int OH_, int OW_>
-struct ConvGather {
-  static constexpr int IH = IH_, IW = IW_, C = C_, KS = KS_, S = S_, OH = OH_, OW = OW_, P = OH_ * OW_, M = KS_ * KS_ * C_;
-  static_assert(C % 8 == 0, "16-byte chunks of one tap");
-  __device__ static uint32_t kbase(int k) {
-    const int b = k / P, p = k - b * P, oh = p / OW, ow = p - oh * OW;
-    return (uint32_t)(((b * IH + oh * S) * IW + ow * S) * C);
-  }
-  __device__ static uint32_t roff(int m) {
-    const int tap = m / C, c = m - tap * C, kh = tap / KS, kw = tap - kh * KS;
-    return (uint32_t)((kh * IW + kw) * C + c);
-  }
-};
-
-// The gathered (im2col) A operand as a 128-row k-major image: lane chunk -> rows m0 + 8 gc .. + 7 of k-row kr, fetched from
-// in + kbase(k) + roff(m).  kbase is evaluated per k-step (a few VALU per DMA instruction); roff is fixed per lane.
-template <class G, int NW, int LP>
-struct BStageGather {
-  uint32_t roff[LP];
-  int kr[LP];
-  int first, kstart;
-  __amdgpu_buffer_rsrc_t rs;
-  __device__ void init(const BOp& o, int row0, int kb, int ke, int wave, int lane) {
-    first = wave;
-    kstart = kb;
-    rs = make_rsrc(o.p, (uint32_t)((size_t)o.ld * 2));   // gathered operand: o.ld = elements of the whole input tensor
-#pragma unroll
-    for (int j = 0; j < LP; ++j) {
-      const int ii = wave + NW * j, k = ii * 4 + (lane >> 4), gc = (lane & 15) ^ bswz_k<128>(k);
-      const int m = row0 + 8 * gc;
-      kr[j] = k;
-      roff[j] = m < o.rows ? G::roff(m) : 0xFFFFFFFFu;
-    }
-  }
-  __device__ void issue(int t, char* img) const {
-    const int k0 = kstart + 32 * t;
-#pragma unroll
-    for (int j = 0; j < LP; ++j) {
-      const uint32_t v = roff[j] == 0xFFFFFFFFu ? (uint32_t)kOobOffset : (G::kbase(k0 + kr[j]) + roff[j]) * 2u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr)(img + 1024 * (first + NW * j)), 16, v, 0, 0, 0);
-    }
-  }
-};
-
 template <class C, bool IS_A>
 struct BStageOf {
   using type = BStage<IS_A ? C::AK : C::BKM, IS_A ? C::BM : C::BN, C::NW, IS_A ? C::LPA : C::LPB>;
-};
-template <class C>
-struct BStageA {
-  using type = std::conditional_t<std::is_void<typename C::AG>::value, typename BStageOf<C, true>::type,
-                                  BStageGather<std::conditional_t<std::is_void<typename C::AG>::value, ConvGather<1, 1, 8, 1, 1, 1, 1>,
-                                                                  typename C::AG>,
-                                               C::NW, C::LPA>>;
 };
 
 // fragment read addresses (byte offsets inside an operand image) for fragment f of a wave whose rows start at r0
@@ -210,8 +227,6 @@ __device__ __forceinline__ int bfrag_off(int r0, int f, int lane) {
 // fences the MFMAs behind each wait with a scheduling barrier (cdna_hip_programming.md §5.4 rule 18).
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-template <bool KM>
-constexpr int bfrag_insts() { return KM ? 2 : 1; }   // LDS instructions per fragment
 // one LDS read at addr + OFF (OFF an immediate; the ds offset field is 16 bits, so 64 KB moves into the address)
 template <int OFF>
 __device__ __forceinline__ u32x4 ds_b128(uint32_t addr) {
@@ -285,7 +300,7 @@ __device__ __forceinline__ void bgemm_tile(const BGemmProblem<Epi>& P, int tile,
   const int m0 = bx * C::BM, n0 = by * C::BN;
   const int kb = bz * P.kps, ke = min(P.K, kb + P.kps);
   const int nk = (ke - kb + C::BK - 1) / C::BK;
-  typename BStageA<C>::type sa;
+  typename BStageOf<C, true>::type sa;
   typename BStageOf<C, false>::type sb;
   sa.init(P.A, m0, kb, ke, wave, lane);
   sb.init(P.B, n0, kb, ke, wave, lane);
@@ -324,7 +339,7 @@ __device__ __forceinline__ void bgemm_tile(const BGemmProblem<Epi>& P, int tile,
   if (nk > 0) {
     wait_vm_n<LPW, S - 2>(min(S - 2, nk - 1));
     __builtin_amdgcn_s_barrier();
-    if constexpr (C::DBG != 3) read_frags(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    read_frags(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
   }
   auto step = [&](auto u_c, int t) {
     constexpr int u = decltype(u_c)::value, stage = u % S, par = u % 2;
@@ -335,17 +350,13 @@ __device__ __forceinline__ void bgemm_tile(const BGemmProblem<Epi>& P, int tile,
     if (more) {
       wait_vm_n<LPW, S - 3>(min(S - 3, nk - 2 - t));
       __builtin_amdgcn_s_barrier();
-      if (t + S - 1 < nk && C::DBG != 2) issue(t + S - 1, (stage + S - 1) % S);
+      if (t + S - 1 < nk) issue(t + S - 1, (stage + S - 1) % S);
     }
-    if constexpr (C::DBG == 3) return;
     bfrag_wait<0>();   // the fragments of step t (read during step t - 1)
     auto col = [&](auto jc) {
       constexpr int j = decltype(jc)::value;
 #pragma unroll
-      for (int i = 0; i < C::FM; ++i) {
-        if constexpr (C::DBG == 1) acc[i][j][0] += (float)fb[par][j][0] * (float)fa[par][i][0];
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[par][j], fa[par][i], acc[i][j], 0, 0, 0);
-      }
+      for (int i = 0; i < C::FM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[par][j], fa[par][i], acc[i][j], 0, 0, 0);
       if constexpr (j == 0) {   // the next step's reads go out behind the first column of MFMAs
         if (more) read_frags(std::integral_constant<int, (stage + 1) % S>{}, std::integral_constant<int, par ^ 1>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -355,8 +366,7 @@ __device__ __forceinline__ void bgemm_tile(const BGemmProblem<Epi>& P, int tile,
   };
   // the loop unrolled by U (a multiple of S and of 2), so every stage offset and register set is static
   constexpr int U = S % 2 == 0 ? S : 2 * S;
-  int t = C::DBG == 4 ? nk : 0;
-  if constexpr (C::DBG == 4) wait_vm<0>();
+  int t = 0;
   for (; t + U <= nk; t += U) static_for<U>([&](auto uc) { step(uc, t + decltype(uc)::value); });
   static_for<U - 1>([&](auto uc) {
     if (t + decltype(uc)::value < nk) step(uc, t + decltype(uc)::value);
@@ -386,10 +396,6 @@ __device__ __forceinline__ void bgemm_tile(const BGemmProblem<Epi>& P, int tile,
       const int r = it * RPI + lane / LPR, c = 4 * (lane % LPR);
       const f32x4 v = *reinterpret_cast<const f32x4*>(img + r * PITCH + c);
       const int m = m0 + wm * C::TM + h * HR + r, n = n0 + wn * C::TN + c;
-      if constexpr (C::DBG == 5) {
-        asm volatile("" ::"v"(v));
-        continue;
-      }
       if (m < P.M && n < P.N) {
         epi(m, n, v, bz);
         if constexpr (Epi::kSq) {

@@ -24,12 +24,6 @@ namespace qlx {
 
 using namespace q32;
 
-static int64_t voff(int v) {
-  int64_t o = 0;
-  for (int i = 0; i < v; ++i) o += kVarSize[i];
-  return o;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // dense 512 -> 3 head: q[b][n] = (fmaf chain over k ascending of a4[b][k] W4[k][n]) + b4[n], as the MFMA product
 // W4^T a4^T (one wave per 16 samples: A = W4^T rows n < 3, B = a4 columns; each output is the k-ordered chain), the
@@ -568,7 +562,6 @@ static int conv_adam_blocks() {
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 static int segs_of(int v) { return (kVarSize[v] + kNormSeg - 1) / kNormSeg; }
 static_assert((1605632 + kNormSeg - 1) / kNormSeg <= kNormSegMax, "norm partials per variable");
@@ -798,7 +791,7 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
       const size_t lds = frames + 3 * kC1RmDw * 4 + (size_t)((n + G - 1) / G) * 6 * 8 + 8;   // frames, row masks, flags, claim
       set_lds_limit((const void*)kern, frames + 3 * kC1RmDw * 4 + (size_t)(one ? 1 : kC1MaxIt) * 6 * 8 + 8);
       hipExtLaunchKernelGGL(kern, dim3(G), dim3(256), lds, s, ea, eb, 0u, table + (size_t)c0 * 4, n,
-                            p + voff(0), p + voff(1), w.fa1, c1_skip(m), L);
+                            p + var_offset(0), p + var_offset(1), w.fa1, c1_skip(m), L);
       QLX_HIP(hipGetLastError());
       debug_sync(s, sc);
     }
@@ -816,45 +809,41 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
         // the constant rows' chains in the conv2 launch's first block
         using PC2 = PConv2FwdL<16, 64, 1, 4>;
         using PC3 = PConv3FwdL<16, 64, 1, 4>;
-        const ConstRows<PC2, PC3> cr{PC2{Grid{1, 1, 1}, w.fa1, p + voff(2), p + voff(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, c2},
-                                     PC3{Grid{1, 1, 1}, w.fa2, p + voff(4), p + voff(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, c3}};
+        const ConstRows<PC2, PC3> cr{PC2{Grid{1, 1, 1}, w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, c2},
+                                     PC3{Grid{1, 1, 1}, w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, c3}};
         // (the list tiles start at row tile 1; row tile 0, the constant row, is ConstRows' work: its blocks return)
-        P2 p2{lgrid(cap2, P2::BM, P2::BN), w.fa1, p + voff(2), p + voff(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, nullptr};
+        P2 p2{lgrid(cap2, P2::BM, P2::BN), w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, nullptr};
         p2.pre_batched = big;
         launch_list(m, p2, cr, sc2, 2.0 * n * 81 * 64 * 512, s);
-        launch_list(m, P3{lgrid(cap3, P3::BM, P3::BN), w.fa2, p + voff(4), p + voff(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, nullptr},
+        launch_list(m, P3{lgrid(cap3, P3::BM, P3::BN), w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, nullptr},
                     s23, sc3, 2.0 * n * 49 * 64 * 576, s);
       };
       if (big) {
         // (64 x 32 list tiles here: conv2 / conv3 145 / 185 us against 139 / 181 us, gpurun_out/w10)
         run(PConv2FwdL<64, 64, 2, 2>{}, PConv3FwdL<64, 64, 2, 2>{}, "f32_conv2_fwd_big", "f32_conv3_fwd_big");
-        model_dense_join(m, s);   // W3 / b3 of a dense update in flight on the aux stream
-        launch(m, PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), w.fa3, p + voff(6), p + voff(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd_big",
+        launch(m, PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), w.fa3, p + var_offset(6), p + var_offset(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd_big",
                2.0 * n * 3136 * 512, s);
       } else {
         // (on the stream core, in place: conv2 64 x 64 24.3 us against 27.9 us for 64 x 32 and 28.7 for 32 x 64; conv3 32 x 64
         // 27.6 us against 28.5 / 29.8 for 64 x 32 / 64 x 64 - gpurun_out/w10)
         run(PConv2FwdL<64, 64, 2, 2>{}, PConv3FwdL<32, 64, 2, 2>{}, "f32_conv2_fwd", "f32_conv3_fwd");
-        model_dense_join(m, s);
-        launch(m, PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), w.fa3, p + voff(6), p + voff(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd",
+        launch(m, PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), w.fa3, p + var_offset(6), p + var_offset(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd",
                2.0 * n * 3136 * 512, s);
       }
     } else if (big) {
       // (plain grids: 40.5 / 24.5 whole tiles per CU at 8,192 samples; the balanced split measured 373 -> 385 us on conv2)
-      launch(m, PConv2Fwd{grid(n * 81, 64, 64, 64, 1), w.fa1, p + voff(2), p + voff(3), w.fa2, n * 81}, "f32_conv2_fwd_big",
+      launch(m, PConv2Fwd{grid(n * 81, 64, 64, 64, 1), w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, n * 81}, "f32_conv2_fwd_big",
              2.0 * n * 81 * 64 * 512, s);
-      launch(m, PConv3Fwd{grid(n * 49, 64, 64, 64, 1), w.fa2, p + voff(4), p + voff(5), w.fa3, n * 49}, "f32_conv3_fwd_big",
+      launch(m, PConv3Fwd{grid(n * 49, 64, 64, 64, 1), w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, n * 49}, "f32_conv3_fwd_big",
              2.0 * n * 49 * 64 * 576, s);
-      model_dense_join(m, s);
-      launch(m, PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), w.fa3, p + voff(6), p + voff(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd_big",
+      launch(m, PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), w.fa3, p + var_offset(6), p + var_offset(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd_big",
              2.0 * n * 3136 * 512, s);
     } else {
-      conv_fwd<PConv2Fwd, PConv2FwdR>(m, n * 81, w.fa1, p + voff(2), p + voff(3), w.fa2, "f32_conv2_fwd", 2.0 * n * 81 * 64 * 512, s,
-                                      PConv2FwdS{grid(n * 81, 64, 64, 32, 1), w.fa1, p + voff(2), p + voff(3), w.fa2, n * 81});
-      conv_fwd<PConv3Fwd, PConv3FwdR>(m, n * 49, w.fa2, p + voff(4), p + voff(5), w.fa3, "f32_conv3_fwd", 2.0 * n * 49 * 64 * 576, s,
-                                      PConv3FwdS{grid(n * 49, 64, 64, 32, 1), w.fa2, p + voff(4), p + voff(5), w.fa3, n * 49});
-      model_dense_join(m, s);
-      launch(m, PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), w.fa3, p + voff(6), p + voff(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd",
+      conv_fwd<PConv2Fwd, PConv2FwdR>(m, n * 81, w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, "f32_conv2_fwd", 2.0 * n * 81 * 64 * 512, s,
+                                      PConv2FwdS{grid(n * 81, 64, 64, 32, 1), w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, n * 81});
+      conv_fwd<PConv3Fwd, PConv3FwdR>(m, n * 49, w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, "f32_conv3_fwd", 2.0 * n * 49 * 64 * 576, s,
+                                      PConv3FwdS{grid(n * 49, 64, 64, 32, 1), w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, n * 49});
+      launch(m, PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), w.fa3, p + var_offset(6), p + var_offset(7), w.fa4 + (size_t)c0 * 512, n}, "f32_fc1_fwd",
              2.0 * n * 3136 * 512, s);
     }
   }
@@ -878,6 +867,7 @@ void f32_head(int mode, const Fc2Args& a, int B, hipStream_t s) {
 void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                         const float* weights, float* td_abs) {
   QLX_CHECK(B <= m->w.fchunk && B == m->last_batch, QLX_E_STATE, "f32 backward: batch must follow its forward");
+  m->f32_dense_partials = false;   // partials of an earlier gradient (an update that threw before its Adam)
   f32_grad_workspace(m, B);
   ModelWs& w = m->w;
   float* G = m->d_grads;
@@ -895,14 +885,14 @@ void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float
     f32_head(3, a, B, s);
   }
   {  // dW3 + db3 and dz3 tiles in one grid, dW4 / db4 / loss as its leading blocks
-    PFc1WgradS Pw{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), w.fa3, w.fdz4, G + voff(6), G + voff(7), B};
-    PFc1DgradS Pd{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), w.fdz4, p + voff(6), w.fa3, w.fdz3, B};
+    PFc1WgradS Pw{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), w.fa3, w.fdz4, G + var_offset(6), G + var_offset(7), B};
+    PFc1DgradS Pd{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), w.fdz4, p + var_offset(6), w.fa3, w.fdz3, B};
     if (bg_rows(m)) {   // conv3's background-row dz3 sums (the compacted conv3 weight gradient)
       Pd.pbg = w.fpbg3;
       Pd.bg = w.fbg3;
       Pd.bg_ld = w.fneed_ld;
     }
-    SideFc2 S{w.fa4, actions, w.gs, w.hs, B, G + voff(8), G + voff(9), loss_dev};
+    SideFc2 S{w.fa4, actions, w.gs, w.hs, B, G + var_offset(8), G + var_offset(9), loss_dev};
     launch_pair(m, Pw, Pd, S, "f32_fc1_bwd", 2.0 * 2.0 * B * 512 * 3136, s);   // (3 blocks per CU: 72.8 vs 61.8 us, w23)
   }
 }
@@ -959,7 +949,7 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
   {  // conv3: dz2 pixel tiles + weight-gradient chunk tiles
     PConv3Wgrad Pw{grid(576, 64, 64, 64, z3), w.fa2, w.fdz3, w.fslab3, B, w.frows3};
     PConv3WgradD Pw_dense{grid(576, 64, 64, 64, z3), w.fa2, w.fdz3, w.fslab3, B};
-    PConv3DgradP Pd{Grid{(B + PConv3DgradP::BM - 1) / PConv3DgradP::BM, 1, 81}, w.fdz3, p + voff(4), w.fa2, w.fdz2, B};
+    PConv3DgradP Pd{Grid{(B + PConv3DgradP::BM - 1) / PConv3DgradP::BM, 1, 81}, w.fdz3, p + var_offset(4), w.fa2, w.fdz2, B};
     if (bg_rows(m)) {   // conv2's background-row dz2 sums (the compacted conv2 weight gradient)
       Pd.pbg = w.fpbg2;
       Pd.bg2 = w.fbg2;
@@ -974,7 +964,7 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
     // over every row on the dense-frame path
     PConv2Wgrad Pw{grid(512, 64, 64, 64, z2), w.fa1, w.fdz2, w.fslab2, B, w.frows2};
     PConv2WgradD Pw_dense{grid(512, 64, 64, 64, z2), w.fa1, w.fdz2, w.fslab2, B};
-    PConv2DgradP Pd{Grid{(B + 63) / 64, 2, 100}, w.fdz2, p + voff(2), w.fa1, w.fdz1, B, w.fpb1};
+    PConv2DgradP Pd{Grid{(B + 63) / 64, 2, 100}, w.fdz2, p + var_offset(2), w.fa1, w.fdz1, B, w.fpb1};
     if (c1_sparse_dz(m)) {   // dz1 rows of clear conv1 steps are neither stored here nor fetched by the conv1 weight gradient
       Pd.need = w.fneed;
       Pd.need_ld = w.fneed_ld;
@@ -998,9 +988,9 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
   {
     ProfScope ps(m->prof, "f32_wgrad_reduce", s);
     WRed R;
-    R.slab[0] = w.fslab3; R.nz[0] = z3; R.count[0] = 577 * 64; R.oc[0] = 64; R.gw[0] = G + voff(4); R.gb[0] = G + voff(5);
-    R.slab[1] = w.fslab2; R.nz[1] = z2; R.count[1] = 513 * 64; R.oc[1] = 64; R.gw[1] = G + voff(2); R.gb[1] = G + voff(3);
-    R.slab[2] = w.fslab1; R.nz[2] = z1; R.count[2] = 257 * 32; R.oc[2] = 32; R.gw[2] = G + voff(0); R.gb[2] = G + voff(1);
+    R.slab[0] = w.fslab3; R.nz[0] = z3; R.count[0] = 577 * 64; R.oc[0] = 64; R.gw[0] = G + var_offset(4); R.gb[0] = G + var_offset(5);
+    R.slab[1] = w.fslab2; R.nz[1] = z2; R.count[1] = 513 * 64; R.oc[1] = 64; R.gw[1] = G + var_offset(2); R.gb[1] = G + var_offset(3);
+    R.slab[2] = w.fslab1; R.nz[2] = z1; R.count[2] = 257 * 32; R.oc[2] = 32; R.gw[2] = G + var_offset(0); R.gb[2] = G + var_offset(1);
     R.sbg[0] = bg_rows(m) ? w.fs3 : nullptr;
     R.ubg[0] = w.fbgc + 32;   // c2, written by the training forward's conv2 launch (ConstRows)
     R.sbg[1] = bg_rows(m) ? w.fs2 : nullptr;
@@ -1018,7 +1008,7 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
     // backward ends) - the launch waits for it, so the update tail is the plain path's two launches (+ the conv all-reduce)
     const bool dp_dense = dense_ready != nullptr;
     if (dp_dense) QLX_HIP(hipStreamWaitEvent(s, dense_ready, 0));
-    const int dseg = (m->f32_update_scheduled && !m->f32_dense_async) || dp_dense ? N.seg_first[kNumVars] - N.seg_first[6] : 0;
+    const int dseg = m->f32_update_scheduled || dp_dense ? N.seg_first[kNumVars] - N.seg_first[6] : 0;
     hipLaunchKernelGGL(k_wreduce32, dim3(nred + (dseg + 3) / 4), dim3(1024), 0, s, R, N, nred, N.seg_first[6], dseg);
     QLX_HIP(hipGetLastError());
     debug_sync(s, "k_wreduce32");
@@ -1057,50 +1047,15 @@ void f32_adam(qlx_model* m, hipStream_t s, float scale) {
   const Adam32Args a = adam_args(m, scale);
   QLX_CHECK(m->f32_update_scheduled ? scale == 1.0f : (m->f32_dense_partials && scale == m->f32_partials_scale), QLX_E_STATE,
             "fp32 update without the dense norm partials of this gradient scale (model_norms first)");
-  const bool dense_here = !m->f32_dense_async;   // else the dense blocks run on f32_aux (f32_dense_async)
-  ProfScope ps(m->prof, "f32_adam", s, dense_here ? 28.0 * kNumParams : 28.0 * kVarOffsetDense);
+  ProfScope ps(m->prof, "f32_adam", s, 28.0 * kNumParams);
   const int nconv = conv_adam_blocks(), ndense = kDenseAdamBlocks;
-  hipLaunchKernelGGL(k_update32, dim3(nconv + (dense_here ? ndense : 0)), dim3(1024), 0, s, a, norm_args(m, scale), nconv, ndense);
+  hipLaunchKernelGGL(k_update32, dim3(nconv + ndense), dim3(1024), 0, s, a, norm_args(m, scale), nconv, ndense);
   QLX_HIP(hipGetLastError());
   debug_sync(s, "k_update32");
   m->f32_update_scheduled = false;
   m->f32_dense_partials = false;
-  m->f32_dense_async = false;
   m->iterations = t;
 }
-
-// The dense variables (W3, b3, W4, b4: 95 % of the update's Adam bytes) are final after the fc1 backward and are next read
-// by the next forward's fc1: their clip-norm segment partials (k_wreduce32's dense blocks) and clip_by_norm + Adam
-// (k_update32's dense blocks) run on a second stream from there, beside the conv backward, the conv update and the next
-// forward's convs.  Same kernels and arithmetic as the one-stream tail, so the results are bit-identical.
-void f32_dense_async(qlx_model* m, hipStream_t s) {
-  if (!m->f32_aux) {
-    QLX_HIP(hipStreamCreateWithFlags(&m->f32_aux, hipStreamNonBlocking));
-    QLX_HIP(hipEventCreateWithFlags(&m->ev_dense_ready, hipEventDisableTiming));
-    QLX_HIP(hipEventCreateWithFlags(&m->ev_dense_done, hipEventDisableTiming));
-  }
-  hipStream_t a = m->f32_aux;
-  QLX_HIP(hipEventRecord(m->ev_dense_ready, s));
-  QLX_HIP(hipStreamWaitEvent(a, m->ev_dense_ready, 0));
-  ProfScope ps(m->prof, "f32_dense_update", a, 28.0 * (kNumParams - kVarOffsetDense));
-  const NormArgs N = norm_args(m, 1.0f);
-  const int dseg = N.seg_first[kNumVars] - N.seg_first[6];
-  const WRed R{};
-  hipLaunchKernelGGL(k_wreduce32, dim3((dseg + 3) / 4), dim3(1024), 0, a, R, N, 0, N.seg_first[6], dseg);
-  hipLaunchKernelGGL(k_update32, dim3(kDenseAdamBlocks), dim3(1024), 0, a, adam_args(m, 1.0f), N, 0, kDenseAdamBlocks);
-  QLX_HIP(hipGetLastError());
-  QLX_HIP(hipEventRecord(m->ev_dense_done, a));
-  debug_sync(a, "dense update (aux stream)");
-  m->f32_dense_async = true;
-  m->dense_pending = true;
-}
-
-void model_dense_join(qlx_model* m, hipStream_t s) {
-  if (!m->dense_pending) return;
-  QLX_HIP(hipStreamWaitEvent(s, m->ev_dense_done, 0));
-  m->dense_pending = false;
-}
-
 
 // ---- frame sparsity of a batch (diagnostic, bench.py): how much of the fp32 conv work the exact skips leave out ----
 // Per sample, in the kernels' own units (the same predicates, re-evaluated from the frames): conv1 forward (tile, kq)

@@ -17,7 +17,6 @@ typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // bf16 a3 row pitch: columns 0..3135 the flattened conv3 output, column 3136 = 1.0 and 3137..3143 = 0 (written once per
 // workspace, k_a3_pad), so the fc1 weight gradient a3^T dz4 over 3137 rows yields db3 as its last row (bgemm.h)
@@ -41,10 +40,6 @@ __host__ __device__ constexpr int frag_index(int row, int k, int K) {
   return (((row >> 4) * (K / 32) + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + (row & 15)) * 8 + (k & 7);
 }
 
-__device__ __forceinline__ bf16x8 zero8() {
-  const uint4 z = {0, 0, 0, 0};
-  return __builtin_bit_cast(bf16x8, z);
-}
 __device__ __forceinline__ bf16x8 ld8(const bf16* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); }
 __device__ __forceinline__ bf16x8 ldfrag(const bf16* base, int slice, int s, int K, int lane) {
   return ld8(base + ((slice * (K / 32) + s) * 64 + lane) * 8);
@@ -56,21 +51,13 @@ __device__ __forceinline__ uint32_t u8pair_bf16(uint32_t w, int s) {
   const uint32_t hi = __builtin_bit_cast(uint32_t, (float)((w >> (s + 8)) & 0xFFu)) & 0xFFFF0000u;
   return lo | hi;
 }
-__device__ __forceinline__ bf16x8 u8x8_to_bf16(uint2 v) {
-  uint4 r;
-  r.x = u8pair_bf16(v.x, 0);
-  r.y = u8pair_bf16(v.x, 16);
-  r.z = u8pair_bf16(v.y, 0);
-  r.w = u8pair_bf16(v.y, 16);
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 // ------------------------------------------------------------------------------------------
 // Fixed-order reductions of per-block fp32 partial slabs.
 
 // out[dst(i)] = sum_c slab[c][i] (deterministic): block = 64 outputs x 4 waves; wave w sums chunk quarter w
 // (8 loads in flight per lane), the quarters are added in fixed order through LDS.  grid = ceil(count/64).
-// CONV1: i < 8192 is conv1's s2d-ordered [k][oc] weight gradient, stored to its HWIO index (the bias
+// conv1: i < 8192 is conv1's s2d-ordered [k][oc] weight gradient, stored to its HWIO index (the bias
 // partials that follow are stored in place).
 __device__ __forceinline__ int conv1_hwio_from_s2d(int i) {   // i = k * 32 + oc, k = ((ij*4 + c)*16) + dx*4 + dy
   const int oc = i & 31, k = i >> 5;
@@ -122,12 +109,6 @@ __device__ __forceinline__ void slab_reduce_block(const float* slab, size_t zstr
       if (lane == 0) sq[blk] = q;
     }
   }
-}
-
-template <bool CONV1 = false>
-__global__ __launch_bounds__(256) void k_slab_reduce(const float* slab, size_t zstride, int chunks, size_t count,
-                                                     float* out) {
-  slab_reduce_block(slab, zstride, chunks, count, out, CONV1, blockIdx.x);
 }
 
 // three independent slab reductions in one launch (segment i owns blocks [first_block[i], first_block[i+1]))

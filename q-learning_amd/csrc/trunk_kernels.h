@@ -46,8 +46,6 @@ static_assert(9 * kA2W * kA2S <= kLdsXf, "A2 aliases X");
 // sample's staging (see k_trunk_fwd)
 constexpr size_t kTrunkFwdLds = (size_t)(kLdsXf + kLdsA1f + kLdsA3) * 2;
 constexpr size_t kConv1WgradLds = (size_t)(kLdsX + kLdsDZ) * 2;
-constexpr int kFrameChunks = 4 * 441;    // 16-byte s2d blocks per sample
-constexpr int kPf = (kFrameChunks + kTrunkThreads - 1) / kTrunkThreads;
 
 // 16 u8 -> 16 bf16 (exact) as two 16-byte halves
 __device__ __forceinline__ void u8x16_to_bf16(uint4 v, uint4& lo, uint4& hi) {
@@ -61,45 +59,7 @@ __device__ __forceinline__ void u8x16_to_bf16(uint4 v, uint4& lo, uint4& hi) {
   hi.w = u8pair_bf16(v.w, 16);
 }
 
-template <int NT>
-constexpr int pf_chunks() { return (kFrameChunks + NT - 1) / NT; }
-
-// register prefetch of one sample's frames: chunk c = slot * 441 + pos (nullptr frame = zeros); NT threads
-template <int NT = kTrunkThreads>
-__device__ __forceinline__ void frames_prefetch(const uint8_t* const* table, int b, int B, uint4 (&pf)[pf_chunks<NT>()]) {
-#pragma unroll
-  for (int u = 0; u < pf_chunks<NT>(); ++u) {
-    const int c = threadIdx.x + u * NT;
-    pf[u] = uint4{0, 0, 0, 0};
-    if (b < B && c < kFrameChunks) {
-      const int slot = c / 441, pos = c - slot * 441;
-      const uint8_t* f = table[b * 4 + slot];
-      // global (not flat) load: a flat load also counts on lgkmcnt, so every LDS wait in the conv phases
-      // would wait for this prefetch too
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      if (f) pf[u] = __builtin_bit_cast(uint4, *(const __attribute__((address_space(1))) u32x4*)(f + pos * 16));
-    }
-  }
-}
-
-// the same with the sample's 4 frame pointers already in LDS (fptr[slot]): no dependent pointer load in the
-// issuing wave's path (the table entry is fetched a sample earlier, see k_trunk_fwd)
-template <int NT = kTrunkThreads>
-__device__ __forceinline__ void frames_prefetch_ptrs(const uint8_t* const* fptr, bool valid, uint4 (&pf)[pf_chunks<NT>()]) {
-#pragma unroll
-  for (int u = 0; u < pf_chunks<NT>(); ++u) {
-    const int c = threadIdx.x + u * NT;
-    pf[u] = uint4{0, 0, 0, 0};
-    if (valid && c < kFrameChunks) {
-      const int slot = c / 441, pos = c - slot * 441;
-      const uint8_t* f = fptr[slot];
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      if (f) pf[u] = __builtin_bit_cast(uint4, *(const __attribute__((address_space(1))) u32x4*)(f + pos * 16));
-    }
-  }
-}
-
-// Slot-major variant for the forward trunk: thread tid < 441 owns s2d block pos = tid of all 4 slots, so the
+// Register prefetch of one sample's frames, slot-major: thread tid < 441 owns s2d block pos = tid of all 4 slots, so the
 // frame pointer of each load is wave-uniform (read from LDS, fptr[slot]) and the per-lane address is one
 // 32-bit offset - no 64-bit per-chunk addresses to keep live across the sample.
 __device__ __forceinline__ void frames_prefetch_slots(const uint8_t* const* fptr, bool valid, uint4 (&pf)[4]) {
@@ -130,23 +90,6 @@ __device__ __forceinline__ void frames_stage_slots(bf16* X, const uint4 (&pf)[4]
   }
 }
 
-// u8 -> bf16 into the staged image X [441][XS] (ch = slot * 16 + sub-pixel)
-template <int NT = kTrunkThreads, int XS = kXS>
-__device__ __forceinline__ void frames_stage(bf16* X, const uint4 (&pf)[pf_chunks<NT>()]) {
-#pragma unroll
-  for (int u = 0; u < pf_chunks<NT>(); ++u) {
-    const int c = threadIdx.x + u * NT;
-    if (c < kFrameChunks) {
-      const int slot = c / 441, pos = c - slot * 441;
-      uint4 lo, hi;
-      u8x16_to_bf16(pf[u], lo, hi);
-      uint4* d = reinterpret_cast<uint4*>(X + pos * XS + slot * 16);
-      d[0] = lo;
-      d[1] = hi;
-    }
-  }
-}
-
 // LDS rows [rows][stride] -> global contiguous [rows][cols] with 16-byte chunks
 template <int ROWS, int COLS, int STRIDE, int NT = kTrunkThreads>
 __device__ __forceinline__ void lds_copy_out(const bf16* src, bf16* dst) {
@@ -168,8 +111,6 @@ __device__ __forceinline__ void lds_copy_out_pitched(const bf16* src, bf16* dst)
 }
 
 __device__ __forceinline__ bf16x8 lds8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-
-__device__ __forceinline__ bf16 relu_bf16(float v) { return (bf16)(v > 0.0f ? v : 0.0f); }
 
 // One wave's share of a per-sample conv GEMM in the D^T = W X^T orientation: the lane's weight registers
 // w[s] (row = output channel lane & 15 of the wave's 16-channel slice, k = 8 (lane >> 4) + j) are the A
@@ -214,24 +155,13 @@ __device__ __forceinline__ uint2 pack4_bf16(float a, float b, float c, float d) 
 __device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
 
 // a1 [B][400][32], a2 [B][81][64] (written when STORE12), a3 [B][49][64] (always)
-// TIMING (development only): wave 0 accumulates s_memtime cycles per phase (staging, conv1, conv2, conv3)
-// into timing[blockIdx.x * 4 + phase]
-template <bool STORE12, bool TIMING = false>
+template <bool STORE12>
 __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* const* __restrict__ table, int B,
                                                                 const bf16* __restrict__ wf0, const bf16* __restrict__ wf1,
                                                                 const bf16* __restrict__ wf2, const float* __restrict__ bias0,
                                                                 const float* __restrict__ bias1,
                                                                 const float* __restrict__ bias2, bf16* __restrict__ a1,
-                                                                bf16* __restrict__ a2, bf16* __restrict__ a3,
-                                                                unsigned long long* __restrict__ timing = nullptr) {
-  unsigned long long ph[4] = {0, 0, 0, 0}, tm = 0;
-  auto mark = [&](int i) {
-    if constexpr (TIMING) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (i >= 0) ph[i] += t - tm;
-      tm = t;
-    }
-  };
+                                                                bf16* __restrict__ a2, bf16* __restrict__ a3) {
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
   bf16* X = lds;
   bf16* A1 = lds + kLdsXf;
@@ -270,13 +200,11 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* c
   lds_barrier();
   frames_prefetch_slots(sptr, (int)blockIdx.x < B, pf);
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    mark(-1);
     lds_barrier();   // previous sample's conv phases are done with X / A2 (and the pointer slots)
     frames_stage_slots<kXW>(X, pf);
     if (threadIdx.x < 4) sptr[threadIdx.x] = pnext;
     if (b != (int)blockIdx.x) lds_copy_out<49, 64, kA3S>(A3, a3 + (size_t)(b - gridDim.x) * kA3Ld);
     lds_barrier();
-    mark(0);
     frames_prefetch_slots(sptr, b + (int)gridDim.x < B, pf);
     if (threadIdx.x < 4 && b + 2 * (int)gridDim.x < B) pnext = table[(b + 2 * gridDim.x) * 4 + threadIdx.x];
     // conv1: M = 400 (25 tiles of 16), N = 32, K = 256: k-step s covers tap (i, j) = (s >> 2, (s >> 1) & 1)
@@ -292,7 +220,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* c
           *reinterpret_cast<uint2*>(A1 + (ox * kA1W + m - ox * 20) * kA1S + c1 + 4 * g) = bias_relu4(bv, acc);
         });
     lds_barrier();
-    mark(1);
     if (STORE12) lds_copy_out_pitched<400, 32, kA1S, 20, kA1W>(A1, a1 + (size_t)b * 12800);
     // conv2: 4x4 stride 2 over A1 [20][20][32]; M = 81 (6 tiles), k-step s = tap (kh, kw) = (s >> 2, s & 3)
     conv_tiles<16, 4>(
@@ -307,7 +234,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* c
           if (m < 81) *reinterpret_cast<uint2*>(A2 + (p * kA2W + m - p * 9) * kA2S + c2 + 4 * g) = bias_relu4(bv, acc);
         });
     lds_barrier();
-    mark(2);
     if (STORE12) lds_copy_out_pitched<81, 64, kA2S, 9, kA2W>(A2, a2 + (size_t)b * 5184);
     // conv3: 3x3 stride 1 over A2 [9][9][64]; M = 49 (4 tiles), k-step s: tap s >> 1, channel half s & 1
     conv_tiles<18, 3>(
@@ -322,11 +248,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* c
           const int m = t * 16 + r;
           if (m < 49) *reinterpret_cast<uint2*>(A3 + m * kA3S + c2 + 4 * g) = bias_relu4(bv, acc);
         });
-    mark(3);
-  }
-  if constexpr (TIMING) {
-    if (threadIdx.x == 0)
-      for (int i = 0; i < 4; ++i) timing[blockIdx.x * 4 + i] = ph[i];
   }
   lds_barrier();
   const int last = (int)blockIdx.x + ((B - 1 - (int)blockIdx.x) / (int)gridDim.x) * (int)gridDim.x;
@@ -334,7 +255,7 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_fwd(const uint8_t* c
 }
 
 // conv1 weight gradient: per block fp32 partial dW[256 (s2d k)][32] followed by the bias partial db[32] in
-// slab[blockIdx.x] (stride kConv1SlabStride); reduced over blocks in fixed order by k_slab_reduce<true>.
+// slab[blockIdx.x] (stride kConv1SlabStride); reduced over blocks in fixed order by k_slab_reduce3 (its conv1 segment).
 constexpr int kConv1SlabStride = 8192 + 32;
 // Wave w owns k tiles 2w, 2w+1 (one s2d tap (i, j) = ((w >> 1) >> 1, (w >> 1) & 1), 32 channels) x both
 // 16-column n tiles.  m-steps of 32 im2col rows (13 per sample, rows 400..415 have dz = 0).
@@ -570,22 +491,10 @@ constexpr int kLdsPad = kLdsPad3 + kLdsPad2;   // both images
 constexpr int kLdsA2M = 81 * 72;           // staged a2 (ReLU mask of dz2), row stride 72
 constexpr size_t kTrunkBwdLds = (size_t)(kLdsPad + kLdsA2M + kLdsA1) * 2;
 
-// TIMING (development only): wave 0's s_memtime cycles per phase (staging + dz1 copy-out, dz2, dz1) ->
-// timing[blockIdx.x * 4 + phase]
-template <bool TIMING = false>
 __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_bwd_data(const bf16* __restrict__ dz3, const bf16* __restrict__ a2,
                                                                      const bf16* __restrict__ a1, int B,
                                                                      const bf16* __restrict__ wb2, const bf16* __restrict__ wb1,
-                                                                     bf16* __restrict__ dz2, bf16* __restrict__ dz1,
-                                                                     unsigned long long* __restrict__ timing) {
-  unsigned long long ph[4] = {0, 0, 0, 0}, tm = 0;
-  auto mark = [&](int i) {
-    if constexpr (TIMING) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (i >= 0) ph[i] += t - tm;
-      tm = t;
-    }
-  };
+                                                                     bf16* __restrict__ dz2, bf16* __restrict__ dz1) {
   extern __shared__ __attribute__((aligned(16))) bf16 lds[];
   bf16* P3 = lds;                   // dz3, interior (oh + 2, ow + 2)
   bf16* P2 = lds + kLdsPad3;        // dz2 (masked), interior (oh + 1, ow + 1)
@@ -645,7 +554,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_bwd_data(const bf16*
   prefetch(blockIdx.x);
   lds_barrier();   // borders zeroed
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    mark(-1);
     lds_barrier();   // previous sample's readers are done
 #pragma unroll
     for (int u = 0; u < kPB; ++u) {
@@ -660,7 +568,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_bwd_data(const bf16*
     }
     if (b != (int)blockIdx.x) dz1_out(b - gridDim.x);
     lds_barrier();
-    mark(0);
     prefetch(b + gridDim.x);
     prefetch_mask(b);
     // phase A: dz2 (wave: channel slice c3, tiles wave >> 2, +2, ...)
@@ -682,7 +589,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_bwd_data(const bf16*
           }
         });
     lds_barrier();
-    mark(1);
     // dz2 -> global (81 x 64)
     for (int c = tid; c < 648; c += kTrunkThreads) {
       const int row = c >> 3, col = (c & 7) * 8, oh = row / 9, ow = row - oh * 9;
@@ -710,11 +616,6 @@ __global__ __launch_bounds__(kTrunkThreads, 1) void k_trunk_bwd_data(const bf16*
           });
     }
     lds_barrier();
-    mark(2);
-  }
-  if constexpr (TIMING) {
-    if (threadIdx.x == 0)
-      for (int i = 0; i < 4; ++i) timing[blockIdx.x * 4 + i] = ph[i];
   }
   lds_barrier();
   const int last = (int)blockIdx.x + ((B - 1 - (int)blockIdx.x) / (int)gridDim.x) * (int)gridDim.x;
