@@ -1,7 +1,8 @@
 // fp32 Nature-DQN kernels for gfx950: the reference's arithmetic (Keras float32 graph,
 // create_ql_model_breakout_84x84x4_3_32.py:20-33,37-61) on v_mfma_f32_16x16x4_f32.
 //
-// Every GEMM-shaped op is one LDS-tiled implicit-GEMM kernel (gemm_body) driven by a per-layer operand policy.
+// Every GEMM-shaped op is one LDS-tiled implicit-GEMM kernel driven by a per-layer operand policy, which describes its
+// operand addresses once: as streams (gemm_body_s), or as ldA / ldB (gemm_body: the dense-frame forward, the constant rows).
 // v_mfma_f32_16x16x4_f32 is bit-for-bit a k-ordered fmaf chain over its four k (lane group 0 first; measured on
 // MI355X, scripts/mfma_f32_probe.hip), and each output element keeps ONE accumulator over the whole reduction,
 // consumed in ascending k.  So every output is exactly
@@ -468,15 +469,45 @@ struct Grid {
 // Operand streams: slab staging with no per-slab vector address arithmetic.
 //
 // On gfx950 the fp32 MFMA and the VALU do not overlap: an MFMA loop and a VALU loop on one SIMD take the sum of their
-// times (scripts/coexec_probe.hip), so every vector instruction of a slab loop is MFMA time lost.  The ldA / ldB form of
-// the policies recomputes each load's 64-bit address per slab (divisions, masks, selects: 40 to 100 VALU instructions per
-// slab of 32 MFMAs).  A stream computes its per-lane byte offsets once per tile; per slab it adds a wave-uniform offset
-// (SALU) and issues raw buffer loads, whose range check returns zeros for a lane offset past the buffer (rows past the
-// batch) or for a whole-slab descriptor of zero records (gather rows past a chunk).
+// times (scripts/coexec_probe.hip), so every vector instruction of a slab loop is MFMA time lost.  The ldA / ldB form
+// (gemm_body: the dense-frame forward and the constant-row tiles) recomputes each load's 64-bit address per slab (divisions,
+// masks, selects: 40 to 100 VALU instructions per slab of 32 MFMAs).  A stream computes its per-lane byte offsets once per
+// tile; per slab it adds a wave-uniform offset (SALU) and issues raw buffer loads, whose range check returns zeros for a
+// lane offset past the buffer (rows past the batch, gather rows past a chunk).  A streamed policy has no other description
+// of its operand addresses: the host address replay (scripts/q32_host_check.hip) runs these streams.
 //   load(s, regs)  - issue the slab's loads (s wave-uniform)
 //   store(t, regs) - write them into the operand's LDS image t (the Opnd layout the fragment reads use)
 constexpr uint32_t kOob = 0x80000000u;   // lane offset past any buffer: the load returns zeros
+// byte count of a descriptor with no end of its own (PConvFwdL: one descriptor from `in` or cx, whichever is lower, over
+// both; its lane offsets are bounded by the list entries)
+constexpr uint32_t kNoEnd = 0x7FFFFFF0u;
 
+#ifdef QLX_Q32_POLICIES_ONLY
+// Host address replay: a descriptor is its base and byte count (which must lie inside the host buffer, kNoEnd apart).  A load
+// is in range when it lies inside the count with and without the scalar offset - it then reads the host buffer, under
+// AddressSanitizer - and zero-filled when it lies past the count either way at a lane offset the stream chose for that
+// (>= host_loads.past: kOob, or what a packed table's all-ones entry decodes to).  Any other load ends the replay.
+struct Rsrc { const char* base; uint32_t bytes; };
+struct HostLoads {
+  const char* policy; int block, slab, tid; uint32_t past; long in_range, zero_filled;
+  // (the tool's: on a failure they print the policy, block, slab and thread and exit)
+  void check_rsrc(const char* base, uint32_t bytes) const;   // the bytes all lie inside a host buffer
+  void bad_load(uint32_t voff, uint32_t soff, uint32_t bytes) const;
+};
+inline HostLoads host_loads{};
+inline Rsrc buf_rsrc(const void* base, uint32_t bytes) {
+  if (bytes != kNoEnd) host_loads.check_rsrc(static_cast<const char*>(base), bytes);
+  return Rsrc{static_cast<const char*>(base), bytes};
+}
+inline f32x4 buf_ld4(Rsrc r, uint32_t voff, uint32_t soff) {
+  const uint64_t v = voff, vs = v + soff;
+  const bool in = v + 16 <= r.bytes && vs + 16 <= r.bytes, out = v >= r.bytes && vs >= r.bytes && voff >= host_loads.past;
+  if (in == out) host_loads.bad_load(voff, soff, r.bytes);
+  ++(in ? host_loads.in_range : host_loads.zero_filled);
+  return in ? *reinterpret_cast<const volatile f32x4*>(r.base + vs) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+#else
+using Rsrc = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, uint32_t bytes) {
   // descriptor words from provably wave-uniform inputs (otherwise each load is wrapped in a waterfall loop)
   const uint64_t a = (uint64_t)base;
@@ -490,6 +521,7 @@ __device__ __forceinline__ f32x4 buf_ld4(__amdgpu_buffer_rsrc_t r, uint32_t voff
 __device__ __forceinline__ float buf_ld1(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
+#endif
 
 // Affine stream over an Opnd<ROWS, KMAJ> image: element (row, k) of slab s at lane_off(row, k) + slab_off(s) bytes.
 // RMAJ: k runs along memory (16-byte chunks of 4 k), KMAJ: rows run along memory (chunks of 4 rows).  KMASK: lanes whose
@@ -499,7 +531,7 @@ struct AffineStream {
   using O = Opnd<ROWS, KMAJ>;
   static constexpr int N = (O::F4 + T - 1) / T;
   using Regs = f32x4[N];
-  __amdgpu_buffer_rsrc_t rs;
+  Rsrc rs;
   uint32_t vo[N];
   int kk[N];        // (KMASK) the lane's k of each load
   int tid;
@@ -575,8 +607,9 @@ struct TableK4Stream {
   static_assert(T == 256, "table gather stream: four waves");
   using O = Opnd<64, true>;
   static constexpr int N = 2;   // float4 loads per thread per slab
+  static constexpr uint32_t PAST = SHIFT == 0 && MASK == 0xFFFFFFFFu ? kOob : MASK * MUL;   // what an entry past the end adds
   using Regs = f32x4[N];
-  __amdgpu_buffer_rsrc_t rs;
+  Rsrc rs;
   uint32_t vo;   // the lane's row-group offset
   int tid, g, k0;
   const uint32_t* tbl;   // LDS: byte offset of each k of the tile's reduction (kOob past its end), in the operand images' pads
@@ -591,7 +624,7 @@ struct TableK4Stream {
     rs = buf_rsrc(base, bytes);
     tid = tid_;
     g = (tid & 63) >> 4;
-    k0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 4;
+    k0 = q32_uniform(tid >> 6) * 4;
     vo = row_off;
   }
   __device__ void load(int kbase, Regs& rg) const {
@@ -627,11 +660,10 @@ constexpr size_t gemm_lds_bytes() {
 // and epilogue, with the slab staging done by the policy's streams:
 //   typename P::Streams st = p.streams(z, row0, col0, tid);   per tile
 //   st.load(s, x) / st.store(s, x, As, Bs)                    x: a P::Streams::Regs register set
-// (a policy whose Streams is void - a tile shape its streams do not cover - stays on the ldA / ldB core)
 template <class P, class = void>
 struct HasStreams : std::false_type {};
 template <class P>
-struct HasStreams<P, std::void_t<typename P::Streams>> : std::bool_constant<!std::is_void_v<typename P::Streams>> {};
+struct HasStreams<P, std::void_t<typename P::Streams>> : std::true_type {};
 
 // K split (round 6, policies with KSPLIT = G > 1 or KSEQ = Q > 1): the reduction is G (Q) chains over consecutive equal
 // slab ranges, combined ((C0 + C1) + ..) before the epilogue - the same value either way: KSPLIT runs the chains in G
@@ -1076,7 +1108,7 @@ struct PConvFwdL {
   // a row's background taps read the constant row cx instead (one buffer spans `in` and cx: both live in the model's
   // workspace), a per-lane select per slab.  B = the weight rows, affine.
   struct StreamsImpl {
-    __amdgpu_buffer_rsrc_t ra;
+    Rsrc ra;
     uint32_t vo[NA], cxo[NA], msk[NA];
     int tid;
     AffineStream<BN_, true, T> b;
@@ -1121,7 +1153,7 @@ struct PConvFwdL {
     const char* lo = (const char*)in;
     const char* base = SEL && (const char*)cx < lo ? (const char*)cx : lo;
     const uint32_t in_off = (uint32_t)(lo - base), cx_off = SEL ? (uint32_t)((const char*)cx - base) : 0u;
-    st.ra = buf_rsrc(base, 0x7FFFFFF0u);   // (row offsets are bounded by the list entries: b * R + p of this chunk)
+    st.ra = buf_rsrc(base, kNoEnd);   // (row offsets are bounded by the list entries: b * R + p of this chunk)
     int rows[NA], raws[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
@@ -1229,10 +1261,6 @@ struct PFc1FwdT {
   int M;
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return 3136 / BK; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    return ld4m(a3 + (size_t)(row < M ? row : 0) * 3136 + s * BK + k, row < M);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const { return ld4(w3 + (size_t)(s * BK + k) * 512 + col); }
   __device__ void epi(int, int row, int col, f32x4 v) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1306,10 +1334,6 @@ struct PFc1DgradT {
   };
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return 512 / BK; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    return ld4m(dz4 + (size_t)(row < M ? row : 0) * 512 + s * BK + k, row < M);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const { return ld4(w3 + (size_t)col * 512 + s * BK + k); }
   __device__ void epi(int z, int row, int col, f32x4 v) const { epi_post(z, row, col, v, epi_pre(z, row, col)); }
   // the ReLU mask of the four rows, loaded before the slab loop (HasEpiPre; rows past M read row 0)
   __device__ Pre epi_pre(int, int row, int col) const {
@@ -1366,15 +1390,6 @@ struct PFc1WgradT {
   int B;
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return (B + BK - 1) / BK; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    const int b = s * BK + k;
-    const bool ok = b < B && row < 3136;
-    return ld4m(a3 + (ok ? (size_t)b * 3136 + row : 0), ok);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const {
-    const int b = s * BK + k;
-    return ld4m(dz4 + (size_t)(b < B ? b : 0) * 512 + col, b < B);
-  }
   __device__ void epi(int, int row, int col, f32x4 v) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1447,16 +1462,6 @@ struct PConv3DgradPx {
     return q;
   }
   __host__ __device__ int nslabs(int z) const { return 2 * px(z).ntap; }
-  __device__ f32x4 ldA(int z, int s, int row, int k) const {
-    const Px q = px(z);
-    const int t = s >> 1, kh = q.kh0 + t / q.nkw, kw = q.kw0 + t % q.nkw;
-    return ld4m(dz3 + ((size_t)((row < B ? row : 0) * 7 + q.ih - kh) * 7 + q.iw - kw) * 64 + (s & 1) * 32 + k, row < B);
-  }
-  __device__ f32x4 ldB(int z, int s, int col, int k) const {   // W2[kh][kw][c = col][oc]
-    const Px q = px(z);
-    const int t = s >> 1, kh = q.kh0 + t / q.nkw, kw = q.kw0 + t % q.nkw;
-    return ld4(w2 + ((size_t)(kh * 3 + kw) * 64 + col) * 64 + (s & 1) * 32 + k);
-  }
   __device__ void epi(int z, int row, int col, f32x4 v) const { epi_post(z, row, col, v, epi_pre(z, row, col)); }
   __device__ Pre epi_pre(int z, int row, int col) const {
     const Px q = px(z);
@@ -1556,17 +1561,6 @@ struct PConv2DgradPx {
     return q;
   }
   __host__ __device__ int nslabs(int z) const { return 2 * px(z).ntap; }
-  __device__ f32x4 ldA(int z, int s, int row, int k) const {
-    const Px q = px(z);
-    const int t = s >> 1, th = q.th0 + t / q.ntw, tw = q.tw0 + t % q.ntw;
-    return ld4m(dz2 + ((size_t)((row < B ? row : 0) * 9 + q.i - th) * 9 + q.j - tw) * 64 + (s & 1) * 32 + k, row < B);
-  }
-  __device__ f32x4 ldB(int z, int s, int col, int k) const {   // W1[kh][kw][c][oc], col = (py, px, c)
-    const Px q = px(z);
-    const int t = s >> 1, th = q.th0 + t / q.ntw, tw = q.tw0 + t % q.ntw;
-    const int cls = col >> 5, kh = (cls >> 1) + 2 * th, kw = (cls & 1) + 2 * tw;
-    return ld4(w1 + ((size_t)(kh * 4 + kw) * 32 + (col & 31)) * 64 + (s & 1) * 32 + k);
-  }
   __device__ void epi(int z, int row, int col, f32x4 v) const { epi_post(z, row, col, v, epi_pre(z, row, col)); }
   __device__ Pre epi_pre(int z, int row, int col) const {
     const Px q = px(z);
@@ -1666,19 +1660,6 @@ struct PConvWgrad {
     return n;
   }
   __host__ __device__ int nslabs(int z) const { return ((CMP ? kept_in(z) : rows_in(z)) + BK - 1) / BK; }
-  __device__ f32x4 ldA(int z, int s, int row, int k) const {
-    const int r0 = s * BK + k;
-    const bool ok = r0 < rows_in(z);
-    const int r = ok ? r0 : 0;
-    const int tap = row / C, c = row - tap * C, kh = tap / KS, kw = tap - kh * KS;
-    const int bl = r / P, p = r - bl * P, oh = p / OW, ow = p - oh * OW, b = z * SC + bl;
-    return ld4m(in + ((size_t)(b * H + oh * S + kh) * W + ow * S + kw) * C + c, ok);
-  }
-  __device__ f32x4 ldB(int z, int s, int col, int k) const {
-    const int r = s * BK + k;
-    const bool ok = r < rows_in(z);
-    return ld4m(dz + ((size_t)z * SC * P + (ok ? r : 0)) * OC + col, ok);
-  }
   __device__ void epi(int z, int row, int col, f32x4 v) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r) slab[((size_t)z * (MROWS + 1) + row + r) * OC + col] = v[r];
@@ -1764,20 +1745,17 @@ struct PConvWgrad {
       b.store(bs, x.b);
     }
   };
-  // (the table stream stages 64-row tiles on four waves: other tile shapes keep the ldA / ldB core)
-  // (in place against the ldA / ldB core: 262.3K vs 263.0K env-steps/s, conv2 pair 102.0 vs 102.2 us - neutral; kept as the
+  // (in place against an ldA / ldB core: 262.3K vs 263.0K env-steps/s, conv2 pair 102.0 vs 102.2 us - neutral; kept as the
   // one path: the weight-gradient tiles then issue no per-slab address arithmetic)
-  static constexpr bool STREAMED = BM_ == 64 && WM_ * WN_ == 4;
-  static_assert(!CMP || STREAMED, "compacted weight gradient: streamed tiles");
-  using Streams = std::conditional_t<STREAMED, std::conditional_t<CMP, StreamsCmp, StreamsImpl>, void>;
+  static_assert(BM_ == 64 && WM_ * WN_ == 4, "weight gradient: the table stream stages 64-row tiles on four waves");
+  using Streams = std::conditional_t<CMP, StreamsCmp, StreamsImpl>;
   static_assert(!TPADS || KMAX <= 4 * 32 * 16, "weight-gradient chunk: the offset table lives in the four images' pads");
   // TableK4Stream::slot() places the table in the pad columns 64..79 of four 64-row KMAJ images (A and B, two buffers):
   // a B tile of another width would put it into B's live data
-  static_assert(!STREAMED || !TPADS || BN_ == 64, "streamed weight-gradient tiles with the table in the pads need BN = 64");
-  static constexpr size_t EXTRA_LDS = STREAMED && !TPADS ? (size_t)KMAX * 4 : 0;
-  template <class ST = Streams>
-  __device__ ST streams(int z, int row0, int col0, int tid) const {
-    ST st;
+  static_assert(!TPADS || BN_ == 64, "weight-gradient tiles with the table in the pads need BN = 64");
+  static constexpr size_t EXTRA_LDS = !TPADS ? (size_t)KMAX * 4 : 0;
+  __device__ Streams streams(int z, int row0, int col0, int tid) const {
+    Streams st;
     st.z = z;
     const int m = row0 + (tid & 15) * 4, tap = m / C, c = m - tap * C, kh = tap / KS, kw = tap - kh * KS;
     if constexpr (CMP) {

@@ -1,6 +1,8 @@
 // Host-side address check of the fp32 GEMM policies (qnet32_kernels.h): every operand load and epilogue store a
 // launch of qnet32.hip would issue is replayed on the CPU against host buffers of exactly the device workspace
-// sizes, under AddressSanitizer.  Dev tool (no GPU needed):
+// sizes, under AddressSanitizer, through the code the device runs: a policy with Streams builds its streams per
+// thread, writes their LDS tables and issues every slab's buffer loads (host stand-ins for the descriptor and the
+// loads, which also check the descriptor's byte count); the others go through ldA / ldB.  Dev tool (no GPU needed):
 //   hipcc --offload-host-only -x hip -I q-learning_amd/csrc -I include -fsanitize=address -g -O1 \
 //         scripts/q32_host_check.hip -o /tmp/q32_host_check && /tmp/q32_host_check 32 128
 #include <hip/hip_runtime.h>
@@ -9,8 +11,13 @@
 #define QLX_Q32_POLICIES_ONLY
 #include "qnet32_kernels.h"
 
+#include <sanitizer/asan_interface.h>
+
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <set>
+#include <utility>
 #include <vector>
 
 using namespace qlx;
@@ -20,13 +27,31 @@ static Grid grid(int M, int BM, int N, int BN, int nz) { return Grid{(M + BM - 1
 
 static long checks = 0;
 
-template <class P>
-static void replay(const P& p, const char* name) {
+void HostLoads::bad_load(uint32_t voff, uint32_t soff, uint32_t bytes) const {
+  fprintf(stderr, "%s: block %d slab %d thread %d: buffer load at lane offset %u + scalar offset %u is neither inside the descriptor's "
+                  "%u bytes nor a load the stream put past them (lane offset >= %u)\n", policy, block, slab, tid, voff, soff, bytes, past);
+  exit(1);
+}
+// (a launch builds the same few descriptors in every thread: each distinct one is looked up in the shadow memory once)
+void HostLoads::check_rsrc(const char* base, uint32_t bytes) const {
+  static std::set<std::pair<const char*, uint32_t>> held;
+  if (!held.insert({base, bytes}).second || !__asan_region_is_poisoned(const_cast<char*>(base), bytes)) return;
+  fprintf(stderr, "%s: block %d thread %d: a descriptor of %u bytes reaches past its host buffer\n", policy, block, tid, bytes);
+  exit(1);
+}
+
+// STREAMS = false for a policy with Streams: the tiles the device sends to gemm_body explicitly (ConstRows).
+// past: the smallest lane offset at which the launch's streams ask for zeros
+template <class P, bool STREAMS = HasStreams<P>::value>
+static void replay(const P& p, const char* name, uint32_t past = kOob) {
   using OA = Opnd<P::BM, P::A_KMAJ>;
   using OB = Opnd<P::BN, P::B_KMAJ>;
-  constexpr int T = P::WM * P::WN * 64;
+  constexpr int T = P::WM * P::WN * 64;   // threads of one K group
   constexpr int TM = P::BM / (P::WM * 16), TN = P::BN / (P::WN * 16);
   volatile float sink = 0.0f;
+  host_loads = HostLoads{name, 0, 0, 0, past, 0, 0};
+  long ld = 0;
+  float* lds = static_cast<float*>(std::malloc(gemm_lds_bytes<P>()));   // (the streams' tables: exact size)
   for (int lb = 0; lb < p.g.blocks(); ++lb) {
     int tm, tn, z;
     p.decode(lb, tm, tn, z);
@@ -34,23 +59,47 @@ static void replay(const P& p, const char* name) {
     if constexpr (HasActive<P>::value) {
       if (!p.active(z, row0)) continue;
     }
-    const int ns = p.nslabs(z);
-    for (int s = 0; s < ns; ++s) {
-      for (int idx = 0; idx < OA::F4; ++idx) {
-        int r, k;
-        OA::coord(idx, r, k);
-        f32x4 v;
-        if constexpr (HasACtx<P>::value) v = p.ldA_c(p.a_ctx(z, row0, idx % T), idx / T, z, s, row0 + r, k);
-        else v = p.ldA(z, s, row0 + r, k);
-        sink = sink + v[0];
-        ++checks;
+    host_loads.block = lb;
+    if constexpr (STREAMS) {   // gemm_body_s: per K group the streams of its T threads, their tables, then the slabs
+      using St = typename P::Streams;
+      constexpr int G = KSplitOf<P>::value, GROUP_LDS = 2 * (OA::FLOATS + OB::FLOATS);
+      const int ns = p.nslabs(z) / G;
+      static std::vector<St> st(T);
+      for (int tid = 0; tid < T; ++tid) {   // (the same in every group)
+        host_loads.tid = tid;
+        st[tid] = p.streams(z, row0, col0, tid);
       }
-      for (int idx = 0; idx < OB::F4; ++idx) {
-        int r, k;
-        OB::coord(idx, r, k);
-        const f32x4 v = p.ldB(z, s, col0 + r, k);
-        sink = sink + v[0];
-        ++checks;
+      for (int kg = 0; kg < G; ++kg) {
+        if constexpr (HasPrepare<St>::value)
+          for (int tid = 0; tid < T; ++tid) st[tid].prepare(lds + kg * GROUP_LDS, ns);
+        for (int s = 0; s < ns; ++s) {
+          host_loads.slab = kg * ns + s;
+          for (int tid = 0; tid < T; ++tid) {
+            host_loads.tid = tid;
+            typename St::Regs x;
+            st[tid].load(kg * ns + s, x);
+          }
+        }
+      }
+    } else {
+      const int ns = p.nslabs(z);
+      for (int s = 0; s < ns; ++s) {
+        for (int idx = 0; idx < OA::F4; ++idx) {
+          int r, k;
+          OA::coord(idx, r, k);
+          f32x4 v;
+          if constexpr (HasACtx<P>::value) v = p.ldA_c(p.a_ctx(z, row0, idx % T), idx / T, z, s, row0 + r, k);
+          else v = p.ldA(z, s, row0 + r, k);
+          sink = sink + v[0];
+          ++ld;
+        }
+        for (int idx = 0; idx < OB::F4; ++idx) {
+          int r, k;
+          OB::coord(idx, r, k);
+          const f32x4 v = p.ldB(z, s, col0 + r, k);
+          sink = sink + v[0];
+          ++ld;
+        }
       }
     }
     for (int wave = 0; wave < T / 64; ++wave) {
@@ -72,7 +121,10 @@ static void replay(const P& p, const char* name) {
         for (int t = 0; t < P::BN; ++t) p.epi_bias(z, col0 + t, 0.0f);
     }
   }
-  printf("%-24s blocks %6d ok\n", name, p.g.blocks());
+  std::free(lds);
+  if (STREAMS) printf("%-24s blocks %6d buffer loads %10ld in range %9ld zero-filled ok\n", name, p.g.blocks(), host_loads.in_range, host_loads.zero_filled);
+  else printf("%-24s blocks %6d ldA / ldB loads %7ld ok\n", name, p.g.blocks(), ld);
+  checks += ld + host_loads.in_range + host_loads.zero_filled;
 }
 
 template <class T>
@@ -93,7 +145,15 @@ int main(int argc, char** argv) {
   for (size_t i = 0; i < table.size(); ++i)   // every 5th entry null: a ring slot before an episode's first frame
     table[i] = i % 5 == 3 ? nullptr : buf<uint8_t>(kFramePix);
   const uint8_t* const* tab = table.data();
-  float* a1 = buf<float>((size_t)C * 12800); float* a2 = buf<float>((size_t)C * 5184); float* a3 = buf<float>((size_t)C * 3136);
+  // a1, a2, a3 and the constant rows (relu(b0) [32], c2 [64], c3 [64]) in one allocation in f32_workspace's order, as on the
+  // device: the list forward's one descriptor spans `in` and cx (PConvFwdL::streams).  The gaps between them are poisoned.
+  const size_t asz[4] = {(size_t)C * 12800 * 4, (size_t)C * 5184 * 4, (size_t)C * 3136 * 4, 160 * 4};
+  size_t aoff[5] = {0};
+  for (int i = 0; i < 4; ++i) aoff[i + 1] = (aoff[i] + asz[i] + 255) / 256 * 256 + 256;
+  char* arena = buf<char>(aoff[4]);
+  for (int i = 0; i < 4; ++i) ASAN_POISON_MEMORY_REGION(arena + aoff[i] + asz[i], aoff[i + 1] - aoff[i] - asz[i]);
+  float* a1 = (float*)(arena + aoff[0]); float* a2 = (float*)(arena + aoff[1]); float* a3 = (float*)(arena + aoff[2]);
+  float* cx = (float*)(arena + aoff[3]); float* c2 = cx + 32; float* c3 = cx + 96;
   float* a4 = buf<float>((size_t)n * 512);
   // forward over n, every launch form of f32_forward.  Dense frames (no row lists): the 64 x 64 tiles of the chunk-size
   // pass, the training batch's 64 x 32 tiles and its balanced grid's 16-row remainder tiles (RowShift)
@@ -115,9 +175,6 @@ int main(int argc, char** argv) {
     for (int i = 0; i < kListSlots * cap2; ++i) rl2[i] = (int)(((long)i * 7919) % (n * 81));
     for (int i = 0; i < kListSlots * cap3; ++i) rl3[i] = (int)(((long)i * 7919) % (n * 49)) | ((i * 37) % 511) << 20;
     unsigned long long* cnt = buf<unsigned long long>(2 * kListSlots * kCntStride);
-    float* cx = buf<float>(64);
-    float* c2 = buf<float>(64);
-    float* c3 = buf<float>(64);
     for (int full = 0; full < 2; ++full) {
       for (int x = 0; x < kListSlots; ++x) {
         const unsigned long long k2 = full ? cap2 : cap2 * 2 / 3, k3 = full ? cap3 : cap3 * 2 / 3;
@@ -133,8 +190,9 @@ int main(int argc, char** argv) {
       replay(PConv3FwdL<64, 64, 2, 2>{lg(cap3, 64, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L big");
       replay(PConv3FwdL<32, 64, 2, 2>{lg(cap3, 32, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L");
     }
-    replay(PConv2FwdL<16, 64, 1, 4>{Grid{1, 1, 1}, a1, w1, b1, a2, rl2, cap2, cnt, cx, c2}, "const row c2");
-    replay(PConv3FwdL<16, 64, 1, 4>{Grid{1, 1, 1}, a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, c3}, "const row c3");
+    // (ConstRows runs these two on gemm_body: their ldA_c / ldB)
+    replay<PConv2FwdL<16, 64, 1, 4>, false>({Grid{1, 1, 1}, a1, w1, b1, a2, rl2, cap2, cnt, cx, c2}, "const row c2");
+    replay<PConv3FwdL<16, 64, 1, 4>, false>({Grid{1, 1, 1}, a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, c3}, "const row c3");
   }
   replay(PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd B");
   replay(PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd S");
@@ -164,7 +222,8 @@ int main(int argc, char** argv) {
     Pd.bg_ld = need_ld;
     replay(Pd, "fc1_dgrad S pbg");
   }
-  replay(PConv3Wgrad{grid(576, 64, 64, 64, z3), a2, dz3, s3, B, row_bits(49)}, "conv3_wgrad compacted");
+  // (compacted: rows past the kept ones read at what the table's all-ones entry decodes to)
+  replay(PConv3Wgrad{grid(576, 64, 64, 64, z3), a2, dz3, s3, B, row_bits(49)}, "conv3_wgrad compacted", std::min(PConv3Wgrad::TA::PAST, PConv3Wgrad::TB::PAST));
   replay(PConv3WgradD{grid(576, 64, 64, 64, z3), a2, dz3, s3, B}, "conv3_wgrad dense");
   {
     PConv3DgradP Pd{Grid{(B + PConv3DgradP::BM - 1) / PConv3DgradP::BM, 1, 81}, dz3, w2, a2, dz2, B};
@@ -174,7 +233,7 @@ int main(int argc, char** argv) {
     Pd.bg2_ld = need_ld;
     replay(Pd, "conv3_dgrad px pbg");
   }
-  replay(PConv2Wgrad{grid(512, 64, 64, 64, z2), a1, dz2, s2, B, row_bits(81)}, "conv2_wgrad compacted");
+  replay(PConv2Wgrad{grid(512, 64, 64, 64, z2), a1, dz2, s2, B, row_bits(81)}, "conv2_wgrad compacted", std::min(PConv2Wgrad::TA::PAST, PConv2Wgrad::TB::PAST));
   replay(PConv2WgradD{grid(512, 64, 64, 64, z2), a1, dz2, s2, B}, "conv2_wgrad dense");
   {  // conv1's bias partials always; the step bytes when the forward built row lists
     PConv2DgradP Pd{Grid{(B + 63) / 64, 2, 100}, dz2, w1, a1, dz1, B, buf<float>((size_t)(B + 15) / 16 * 400 * 32)};

@@ -619,7 +619,6 @@ int main(int argc, char** argv) {
     run1("conv2_fwd t32x64 w2x2", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 32, 64, 2, 2>{grid(B * 81, 32, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
     run1("conv2_fwd t128x64 w2x2", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 64, 2, 2>{grid(B * 81, 128, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
     run1("conv2_fwd t128x64 w4x1", PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 128, 64, 4, 1>{grid(B * 81, 128, 64, 64, 1), a1, W1, W1, a2, B * 81}, flop);
-    run1("conv2_wgrad t128x64 w2x2", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16, 128, 64, 2, 2>{grid(512, 128, 64, 64, B / 16), a1, dz2, slab, B}, flop);
     flop = 2.0 * B * 49 * 64 * 576;
     run1("conv3_fwd t64x32 w2x2", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 64, 32, 2, 2>{grid(B * 49, 64, 64, 32, 1), a2, W2, W2, a3, B * 49}, flop);
     run1("conv3_fwd t32x64 w2x2", PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 32, 64, 2, 2>{grid(B * 49, 32, 64, 64, 1), a2, W2, W2, a3, B * 49}, flop);
@@ -648,7 +647,6 @@ int main(int argc, char** argv) {
       run1("conv2_wgrad sc16 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 16>{grid(512, 64, 64, 64, BB / 16), a1, dz2, slab, BB}, f2);
       run1("conv2_wgrad sc8 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 8>{grid(512, 64, 64, 64, BB / 8), a1, dz2, slab, BB}, f2);
       run1("conv2_wgrad sc4 t64x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 4>{grid(512, 64, 64, 64, BB / 4), a1, dz2, slab, BB}, f2);
-      run1("conv2_wgrad sc8 t128x64", PConvWgrad<20, 20, 32, 4, 2, 9, 9, 64, 8, 128, 64, 2, 2>{grid(512, 128, 64, 64, BB / 8), a1, dz2, slab, BB}, f2);
     }
     printf("--- K-split wave groups, B = 1024 and 8192\n");
     for (int BB : {1024, 8192}) {
