@@ -69,8 +69,8 @@ struct Epi4StoreF32 {   // out[m][n] = v (fp32); sq (optional): [tiles] partials
 // sum of squares of 4 values with explicit roundings: a tile's clip_by_norm partial does not depend on where
 // the compiler chooses to contract into FMAs
 __device__ __forceinline__ float sq4(f32x4 v) {
-  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(v[0], v[0]), __fmul_rn(v[1], v[1])), __fmul_rn(v[2], v[2])),
-                   __fmul_rn(v[3], v[3]));
+#pragma clang fp contract(off)   // covers the operators written here (__fadd_rn / __fmul_rn are plain + and * in a header)
+  return ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3];
 }
 
 __device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {

@@ -44,11 +44,14 @@ static int sq_first(int v) {
 // tf.clip_by_norm + ResourceApplyAdam (legacy Keras) for one element
 __device__ __forceinline__ float adam_elem(float g, float scale, float clipnorm, float denom, float alpha, float beta1,
                                            float beta2, float eps, float& m, float& v, float w) {
-  // explicit roundings (no contraction): the same bits wherever this is inlined, and the oracle's order
+  // every operation rounds once (no contraction): the same bits wherever this is inlined, and the oracle's order.  The
+  // pragma covers the operators written here; __fadd_rn / __fmul_rn are plain + and * in a header, outside its reach, and
+  // were fused in this file (built with contraction on): m + d * (1 - beta1), gc * gc - v, v + s * (1 - beta2)
+#pragma clang fp contract(off)
   const float gc = (g * scale * clipnorm) / denom;
-  m = __fadd_rn(m, __fmul_rn(__fsub_rn(gc, m), 1.0f - beta1));
-  v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(gc, gc), v), 1.0f - beta2));
-  return __fsub_rn(w, __fmul_rn(m, alpha) / __fadd_rn(sqrtf(v), eps));
+  m = m + (gc - m) * (1.0f - beta1);
+  v = v + (gc * gc - v) * (1.0f - beta2);
+  return w - (m * alpha) / (sqrtf(v) + eps);
 }
 
 // ------------------------------------------------------------------------------------------
