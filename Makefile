@@ -14,7 +14,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 STRICT := -ffp-contract=off
 LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
-OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/qnet.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
+OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
         $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
@@ -37,7 +37,11 @@ $(OUT)/obj/replay.o: $(SRC)/replay.hip $(HDRS) | $(OUT)/obj
 
 # (bf16 Q-net on the default scheduler since round 5: 789K -> 797K env-steps/s against max-ILP, the slab reduction
 # 11.4 -> 10.0 us)
-$(OUT)/obj/qnet.o: $(SRC)/qnet.hip $(HDRS) | $(OUT)/obj
+$(OUT)/obj/qnet_bf16.o: $(SRC)/qnet_bf16.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the precision-independent model layer (its two staging kernels came out of the bf16 file: the same flags)
+$(OUT)/obj/model.o: $(SRC)/model.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # fp32 Q-net: bit-exact against the oracle, so no contraction anywhere (every fma is an explicit fmaf / MFMA)

@@ -1,5 +1,5 @@
 // bf16 GEMM core of the bf16 fast path (round 5): the dense layer fc1 (3136 <-> 512) forward, backward data and weight
-// gradient (qnet.hip).
+// gradient (qnet_bf16.hip).
 //
 //   C[m][n] = sum_k A(m, k) B(n, k), fp32 accumulation on v_mfma_f32_16x16x32_bf16 (16 cycles per MFMA per SIMD).
 //   Operands in global memory: row-major  [rows][ld], k contiguous   (KM = false)

@@ -310,7 +310,7 @@ static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, cons
   ta.dones = L->d_bdone + o;
   ta.gamma = L->p.gamma;
   ta.y_out = L->d_targets + o;
-  launch_fc2(2, ta, (int)n, s);
+  model_head(tg, 2, ta, (int)n, s);
 }
 
 // Target memo.  With the target net frozen, y = r + gamma * max_a Q_target(s') (or r if done) of a transition is a
@@ -351,7 +351,7 @@ static void ycache_fill(qlx_learner* L, uint64_t i0, uint64_t n, uint32_t chunk)
     ta.dones = L->d_ydone;
     ta.gamma = L->p.gamma;
     ta.y_out = L->d_ytmp;
-    launch_fc2(2, ta, (int)m, s);
+    model_head(tg, 2, ta, (int)m, s);
     hipLaunchKernelGGL(k_slot_put, dim3((m + 255) / 256), dim3(256), 0, s, rv, i0 + c0, m, L->d_ytmp, L->d_ycache);
     QLX_HIP(hipGetLastError());
   }
@@ -374,7 +374,7 @@ static void learner_targets(qlx_learner* L, uint32_t U) {
     qlx_model* on = L->online;
     model_forward_trunk(on, L->d_tab_sn, (int)n, s, false);
     Fc2Args oa = fc2_args(on, (int)n);
-    launch_fc2(0, oa, (int)n, s);
+    model_head(on, 0, oa, (int)n, s);
     q_select = on->w.q;
   }
   // (measured and not kept, round 3: the pass after its first chunk on a second stream beside the update chain - the chain
@@ -417,23 +417,18 @@ static void learner_update(qlx_learner* L, uint32_t u_local) {
                                            ncclFloat, ncclSum, L->comm, L->comm_stream);
       QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
     }
-    // fp32: the dense variables' clip-norm partials of the reduced bucket ride in the conv backward's reduction launch,
-    // which waits for this all-reduce (round 6: dp_single_rank 0.963 -> 0.967 of the plain path), or (QLX_DP_FOLD=0) follow
-    // it on the communicator stream in a launch of their own
-    if (on->f32 && !L->dp_fold) model_norms(on, L->comm_stream, scale);
+    // the dense variables' clip-norm partials of the reduced bucket (a model that keeps them apart: the fp32 net) ride in
+    // the conv backward's reduction launch, which waits for this all-reduce (round 6: dp_single_rank 0.963 -> 0.967 of the
+    // plain path), or (QLX_DP_FOLD=0) follow it on the communicator stream in a launch of their own
+    if (!L->dp_fold) model_norms_dense(on, L->comm_stream, scale);
     QLX_HIP(hipEventRecord(L->ev_reduced, L->comm_stream));
-    if (on->f32 && L->dp_fold) model_backward_conv(on, tab_s, (int)B, s, false, L->ev_reduced, scale);
-    else model_backward_conv(on, tab_s, (int)B, s);
+    model_backward_conv(on, tab_s, (int)B, s, false, L->dp_fold ? L->ev_reduced : nullptr, scale);
     QLX_HIP(hipStreamWaitEvent(s, L->ev_reduced, 0));
     {
       ProfScope ps(&L->prof, "allreduce_conv", s);
       const ncclResult_t r = ncclAllReduce(on->d_grads, on->d_grads, (size_t)off_dense, ncclFloat, ncclSum, L->comm, s);
       QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
     }
-    if (!on->f32) model_norms(on, s, scale);
-    model_adam(on, s, scale);
-    L->update_count += 1;
-    return;
   }
   model_norms(on, s, scale);
   model_adam(on, s, scale);
@@ -468,7 +463,7 @@ static void learner_vector_step(qlx_learner* L, bool train = true) {
     ProfScope ps(&L->prof, "act_forward", s);
     model_forward_trunk(L->online, L->d_obs_table, (int)N, s, false);
     Fc2Args a = fc2_args(L->online, (int)N);
-    launch_fc2(0, a, (int)N, s);
+    model_head(L->online, 0, a, (int)N, s);
   }
   {
     ProfScope ps(&L->prof, "select", s);
@@ -623,9 +618,8 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
       st = qlx_model_create(arch, p->init_seed, device, &L->target);   // same initial weights
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
-      // bf16: the target net's fc1 runs in one pass at every batch size, so the memo (chunks of n_envs) and the
-      // per-batch target pass (U * B samples) produce the same y bit for bit (the fp32 kernels never depend on B)
-      L->target->fc1_single = true;
+      // the memo (chunks of n_envs) and the per-batch target pass (U * B samples) must produce the same y bit for bit
+      model_set_batch_invariant(L->target);
       // everything runs on the learner's stream
       L->env->stream = L->stream; L->env->own_stream = false;
       L->rb->stream = L->stream; L->rb->own_stream = false;

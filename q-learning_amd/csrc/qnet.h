@@ -1,4 +1,5 @@
-// Host-side Q-network object and the launch helpers the learner composes.
+// Host-side Q-network: the precision-independent model object (model.hip), the model_* functions the learner composes,
+// and the two backends they choose between (bf16: qnet_bf16.hip, fp32: qnet32.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,11 +13,6 @@ namespace qlx {
 constexpr int kNumVars = 10;
 constexpr int64_t kVarOffsetDense = 77984;   // flat offset of W3 (conv variables before it, dense ones after)
 constexpr int64_t kNumParams = 1685667;   // sum of the 10 Keras variables (variables.index shapes)
-constexpr int kFc1Split = 4;              // bf16: split-K of the 3136-deep dense layer at training batches (25 / 23 k-steps)
-// conv weight-gradient partial slabs, one region per layer (conv3 and conv2 share a launch)
-constexpr size_t kSlabConv3 = 0, kSlabConv2 = (size_t)3200 * 1024, kSlabConv1 = (size_t)7424 * 1024;
-constexpr size_t kWgradSlabFloats = (size_t)9600 * 1024;
-constexpr size_t kBiasSlabFloats = 256 * 512;
 extern const int kVarSize[kNumVars];
 inline int64_t var_offset(int v) {   // flat offset of variable v in d_params / d_m / d_v / d_grads
   int64_t o = 0;
@@ -25,50 +21,32 @@ inline int64_t var_offset(int v) {   // flat offset of variable v in d_params / 
 }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-struct ModelWs {   // per-batch workspace (activations are bf16, heads fp32)
+constexpr int kF32FwdChunk = 8192;   // samples per fp32 forward pass (bounds the a1..a3 workspace)
+
+// Carves one allocation into 256-byte-aligned buffers.  A layout runs twice: from base 0 for the size, then from the
+// allocation for the pointers.
+struct Arena {
+  uintptr_t base = 0;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* p = reinterpret_cast<T*>(base + off);
+    off = align_up(off + count * sizeof(T), 256);
+    return p;
+  }
+};
+
+struct CommonWs {   // the per-batch buffers both backends use (the head's inputs and outputs are fp32 in either)
   uint8_t* frames = nullptr;          // [B*4][7056] s2d staging for host observations
   const uint8_t** table = nullptr;    // [B][4] frame pointers
-  __bf16 *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;
-  __bf16 *dz1 = nullptr, *dz2 = nullptr, *dz3 = nullptr, *dz4 = nullptr;
   float* q = nullptr;
   float *gs = nullptr, *hs = nullptr, *y = nullptr, *rew = nullptr;
   uint8_t *act = nullptr, *argmax = nullptr, *done = nullptr;
-  float* fc1slab = nullptr;
-  int a4_splits = 0;                  // > 0: a4 still pending as that many split-K fc1 partials in fc1slab
-  float* slab = nullptr;
-  float* bslab = nullptr;
   float* loss = nullptr;
-  // fp32 path (qnet32.hip): activations a1..a3 per forward chunk of `fchunk` samples, a4 for the whole batch; the
-  // gradient buffers (dz, weight-gradient chunk slabs) in their own allocation `fgrad`, sized for fgrad_batch
-  float *fa1 = nullptr, *fa2 = nullptr, *fa3 = nullptr, *fa4 = nullptr;
-  float *fdz1 = nullptr, *fdz2 = nullptr, *fdz3 = nullptr, *fdz4 = nullptr;
-  float *fslab1 = nullptr, *fslab2 = nullptr, *fslab3 = nullptr;
-  float* fpb1 = nullptr;    // conv1 bias partials of the conv2 backward [ceil(B / 16)][400][32]
-  float* fpbg2 = nullptr;   // conv2 background-row dz2 partials of the conv3 backward [ceil(B / 16)][81][64]
-  float* fs2 = nullptr;     // their per-chunk sums [ceil(B / 16)][64] (SideBgSum)
-  float* fpbg3 = nullptr;   // conv3 background-row dz3 partials of the fc1 backward [ceil(B / 16)][49][64]
-  float* fs3 = nullptr;     // their per-chunk sums [ceil(B / 16)][64]
-  float* fpart = nullptr;   // clip_by_norm segment partials
-  // background rows of the conv2 / conv3 forward (qnet32_kernels.h C1Lists): row lists of the forward chunk, the list
-  // counters of two forwards (double-buffered by forward parity), the constant rows relu(b0) / c2 / c3
-  int *frl2 = nullptr, *frl3 = nullptr;
-  unsigned long long* frcnt = nullptr;
-  float* fbgc = nullptr;
-  uint32_t* fsteps = nullptr;   // the forward chunk's conv1 step masks [fchunk][4] (written when the row lists are)
-  uint8_t* fneed = nullptr;     // the same bits as bytes [100][fneed_ld] (step-major)
-  int fneed_ld = 0;
-  uint32_t* frows2 = nullptr;   // the forward chunk's conv2 non-background row bits [fchunk][4]
-  uint8_t* fbg2 = nullptr;      // its conv2 background rows as bytes [81][fneed_ld]
-  uint32_t* frows3 = nullptr;   // the same for conv3 [fchunk][4], [49][fneed_ld]
-  uint8_t* fbg3 = nullptr;
-  int fparity = 0;
-  int frl_cap = 0;   // samples the row lists hold
-  int fchunk = 0;
-  void* fgrad = nullptr;
-  int fgrad_batch = 0;
 };
 
-constexpr int kF32FwdChunk = 8192;   // samples per fp32 forward pass (bounds the a1..a3 workspace)
+struct Bf16Net;   // qnet_bf16.hip
+struct F32Net;    // qnet32.hip
 
 }  // namespace qlx
 
@@ -81,48 +59,19 @@ struct qlx_model {
   float* d_m = nullptr;
   float* d_v = nullptr;
   float* d_grads = nullptr;
-  // bf16 MFMA operand copies ([n][k], k contiguous)
-  __bf16 *wf0 = nullptr, *wf1 = nullptr, *wb1 = nullptr, *wf2 = nullptr, *wb2 = nullptr, *wb3 = nullptr;
+  float* d_norms = nullptr;
   int64_t iterations = 0;
   uint64_t version = 0;   // bumped by model_pack, i.e. on every write of the weights from outside the optimizer
   float lr = 0.00025f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f, clipnorm = 1.0f;
-  int n_ranges = 0;
-  int64_t *d_rbeg = nullptr, *d_rend = nullptr;
-  float* d_partial = nullptr;
-  int* d_var_first = nullptr;
-  // clip_by_norm partials written by the gradient producers themselves (fc1 wgrad tiles, conv slab reduction
-  // blocks, fc2 wgrad blocks): when no all-reduce sits between backward and Adam the k_sumsq pass is skipped
-  float* d_sqf = nullptr;
-  int* d_sqf_first = nullptr;
-  bool norms_fused = false;   // set by model_norms: Adam reads d_sqf / d_sqf_first instead
-  float* d_norms = nullptr;
-  // XCD-aware block -> tile table of the fc1 backward launch (built per batch size, qnet.hip fc1_bwd_map)
-  int* d_fc1bwd_map = nullptr;
-  int fc1bwd_map_B = -1, fc1bwd_grid = 0, fc1bwd_cap = 0;
-  void* ws = nullptr;
+  void* ws = nullptr;   // one allocation: the common buffers (w), then the backend's
   int ws_batch = 0;
   int last_batch = 0;
-  qlx::ModelWs w;
+  qlx::CommonWs w;
   qlx::Profiler* prof = nullptr;   // set by the learner while profiling
-  // conv1 weight gradient as channel-half blocks (k_conv1_wgrad_h); QLX_CONV1_HALVES=0 at create time selects the
-  // one-block-per-chunk k_conv1_wgrad (bit-identical gradients)
-  bool conv1_halves = true;
-  // fp32 sparsity paths, read at create time (a learner built with them off runs the dense forward / weight gradient in
-  // the same process: bench.py value_dense_frames): QLX_F32_BG=0 computes every conv2 / conv3 forward row (no background
-  // rows), QLX_F32_C1_SKIP=0 issues conv1's all-zero frame steps.  Bit-identical results either way.
-  bool f32_bg_rows = true;
-  int f32_c1_skip = 1;
-  // fp32 update schedule (when the caller allows it: no all-reduce between backward and Adam): the dense variables' norm
-  // partials as extra blocks of the weight-gradient reduction launch, then every variable's clip_by_norm + Adam in one
-  // launch (k_update32) - the update's tail is two launches.  Set by the backward, consumed by model_norms / model_adam.
-  bool f32_update_scheduled = false;
-  // data parallel (an all-reduce between the backward and the update): model_norms wrote the dense variables' norm
-  // partials of the reduced gradient x f32_partials_scale; model_adam then runs the same k_update32 tail
-  bool f32_dense_partials = false;
-  float f32_partials_scale = 1.0f;
-  // bf16 forward: fc1 as one pass with the fused epilogue at every batch size (no batch-size-dependent split-K), so a
-  // sample's result does not depend on the batch it is evaluated in (the learner's target net)
-  bool fc1_single = false;
+  // the backend's own state (operand copies, activations, norm partials, update-tail flags): exactly one is set, and
+  // only that backend's file sees inside it
+  qlx::Bf16Net* bf16 = nullptr;
+  qlx::F32Net* fp32 = nullptr;
 };
 
 namespace qlx {
@@ -154,14 +103,19 @@ struct Fc2Args {
   float* td_abs;           // training head (optional): |q_a - y| out
   float* dz4_out;          // fp32 training head (optional): the dense-3 backward dz4 [B][512], fused
 };
-// fc2 kernel arguments for the model's last forward; consumes pending fc1 partials (the fc2 launch that
-// follows materialises a4)
-Fc2Args fc2_args(qlx_model* m, int B);
-void launch_fc2(int mode, const Fc2Args& a, int B, hipStream_t s);
+
+// ---- the model layer (model.hip): each call is the backend's of the same name ----
 void model_workspace(qlx_model* m, int B);
 void model_pack(qlx_model* m);
+// a sample's result must not depend on the batch it is evaluated in (the learner's target net, whose memo and per-batch
+// pass evaluate the same transition at different batch sizes)
+void model_set_batch_invariant(qlx_model* m);
 // store_acts = false skips writing a1/a2 (only a3 is needed when no backward pass follows)
 void model_forward_trunk(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool store_acts = true);
+// head arguments for the model's last forward (bf16: consumes pending fc1 partials, the head launch that follows
+// materialises a4), and the head launch: mode 0 q, 1 + argmax, 2 Bellman target
+Fc2Args fc2_args(qlx_model* m, int B);
+void model_head(qlx_model* m, int mode, const Fc2Args& a, int B, hipStream_t s);
 // Huber head + backward after model_forward_trunk: loss -> *loss_dev, raw gradients -> m->d_grads
 // weights (optional): per-sample loss weights; td_abs (optional): |q_a - y| per sample out.
 // = model_backward_dense (head, fc1: the dense gradients, 95 % of the bytes, are final after it) followed by
@@ -172,25 +126,80 @@ void model_backward(qlx_model* m, const uint8_t* const* table, int B, const uint
                     hipStream_t s, const float* weights = nullptr, float* td_abs = nullptr, bool fuse_update = false);
 void model_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                           const float* weights = nullptr, float* td_abs = nullptr);
-// dense_ready (fp32, data parallel): the dense bucket's all-reduce event; the reduction launch then waits for it and computes
-// the dense variables' clip-norm partials of the reduced gradient x dense_scale as its extra blocks (no f32_norms launch)
+// dense_ready (data parallel): the dense bucket's all-reduce event; the fp32 reduction launch then waits for it and computes
+// the dense variables' clip-norm partials of the reduced gradient x dense_scale as its extra blocks (bf16 ignores both)
 void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update = false,
                          hipEvent_t dense_ready = nullptr, float dense_scale = 1.0f);
-// per-variable norm partials for Adam: with scale == 1 (no all-reduce since the backward) the producers'
-// fused partials are used as they are; otherwise per-range sums of squares of the scaled gradients
+// The update tail.  Each backend keeps clip-norm partials its backward produced and knows whether they still belong to
+// d_grads; a caller that writes d_grads itself says so with model_gradient_replaced (an all-reduce in place needs no
+// call: the scale it passes tells).  model_norms_dense: the dense variables' partials of d_grads x scale, which may run as
+// soon as the dense bucket is final (fp32; bf16 has no such split).  model_norms: whatever is still missing before
+// model_adam at that scale.
+void model_gradient_replaced(qlx_model* m);
+void model_norms_dense(qlx_model* m, hipStream_t s, float scale);
 void model_norms(qlx_model* m, hipStream_t s, float scale);
 void model_adam(qlx_model* m, hipStream_t s, float scale);
 
-// fp32 path (qnet32.hip), dispatched to by the model_* functions when m->f32
+// (Re)allocates m->ws for B samples: the common buffers, then whatever `layout` takes from the arena for the backend
+void ws_common(qlx_model* m, Arena& a, int B);
+template <class Layout>
+void ws_alloc(qlx_model* m, int B, Layout&& layout) {
+  QLX_HIP(hipStreamSynchronize(m->stream));
+  if (m->ws) (void)hipFree(m->ws);
+  m->ws = nullptr;
+  m->ws_batch = 0;
+  Arena size;
+  ws_common(m, size, B);
+  layout(size);
+  QLX_HIP(hipMalloc(&m->ws, size.off));
+  Arena a{(uintptr_t)m->ws};
+  ws_common(m, a, B);
+  layout(a);
+  m->ws_batch = B;
+}
+// head arguments both backends fill alike
+inline Fc2Args fc2_common(qlx_model* m, int B) {
+  Fc2Args a{};
+  a.w4 = m->d_params + var_offset(8);
+  a.b4 = m->d_params + var_offset(9);
+  a.b3 = m->d_params + var_offset(7);
+  a.B = B;
+  a.q = m->w.q;
+  a.zstride = (size_t)B * 512;
+  return a;
+}
+
+// ---- the backends: bf16_* (qnet_bf16.hip) and f32_* (qnet32.hip), chosen between by the model_* functions ----
+void bf16_create(qlx_model* m);    // the backend's device state (m->bf16 / m->fp32), nothing of the common model
+void bf16_destroy(qlx_model* m);
+void bf16_workspace(qlx_model* m, int B);   // B > m->ws_batch
+void bf16_pack(qlx_model* m);
+void bf16_set_batch_invariant(qlx_model* m);
+void bf16_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool store_acts);
+Fc2Args bf16_fc2_args(qlx_model* m, int B);
+void bf16_head(int mode, const Fc2Args& a, int B, hipStream_t s);
+void bf16_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
+                         const float* weights, float* td_abs);
+void bf16_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s);
+void bf16_gradient_replaced(qlx_model* m);
+void bf16_norms(qlx_model* m, hipStream_t s, float scale);
+void bf16_adam(qlx_model* m, hipStream_t s, float scale);
+void bf16_last_activation(qlx_model* m, int layer, float* out);
+
+void f32_create(qlx_model* m);
+void f32_destroy(qlx_model* m);
 void f32_workspace(qlx_model* m, int B);
 void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s);
+Fc2Args f32_fc2_args(qlx_model* m, int B);
 void f32_head(int mode, const Fc2Args& a, int B, hipStream_t s);   // mode 3 = training head
 void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                         const float* weights, float* td_abs);
 void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update,
                        hipEvent_t dense_ready = nullptr, float dense_scale = 1.0f);
+void f32_gradient_replaced(qlx_model* m);
 void f32_norms(qlx_model* m, hipStream_t s, float scale);
 void f32_adam(qlx_model* m, hipStream_t s, float scale);
+void f32_last_activation(qlx_model* m, int layer, float* out);
 // fractions of a batch's fp32 conv work the exact skips leave out (qnet32.hip k_frame_sparsity; synchronises s):
 // out = {conv1 forward zero steps, conv1 weight-gradient zero steps, conv2 background rows, conv3 background rows}
 // d_cnt: 4 device counters, h_cnt: their pinned host copy (both the caller's, allocated once)

@@ -24,6 +24,51 @@ namespace qlx {
 
 using namespace q32;
 
+struct F32Net {
+  // sparsity paths, read at create time (a learner built with them off runs the dense forward / weight gradient in the
+  // same process: bench.py value_dense_frames): QLX_F32_BG=0 computes every conv2 / conv3 forward row (no background
+  // rows), QLX_F32_C1_SKIP=0 issues conv1's all-zero frame steps.  Bit-identical results either way.
+  bool bg_rows = true;
+  int c1_skip = 1;
+  // Update-tail protocol: which clip-norm partials in fpart belong to the gradient now in d_grads, and at what scale.
+  // update_scheduled (the caller allowed it: no all-reduce between backward and Adam): the dense variables' partials rode
+  // in the weight-gradient reduction launch, every variable's clip_by_norm + Adam follows in one launch (k_update32).
+  // dense_partials (data parallel): the reduction launch or f32_norms wrote the dense partials of the reduced gradient x
+  // partials_scale.  Set by f32_backward_conv / f32_norms, consumed by f32_adam, dropped by f32_gradient_replaced.
+  bool update_scheduled = false;
+  bool dense_partials = false;
+  float partials_scale = 1.0f;
+  // per-batch workspace (in the model's allocation, after the common buffers): activations a1..a3 per forward chunk of
+  // `fchunk` samples, a4 for the whole batch
+  float *fa1 = nullptr, *fa2 = nullptr, *fa3 = nullptr, *fa4 = nullptr;
+  float* fpart = nullptr;   // clip_by_norm segment partials
+  // background rows of the conv2 / conv3 forward (qnet32_kernels.h C1Lists): row lists of the forward chunk, the list
+  // counters of two forwards (double-buffered by forward parity), the constant rows relu(b0) / c2 / c3
+  int *frl2 = nullptr, *frl3 = nullptr;
+  unsigned long long* frcnt = nullptr;
+  float* fbgc = nullptr;
+  uint32_t* fsteps = nullptr;   // the forward chunk's conv1 step masks [fchunk][4] (written when the row lists are)
+  uint8_t* fneed = nullptr;     // the same bits as bytes [100][fneed_ld] (step-major)
+  int fneed_ld = 0;
+  uint32_t* frows2 = nullptr;   // the forward chunk's conv2 non-background row bits [fchunk][4]
+  uint8_t* fbg2 = nullptr;      // its conv2 background rows as bytes [81][fneed_ld]
+  uint32_t* frows3 = nullptr;   // the same for conv3 [fchunk][4], [49][fneed_ld]
+  uint8_t* fbg3 = nullptr;
+  int fparity = 0;
+  int frl_cap = 0;   // samples the row lists hold
+  int fchunk = 0;
+  // the gradient buffers (dz, weight-gradient chunk slabs) in their own allocation `fgrad`, sized for fgrad_batch
+  void* fgrad = nullptr;
+  int fgrad_batch = 0;
+  float *fdz1 = nullptr, *fdz2 = nullptr, *fdz3 = nullptr, *fdz4 = nullptr;
+  float *fslab1 = nullptr, *fslab2 = nullptr, *fslab3 = nullptr;
+  float* fpb1 = nullptr;    // conv1 bias partials of the conv2 backward [ceil(B / 16)][400][32]
+  float* fpbg2 = nullptr;   // conv2 background-row dz2 partials of the conv3 backward [ceil(B / 16)][81][64]
+  float* fs2 = nullptr;     // their per-chunk sums [ceil(B / 16)][64] (SideBgSum)
+  float* fpbg3 = nullptr;   // conv3 background-row dz3 partials of the fc1 backward [ceil(B / 16)][49][64]
+  float* fs3 = nullptr;     // their per-chunk sums [ceil(B / 16)][64]
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // dense 512 -> 3 head: q[b][n] = (fmaf chain over k ascending of a4[b][k] W4[k][n]) + b4[n], as the MFMA product
 // W4^T a4^T (one wave per 16 samples: A = W4^T rows n < 3, B = a4 columns; each output is the k-ordered chain), the
@@ -258,7 +303,7 @@ __host__ __device__ inline int wred_waves(int nz) {
   while (w < ng && w < 16) w *= 2;
   return w;
 }
-// Blocks [nred, ..) of the launch (update schedule 2, qnet.h): clip-norm segment partials of segments seg0 .. seg0 + nseg
+// Blocks [nred, ..) of the launch (the update-tail protocol, F32Net): clip-norm segment partials of segments seg0 .. seg0 + nseg
 // - the dense variables', final since the fc1 backward - four 256-thread groups per block, one segment's
 // arithmetic each (norm32_lane, then ((w0 + w1) + w2) + w3).
 __global__ __launch_bounds__(1024) void k_wreduce32(WRed R, NormArgs N, int nred, int seg0, int nseg) {
@@ -543,7 +588,7 @@ __device__ __forceinline__ void conv_adam_block(const Adam32Args& A, const NormA
   }
 }
 
-// The scheduled update (qnet.h f32_update_scheduled): clip_by_norm + Adam of every variable in one launch after the
+// The scheduled update (F32Net::update_scheduled): clip_by_norm + Adam of every variable in one launch after the
 // weight-gradient reduction -
 // blocks [0, nconv) the conv variables (conv_adam_block: norm from the gradient itself), the rest the dense variables
 // (their segment partials came from the reduction launch; AdamDense arithmetic).  No block depends on another.
@@ -580,93 +625,74 @@ static int c1_blocks(int n) { return std::max(std::min(n, 2 * num_cus()), (n + k
 static bool c1_one(int n) { return n <= 2048; }
 static int c1_grid(int n) { return c1_one(n) ? n : c1_blocks(n); }
 
+void f32_create(qlx_model* m) {
+  F32Net& w = *(m->fp32 = new F32Net);
+  const char* bg = std::getenv("QLX_F32_BG");
+  w.bg_rows = !(bg && bg[0] == '0');
+  const char* sk = std::getenv("QLX_F32_C1_SKIP");
+  w.c1_skip = (sk && sk[0] == '0') ? 0 : 1;
+}
+
+void f32_destroy(qlx_model* m) {
+  if (!m->fp32) return;
+  (void)hipFree(m->fp32->fgrad);
+  delete m->fp32;
+  m->fp32 = nullptr;
+}
+
 void f32_workspace(qlx_model* m, int B) {
-  if (B <= m->ws_batch) return;
-  QLX_HIP(hipStreamSynchronize(m->stream));
-  if (m->ws) (void)hipFree(m->ws);
-  m->ws = nullptr;
-  ModelWs& w = m->w;
+  F32Net& w = *m->fp32;
   const int C = std::min(B, kF32FwdChunk);   // conv activations are held per forward chunk
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_frames = take((size_t)B * 4 * kFramePix);
-  const size_t o_table = take((size_t)B * 4 * sizeof(void*));
-  const size_t o_a1 = take((size_t)C * 12800 * 4), o_a2 = take((size_t)C * 5184 * 4), o_a3 = take((size_t)C * 3136 * 4);
-  const size_t o_a4 = take((size_t)B * 512 * 4), o_q = take((size_t)B * 3 * 4);
-  const size_t o_gs = take((size_t)B * 4), o_hs = take((size_t)B * 4), o_y = take((size_t)B * 4);
-  const size_t o_act = take((size_t)B), o_argmax = take((size_t)B), o_rew = take((size_t)B * 4), o_done = take((size_t)B);
   int nseg = 0;
   for (int v = 0; v < kNumVars; ++v) nseg += segs_of(v);
-  const size_t o_part = take((size_t)nseg * 4);
-  const size_t o_loss = take(64);
   // row lists: kListSlots regions of ceil(G / kListSlots) blocks x ceil(n / G) samples each (G = c1_blocks(n) for a chunk of
   // n <= C samples): kListSlots x that <= (G + kListSlots)(n / G + 1) = n + G + kListSlots n / G + kListSlots, with
   // G >= min(n, 2 CUs) and G <= max(2 CUs, C / kC1MaxIt + 1) (one sample per block, c1_one: G = n, n + kListSlots)
   const int frl_cap = C + kListSlots * (C / std::max(1, std::min(C, 2 * num_cus())) + 1) +
                       std::max(2 * num_cus(), C / kC1MaxIt + 1) + kListSlots;
-  const size_t o_rl2 = take((size_t)frl_cap * 81 * 4), o_rl3 = take((size_t)frl_cap * 49 * 4);
-  const size_t o_rcnt = take(2 * 2 * kListSlots * kCntStride * 8), o_bgc = take(160 * 4), o_steps = take((size_t)C * 4 * 4);
   const int need_ld = (C + 63) / 64 * 64;   // (the conv2 backward-data tiles read 64-row blocks of it)
-  const size_t o_need = take((size_t)100 * need_ld);
-  const size_t o_rows2 = take((size_t)C * 4 * 4), o_bg2 = take((size_t)81 * need_ld);
-  const size_t o_rows3 = take((size_t)C * 4 * 4), o_bg3 = take((size_t)49 * need_ld);
-  QLX_HIP(hipMalloc(&m->ws, off));
-  char* base = (char*)m->ws;
-  w.frames = (uint8_t*)(base + o_frames);
-  w.table = (const uint8_t**)(base + o_table);
-  w.fa1 = (float*)(base + o_a1); w.fa2 = (float*)(base + o_a2); w.fa3 = (float*)(base + o_a3); w.fa4 = (float*)(base + o_a4);
-  w.q = (float*)(base + o_q);
-  w.gs = (float*)(base + o_gs); w.hs = (float*)(base + o_hs); w.y = (float*)(base + o_y);
-  w.act = (uint8_t*)(base + o_act); w.argmax = (uint8_t*)(base + o_argmax); w.rew = (float*)(base + o_rew);
-  w.done = (uint8_t*)(base + o_done);
-  w.fpart = (float*)(base + o_part);
-  w.loss = (float*)(base + o_loss);
-  w.frl2 = (int*)(base + o_rl2); w.frl3 = (int*)(base + o_rl3);
-  w.frcnt = (unsigned long long*)(base + o_rcnt);
-  w.fbgc = (float*)(base + o_bgc);
-  w.fsteps = (uint32_t*)(base + o_steps);
-  w.fneed = (uint8_t*)(base + o_need);
-  w.fneed_ld = need_ld;
-  w.frows2 = (uint32_t*)(base + o_rows2);
-  w.fbg2 = (uint8_t*)(base + o_bg2);
-  w.frows3 = (uint32_t*)(base + o_rows3);
-  w.fbg3 = (uint8_t*)(base + o_bg3);
+  ws_alloc(m, B, [&](Arena& a) {
+    w.fa1 = a.take<float>((size_t)C * 12800); w.fa2 = a.take<float>((size_t)C * 5184); w.fa3 = a.take<float>((size_t)C * 3136);
+    w.fa4 = a.take<float>((size_t)B * 512);
+    w.fpart = a.take<float>(nseg);
+    w.frl2 = a.take<int>((size_t)frl_cap * 81); w.frl3 = a.take<int>((size_t)frl_cap * 49);
+    w.frcnt = a.take<unsigned long long>(2 * 2 * kListSlots * kCntStride);
+    w.fbgc = a.take<float>(160);
+    w.fsteps = a.take<uint32_t>((size_t)C * 4);
+    w.fneed = a.take<uint8_t>((size_t)100 * need_ld);
+    w.frows2 = a.take<uint32_t>((size_t)C * 4); w.fbg2 = a.take<uint8_t>((size_t)81 * need_ld);
+    w.frows3 = a.take<uint32_t>((size_t)C * 4); w.fbg3 = a.take<uint8_t>((size_t)49 * need_ld);
+  });
   QLX_HIP(hipMemset(w.frcnt, 0, 2 * 2 * kListSlots * kCntStride * 8));
+  w.fneed_ld = need_ld;
   w.frl_cap = frl_cap;
   w.fparity = 0;
   w.fchunk = C;
-  m->ws_batch = B;
 }
 
 // gradient workspace (dz buffers, weight-gradient slabs) for training batches up to B (<= the forward chunk)
 static void f32_grad_workspace(qlx_model* m, int B) {
-  ModelWs& w = m->w;
+  F32Net& w = *m->fp32;
   if (B <= w.fgrad_batch) return;
   QLX_HIP(hipStreamSynchronize(m->stream));
   if (w.fgrad) (void)hipFree(w.fgrad);
   w.fgrad = nullptr;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_dz1 = take((size_t)B * 12800 * 4), o_dz2 = take((size_t)B * 5184 * 4), o_dz3 = take((size_t)B * 3136 * 4);
-  const size_t o_dz4 = take((size_t)B * 512 * 4);
-  const size_t o_s1 = take((size_t)((B + kSC1 - 1) / kSC1) * 257 * 32 * 4);
-  const size_t o_s2 = take((size_t)((B + kSC2 - 1) / kSC2) * 513 * 64 * 4);
-  const size_t o_s3 = take((size_t)((B + kSC3 - 1) / kSC3) * 577 * 64 * 4);
-  const size_t o_pb = take((size_t)((B + 15) / 16) * 400 * 32 * 4);
-  const size_t o_pbg = take((size_t)((B + 15) / 16) * 81 * 64 * 4), o_bgs = take((size_t)((B + 15) / 16) * 64 * 4);
-  const size_t o_pbg3 = take((size_t)((B + 15) / 16) * 49 * 64 * 4), o_bgs3 = take((size_t)((B + 15) / 16) * 64 * 4);
-  void* p = nullptr;
-  QLX_HIP(hipMalloc(&p, off));
-  w.fgrad = p;
-  char* base = (char*)p;
-  w.fdz1 = (float*)(base + o_dz1); w.fdz2 = (float*)(base + o_dz2); w.fdz3 = (float*)(base + o_dz3);
-  w.fdz4 = (float*)(base + o_dz4);
-  w.fslab1 = (float*)(base + o_s1); w.fslab2 = (float*)(base + o_s2); w.fslab3 = (float*)(base + o_s3);
-  w.fpb1 = (float*)(base + o_pb);
-  w.fpbg2 = (float*)(base + o_pbg);
-  w.fs2 = (float*)(base + o_bgs);
-  w.fpbg3 = (float*)(base + o_pbg3);
-  w.fs3 = (float*)(base + o_bgs3);
+  w.fgrad_batch = 0;
+  auto layout = [&](Arena& a) {
+    w.fdz1 = a.take<float>((size_t)B * 12800); w.fdz2 = a.take<float>((size_t)B * 5184); w.fdz3 = a.take<float>((size_t)B * 3136);
+    w.fdz4 = a.take<float>((size_t)B * 512);
+    w.fslab1 = a.take<float>((size_t)((B + kSC1 - 1) / kSC1) * 257 * 32);
+    w.fslab2 = a.take<float>((size_t)((B + kSC2 - 1) / kSC2) * 513 * 64);
+    w.fslab3 = a.take<float>((size_t)((B + kSC3 - 1) / kSC3) * 577 * 64);
+    w.fpb1 = a.take<float>((size_t)((B + 15) / 16) * 400 * 32);
+    w.fpbg2 = a.take<float>((size_t)((B + 15) / 16) * 81 * 64); w.fs2 = a.take<float>((size_t)((B + 15) / 16) * 64);
+    w.fpbg3 = a.take<float>((size_t)((B + 15) / 16) * 49 * 64); w.fs3 = a.take<float>((size_t)((B + 15) / 16) * 64);
+  };
+  Arena size;
+  layout(size);
+  QLX_HIP(hipMalloc(&w.fgrad, size.off));
+  Arena a{(uintptr_t)w.fgrad};
+  layout(a);
   w.fgrad_batch = B;
 }
 
@@ -712,8 +738,8 @@ static int num_cus() {
 static Grid grid(int M, int BM, int N, int BN, int nz) { return Grid{(M + BM - 1) / BM, (N + BN - 1) / BN, nz}; }
 
 // conv1 forward / weight gradient: MFMA steps whose frame operands are all 0 are not issued (exact, see k_conv1_fwd32);
-// a model created under QLX_F32_C1_SKIP=0 issues every step (qlx_model::f32_c1_skip)
-static int c1_skip(const qlx_model* m) { return m->f32_c1_skip; }
+// a model created under QLX_F32_C1_SKIP=0 issues every step (F32Net::c1_skip)
+static int c1_skip(const qlx_model* m) { return m->fp32->c1_skip; }
 
 // training-batch conv2 / conv3 forward over M rows on a balanced grid (PConv2FwdR / PConv3FwdR): `whole` 64 x 64 tiles,
 // a multiple of the CU count, plus the remaining rows as 16 x 64 tiles; 0 when the shape has no such split (fewer whole
@@ -738,8 +764,8 @@ static void launch_list(qlx_model* m, const P& p, const S& side, const char* sco
 }
 
 // background rows (see C1Lists in qnet32_kernels.h): on by default; a model created under QLX_F32_BG=0 computes every
-// conv2 / conv3 row (qlx_model::f32_bg_rows)
-static bool bg_rows(const qlx_model* m) { return m->f32_bg_rows; }
+// conv2 / conv3 row (F32Net::bg_rows)
+static bool bg_rows(const qlx_model* m) { return m->fp32->bg_rows; }
 
 // the conv1 step masks of the training forward (written with its row lists) select the dz1 rows the conv2 backward
 // stores and the conv1 weight gradient fetches; without zero-step skipping every row is multiplied, so every row
@@ -760,7 +786,7 @@ static void conv_fwd(qlx_model* m, int M, const float* in, const float* wt, cons
 // forward over B samples in chunks of the workspace's forward chunk: a1..a3 hold the last chunk (the whole batch when
 // B <= chunk, as training needs), a4 all B samples
 void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s) {
-  ModelWs& w = m->w;
+  F32Net& w = *m->fp32;
   QLX_CHECK(m->ws_batch >= B, QLX_E_STATE, "f32 forward: workspace too small");
   m->last_batch = B;
   const float* p = m->d_params;
@@ -864,21 +890,28 @@ void f32_head(int mode, const Fc2Args& a, int B, hipStream_t s) {
   debug_sync(s, "k_head32");
 }
 
+Fc2Args f32_fc2_args(qlx_model* m, int B) {
+  Fc2Args a = fc2_common(m, B);
+  a.a4f = m->fp32->fa4;
+  return a;
+}
+
 void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                         const float* weights, float* td_abs) {
-  QLX_CHECK(B <= m->w.fchunk && B == m->last_batch, QLX_E_STATE, "f32 backward: batch must follow its forward");
-  m->f32_dense_partials = false;   // partials of an earlier gradient (an update that threw before its Adam)
+  F32Net& w = *m->fp32;
+  QLX_CHECK(B <= w.fchunk && B == m->last_batch, QLX_E_STATE, "f32 backward: batch must follow its forward");
+  w.dense_partials = false;   // partials of an earlier gradient (an update that threw before its Adam)
   f32_grad_workspace(m, B);
-  ModelWs& w = m->w;
   float* G = m->d_grads;
   const float* p = m->d_params;
+  float *gs = m->w.gs, *hs = m->w.hs;
   {
     ProfScope ps(m->prof, "f32_head", s);
-    Fc2Args a = fc2_args(m, B);
+    Fc2Args a = f32_fc2_args(m, B);
     a.actions = actions;
     a.y = y;
-    a.gsample = w.gs;
-    a.hsample = w.hs;
+    a.gsample = gs;
+    a.hsample = hs;
     a.weights = weights;
     a.td_abs = td_abs;
     a.dz4_out = w.fdz4;
@@ -892,7 +925,7 @@ void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float
       Pd.bg = w.fbg3;
       Pd.bg_ld = w.fneed_ld;
     }
-    SideFc2 S{w.fa4, actions, w.gs, w.hs, B, G + var_offset(8), G + var_offset(9), loss_dev};
+    SideFc2 S{w.fa4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev};
     launch_pair(m, Pw, Pd, S, "f32_fc1_bwd", 2.0 * 2.0 * B * 512 * 3136, s);   // (3 blocks per CU: 72.8 vs 61.8 us, w23)
   }
 }
@@ -914,7 +947,7 @@ static NormArgs norm_args(qlx_model* m, float scale) {
   NormArgs A;
   A.g = m->d_grads;
   A.scale = scale;
-  A.partial = m->w.fpart;
+  A.partial = m->fp32->fpart;
   seg_tables(A.seg_first, A.off);
   return A;
 }
@@ -924,7 +957,7 @@ static Adam32Args adam_args(qlx_model* m, float scale) {
   const float tf = (float)(m->iterations + 1);
   const float b1p = std::pow(m->beta1, tf), b2p = std::pow(m->beta2, tf);
   Adam32Args a;
-  a.w = m->d_params; a.m = m->d_m; a.v = m->d_v; a.g = m->d_grads; a.partial = m->w.fpart; a.norms = m->d_norms;
+  a.w = m->d_params; a.m = m->d_m; a.v = m->d_v; a.g = m->d_grads; a.partial = m->fp32->fpart; a.norms = m->d_norms;
   seg_tables(a.seg_first, a.off);
   a.scale = scale;
   a.alpha = m->lr * std::sqrt(1.0f - b2p) / (1.0f - b1p);
@@ -934,8 +967,8 @@ static Adam32Args adam_args(qlx_model* m, float scale) {
 
 void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update, hipEvent_t dense_ready,
                        float dense_scale) {
-  ModelWs& w = m->w;
-  m->f32_update_scheduled = fuse_update;
+  F32Net& w = *m->fp32;
+  w.update_scheduled = fuse_update;
   QLX_CHECK(!(fuse_update && dense_ready), QLX_E_STATE, "dense partials: the scheduled update or the data-parallel form");
   const NormArgs N = norm_args(m, dense_ready ? dense_scale : 1.0f);
   const float* p = m->d_params;
@@ -1008,13 +1041,13 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
     // backward ends) - the launch waits for it, so the update tail is the plain path's two launches (+ the conv all-reduce)
     const bool dp_dense = dense_ready != nullptr;
     if (dp_dense) QLX_HIP(hipStreamWaitEvent(s, dense_ready, 0));
-    const int dseg = m->f32_update_scheduled || dp_dense ? N.seg_first[kNumVars] - N.seg_first[6] : 0;
+    const int dseg = w.update_scheduled || dp_dense ? N.seg_first[kNumVars] - N.seg_first[6] : 0;
     hipLaunchKernelGGL(k_wreduce32, dim3(nred + (dseg + 3) / 4), dim3(1024), 0, s, R, N, nred, N.seg_first[6], dseg);
     QLX_HIP(hipGetLastError());
     debug_sync(s, "k_wreduce32");
     if (dp_dense) {
-      m->f32_dense_partials = true;
-      m->f32_partials_scale = dense_scale;
+      w.dense_partials = true;
+      w.partials_scale = dense_scale;
     }
   }
 }
@@ -1023,9 +1056,12 @@ void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStre
 // partials): the dense variables' clip-norm segment partials of the reduced gradient x scale, as k_wreduce32's extra
 // blocks compute them at world 1 (the same blocks, no chunk sums).  Only the dense gradient is read, so a caller may run it
 // as soon as the dense bucket is reduced (learner.hip: on the communicator stream, beside the conv backward).
+void f32_gradient_replaced(qlx_model* m) { m->fp32->update_scheduled = m->fp32->dense_partials = false; }
+
 void f32_norms(qlx_model* m, hipStream_t s, float scale) {
-  if (m->f32_update_scheduled) return;   // the backward scheduled them (f32_backward_conv)
-  if (m->f32_dense_partials && m->f32_partials_scale == scale) return;   // the data-parallel reduction launch computed them
+  F32Net& w = *m->fp32;
+  if (w.update_scheduled) return;   // the backward scheduled them (f32_backward_conv)
+  if (w.dense_partials && w.partials_scale == scale) return;   // the data-parallel reduction launch computed them
   ProfScope ps(m->prof, "f32_norms", s, 4.0 * (kNumParams - kVarOffsetDense));
   const NormArgs N = norm_args(m, scale);
   const int dseg = N.seg_first[kNumVars] - N.seg_first[6];
@@ -1033,8 +1069,8 @@ void f32_norms(qlx_model* m, hipStream_t s, float scale) {
   hipLaunchKernelGGL(k_wreduce32, dim3((dseg + 3) / 4), dim3(1024), 0, s, R, N, 0, N.seg_first[6], dseg);
   QLX_HIP(hipGetLastError());
   debug_sync(s, "k_wreduce32 (dense norm partials)");
-  m->f32_dense_partials = true;
-  m->f32_partials_scale = scale;
+  w.dense_partials = true;
+  w.partials_scale = scale;
 }
 
 // clip_by_norm + Adam of every variable in one launch (k_update32): the conv blocks finish their variable's norm from the
@@ -1043,18 +1079,29 @@ void f32_norms(qlx_model* m, hipStream_t s, float scale) {
 constexpr int kDenseAdamBlocks = (int)((kNumParams - kVarOffsetDense) / 4 / 2048 + 1);   // 2 float4 groups per thread
 
 void f32_adam(qlx_model* m, hipStream_t s, float scale) {
+  F32Net& w = *m->fp32;
   const int64_t t = m->iterations + 1;
   const Adam32Args a = adam_args(m, scale);
-  QLX_CHECK(m->f32_update_scheduled ? scale == 1.0f : (m->f32_dense_partials && scale == m->f32_partials_scale), QLX_E_STATE,
+  QLX_CHECK(w.update_scheduled ? scale == 1.0f : (w.dense_partials && scale == w.partials_scale), QLX_E_STATE,
             "fp32 update without the dense norm partials of this gradient scale (model_norms first)");
   ProfScope ps(m->prof, "f32_adam", s, 28.0 * kNumParams);
   const int nconv = conv_adam_blocks(), ndense = kDenseAdamBlocks;
   hipLaunchKernelGGL(k_update32, dim3(nconv + ndense), dim3(1024), 0, s, a, norm_args(m, scale), nconv, ndense);
   QLX_HIP(hipGetLastError());
   debug_sync(s, "k_update32");
-  m->f32_update_scheduled = false;
-  m->f32_dense_partials = false;
+  w.update_scheduled = false;
+  w.dense_partials = false;
   m->iterations = t;
+}
+
+// a1..a3 of the last forward chunk (the whole batch up to kF32FwdChunk samples), a4 of all
+void f32_last_activation(qlx_model* m, int layer, float* out) {
+  const F32Net& w = *m->fp32;
+  QLX_CHECK(layer == 4 || m->last_batch <= w.fchunk, QLX_E_STATE, "activations of a chunked forward");
+  QLX_HIP(hipStreamSynchronize(m->stream));
+  const size_t per[5] = {0, 12800, 5184, 3136, 512};
+  const float* src = layer == 1 ? w.fa1 : layer == 2 ? w.fa2 : layer == 3 ? w.fa3 : w.fa4;
+  QLX_HIP(hipMemcpy(out, src, per[layer] * (size_t)m->last_batch * 4, hipMemcpyDeviceToHost));
 }
 
 // ---- frame sparsity of a batch (diagnostic, bench.py): how much of the fp32 conv work the exact skips leave out ----

@@ -1,21 +1,18 @@
-// DeepQLearningModel on MI355X: Nature-DQN forward / backward / Huber / clip_by_norm / Adam.
+// bf16 DeepQLearningModel backend: Nature-DQN forward / backward / Huber / clip_by_norm / Adam with bf16 MFMA operands
+// (fp32 master weights and accumulation), the bf16_* functions of qnet.h.
 //
-// Reference (restated): create_ql_model_breakout_84x84x4_3_32.py:20-33 (graph), :36-55 (predict_action,
-// batch_predict_max_future_reward), :63-82 (train_model; intended q_a = Q(s)[a] semantics of
-// create_ql_model_ballgame_3x3x4_5_512.py:71-78), legacy keras Adam(lr 2.5e-4, clipnorm 1.0) =
+// Reference (restated): create_ql_model_breakout_84x84x4_3_32.py:20-33 (graph), :63-82 (train_model; intended
+// q_a = Q(s)[a] semantics of create_ql_model_ballgame_3x3x4_5_512.py:71-78), legacy keras Adam(lr 2.5e-4, clipnorm 1.0) =
 // tf.clip_by_norm per variable + ResourceApplyAdam (saved_model.pb op names), Huber(delta=1) mean.
-// The reference runs this inside libtensorflow behind Session::run (q_learning_model.rs:107-189).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "objects.h"
 #include "qnet.h"
 #include "qnet_kernels.h"
 #include "trunk_kernels.h"
@@ -26,10 +23,45 @@ namespace qlx {
 
 using namespace qn;
 
-extern const int kVarSize[kNumVars];
-const int kVarSize[kNumVars] = {8 * 8 * 4 * 32, 32, 4 * 4 * 32 * 64, 64, 3 * 3 * 64 * 64, 64, 3136 * 512, 512, 512 * 3, 3};
+constexpr int kFc1Split = 4;   // split-K of the 3136-deep dense layer at training batches (25 / 23 k-steps)
+// conv weight-gradient partial slabs, one region per layer (conv3 and conv2 share a launch)
+constexpr size_t kSlabConv3 = 0, kSlabConv2 = (size_t)3200 * 1024, kSlabConv1 = (size_t)7424 * 1024;
+constexpr size_t kWgradSlabFloats = (size_t)9600 * 1024;
 
-static_assert(8 * 8 * 4 * 32 + 32 + 4 * 4 * 32 * 64 + 64 + 3 * 3 * 64 * 64 + 64 == kVarOffsetDense, "dense bucket offset");
+struct Bf16Net {
+  // bf16 MFMA operand copies of the master weights ([n][k], k contiguous)
+  bf16 *wf0 = nullptr, *wf1 = nullptr, *wb1 = nullptr, *wf2 = nullptr, *wb2 = nullptr, *wb3 = nullptr;
+  // k_sumsq: gradient ranges and their partials
+  int n_ranges = 0;
+  int64_t *d_rbeg = nullptr, *d_rend = nullptr;
+  float* d_partial = nullptr;
+  int* d_var_first = nullptr;
+  // clip_by_norm partials written by the gradient producers themselves (fc1 wgrad tiles, conv slab reduction
+  // blocks, fc2 wgrad blocks): while they belong to d_grads as it stands the k_sumsq pass is skipped
+  float* d_sqf = nullptr;
+  int* d_sqf_first = nullptr;
+  // Update-tail protocol.  fused_valid: this model's backward was the last writer of d_grads, so d_sqf holds that
+  // gradient's partials (set at the end of bf16_backward_conv, cleared by bf16_gradient_replaced alone: Adam reads
+  // d_grads and leaves it and d_sqf as they are).  norms_fused: bf16_norms' decision for the bf16_adam that follows -
+  // read d_sqf / d_sqf_first instead of d_partial / d_var_first.
+  bool fused_valid = false;
+  bool norms_fused = false;
+  // XCD-aware block -> tile table of the fc1 backward launch (built per batch size, fc1_bwd_map)
+  int* d_fc1bwd_map = nullptr;
+  int fc1bwd_map_B = -1, fc1bwd_grid = 0, fc1bwd_cap = 0;
+  // conv1 weight gradient as channel-half blocks (k_conv1_wgrad_h); QLX_CONV1_HALVES=0 at create time selects the
+  // one-block-per-chunk k_conv1_wgrad (bit-identical gradients)
+  bool conv1_halves = true;
+  // forward: fc1 as one pass with the fused epilogue at every batch size (no batch-size-dependent split-K), so a
+  // sample's result does not depend on the batch it is evaluated in (the learner's target net)
+  bool fc1_single = false;
+  // per-batch workspace (in the model's allocation, after the common buffers)
+  bf16 *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr;
+  bf16 *dz1 = nullptr, *dz2 = nullptr, *dz3 = nullptr, *dz4 = nullptr;
+  float* fc1slab = nullptr;
+  int a4_splits = 0;   // > 0: a4 still pending as that many split-K fc1 partials in fc1slab
+  float* slab = nullptr;
+};
 
 // fused clip_by_norm partial slots per variable: conv W/b from the slab reduction blocks (64 outputs each),
 // W3/b3 from the 25 x 4 fc1 wgrad tiles (each writes one W3 and one b3 slot), W4 from the 64 dW4 blocks
@@ -101,27 +133,6 @@ __device__ __forceinline__ void pack_one(const PackPtrs& P, int64_t idx, float w
 __global__ void k_pack_all(const float* w, int64_t count, PackPtrs P) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
     pack_one(P, i, w[i]);
-}
-
-// ------------------------------------------------------------------------------------------
-// host obs [B][x][y][slot] -> s2d frames [B*4][7056] + frame pointer table
-
-__global__ void k_pack_obs(const uint8_t* obs, int B, uint8_t* frames) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over B*84*84
-  if (i >= (int64_t)B * kFramePix) return;
-  const int b = (int)(i / kFramePix), xy = (int)(i - (int64_t)b * kFramePix);
-  const int x = xy / kFrame, y = xy - x * kFrame;
-  const uchar4 v = reinterpret_cast<const uchar4*>(obs)[i];
-  const int off = s2d_offset(x, y);
-  frames[((size_t)b * 4 + 0) * kFramePix + off] = v.x;
-  frames[((size_t)b * 4 + 1) * kFramePix + off] = v.y;
-  frames[((size_t)b * 4 + 2) * kFramePix + off] = v.z;
-  frames[((size_t)b * 4 + 3) * kFramePix + off] = v.w;
-}
-
-__global__ void k_frame_table(const uint8_t* frames, int B, const uint8_t** table) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B * 4) table[i] = frames + (size_t)i * kFramePix;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -322,7 +333,7 @@ __device__ __forceinline__ void fc2_wgrad_block(const Fc2WgradArgs& A, int j, fl
 // reduces), at chunk batches (and for the target net, fc1_single) in one pass with bias + ReLU; the backward as one
 // launch of the weight gradient (dW3 | db3 = a3^T dz4, 3137 x 512 x B), the backward data (dz3 = (dz4 W3^T) (a3 > 0),
 // B x 3136 x 512) and the dense-3 weight gradient blocks.
-// tiles and ring depths from scripts/ubench_bgemm.hip (gpurun_out/a4): forward at B = 1024 on 128 x 64 tiles in 4 k splits
+// tiles and ring depths from scripts/ubench_bgemm.hip: forward at B = 1024 on 128 x 64 tiles in 4 k splits
 // 8.7 us (128 x 128 in 7 splits: 9.6 us, and twice the slab bytes the head reads), backward data 9.1 us and weight
 // gradient 12.5 us on 8-wave 128 x 128 tiles with 4 stages
 using CfgFc1Fwd = BGemmCfg<128, 64, 2, 2, false, true, 4>;    // A = a3 (k = feature), B = W3 [3136][512] k-major
@@ -364,8 +375,8 @@ __global__ void k_a3_pad(bf16* a3, int B) {
 // blocks.  Every a3 / W3 panel is fetched into one L2 instead of up to eight, and both GEMMs (16 vs 8 k-steps
 // per tile) spread evenly over the XCDs.
 template <class PW, class PD>
-static void fc1_bwd_map(qlx_model* m, const PW& Pw, const PD& Pd, int extra, hipStream_t s) {
-  if (m->fc1bwd_map_B == Pd.M) return;
+static void fc1_bwd_map(Bf16Net& n, const PW& Pw, const PD& Pd, int extra, hipStream_t s) {
+  if (n.fc1bwd_map_B == Pd.M) return;
   std::vector<int> lists[8];
   auto tile_of = [](const auto& P, int mi, int nj) {
     return P.n_fastest ? mi * P.tiles_n + nj : nj * P.tiles_m + mi;
@@ -381,19 +392,18 @@ static void fc1_bwd_map(qlx_model* m, const PW& Pw, const PD& Pd, int extra, hip
   std::vector<int> map(8 * per, -1);
   for (int x = 0; x < 8; ++x)
     for (size_t l = 0; l < lists[x].size(); ++l) map[l * 8 + x] = lists[x][l];
-  if ((int)map.size() > m->fc1bwd_cap) {
+  if ((int)map.size() > n.fc1bwd_cap) {
     QLX_HIP(hipStreamSynchronize(s));
-    if (m->d_fc1bwd_map) (void)hipFree(m->d_fc1bwd_map);
-    QLX_HIP(hipMalloc(&m->d_fc1bwd_map, map.size() * sizeof(int)));
-    m->fc1bwd_cap = (int)map.size();
+    if (n.d_fc1bwd_map) (void)hipFree(n.d_fc1bwd_map);
+    QLX_HIP(hipMalloc(&n.d_fc1bwd_map, map.size() * sizeof(int)));
+    n.fc1bwd_cap = (int)map.size();
   }
-  QLX_HIP(hipMemcpy(m->d_fc1bwd_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-  m->fc1bwd_grid = (int)map.size();
-  m->fc1bwd_map_B = Pd.M;
+  QLX_HIP(hipMemcpy(n.d_fc1bwd_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+  n.fc1bwd_grid = (int)map.size();
+  n.fc1bwd_map_B = Pd.M;
 }
 
-void launch_fc2(int mode, const Fc2Args& a, int B, hipStream_t s) {
-  if (a.a4f) { f32_head(mode, a, B, s); return; }
+void bf16_head(int mode, const Fc2Args& a, int B, hipStream_t s) {
   const dim3 g((B + 3) / 4), blk(256);
   switch (mode) {
     case 0: hipLaunchKernelGGL(k_fc2<0>, g, blk, 0, s, a); break;
@@ -539,58 +549,80 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs A) {
 // ------------------------------------------------------------------------------------------
 // host side
 
-void model_workspace(qlx_model* m, int B) {
-  if (m->f32) { f32_workspace(m, B); return; }
-  if (B <= m->ws_batch) return;
-  QLX_HIP(hipStreamSynchronize(m->stream));
-  if (m->ws) (void)hipFree(m->ws);
-  m->ws = nullptr;
-  ModelWs& w = m->w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-  const size_t o_frames = take((size_t)B * 4 * kFramePix);
-  const size_t o_table = take((size_t)B * 4 * sizeof(void*));
-  const size_t o_a1 = take((size_t)B * 12800 * 2), o_a2 = take((size_t)B * 5184 * 2), o_a3 = take((size_t)B * kA3Ld * 2);
-  const size_t o_a4 = take((size_t)B * 512 * 2), o_q = take((size_t)B * 3 * 4);
-  const size_t o_dz1 = take((size_t)B * 12800 * 2), o_dz2 = take((size_t)B * 5184 * 2), o_dz3 = take((size_t)B * 3136 * 2);
-  const size_t o_dz4 = take((size_t)B * 512 * 2);
-  const size_t o_gs = take((size_t)B * 4), o_hs = take((size_t)B * 4), o_y = take((size_t)B * 4);
-  const size_t o_act = take((size_t)B), o_argmax = take((size_t)B), o_rew = take((size_t)B * 4), o_done = take((size_t)B);
-  const size_t o_fc1slab = take((size_t)kFc1Split * B * 512 * 4);
-  const size_t o_slab = take(kWgradSlabFloats * 4);
-  const size_t o_bslab = take(kBiasSlabFloats * 4);
-  const size_t o_loss = take(64);
-  QLX_HIP(hipMalloc(&m->ws, off));
-  char* base = (char*)m->ws;
-  w.frames = (uint8_t*)(base + o_frames);
-  w.table = (const uint8_t**)(base + o_table);
-  w.a1 = (bf16*)(base + o_a1); w.a2 = (bf16*)(base + o_a2); w.a3 = (bf16*)(base + o_a3); w.a4 = (bf16*)(base + o_a4);
-  w.q = (float*)(base + o_q);
-  w.dz1 = (bf16*)(base + o_dz1); w.dz2 = (bf16*)(base + o_dz2); w.dz3 = (bf16*)(base + o_dz3); w.dz4 = (bf16*)(base + o_dz4);
-  w.gs = (float*)(base + o_gs); w.hs = (float*)(base + o_hs); w.y = (float*)(base + o_y);
-  w.act = (uint8_t*)(base + o_act); w.argmax = (uint8_t*)(base + o_argmax); w.rew = (float*)(base + o_rew);
-  w.done = (uint8_t*)(base + o_done);
-  w.fc1slab = (float*)(base + o_fc1slab);
-  w.slab = (float*)(base + o_slab);
-  w.bslab = (float*)(base + o_bslab);
-  w.loss = (float*)(base + o_loss);
+void bf16_create(qlx_model* m) {
+  Bf16Net& n = *(m->bf16 = new Bf16Net);
+  const char* ch = std::getenv("QLX_CONV1_HALVES");
+  n.conv1_halves = !(ch && ch[0] == '0');
+  QLX_HIP(hipMalloc(&n.wf0, 32 * 256 * 2));
+  QLX_HIP(hipMalloc(&n.wf1, 64 * 512 * 2));
+  QLX_HIP(hipMalloc(&n.wb1, 32 * 1024 * 2));
+  QLX_HIP(hipMalloc(&n.wf2, 64 * 576 * 2));
+  QLX_HIP(hipMalloc(&n.wb2, 64 * 576 * 2));
+  QLX_HIP(hipMalloc(&n.wb3, 3136 * 512 * 2));
+  // norm ranges: chunks of <= 2048 elements (~830 blocks) that never cross a variable
+  std::vector<int64_t> rb, re;
+  std::vector<int> vf(kNumVars + 1, 0);
+  int64_t off = 0;
+  for (int v = 0; v < kNumVars; ++v) {
+    vf[v] = (int)rb.size();
+    for (int64_t i = 0; i < kVarSize[v]; i += 2048) {
+      rb.push_back(off + i);
+      re.push_back(off + std::min<int64_t>(kVarSize[v], i + 2048));
+    }
+    off += kVarSize[v];
+  }
+  vf[kNumVars] = (int)rb.size();
+  for (int v = 0; v < kNumVars; ++v)
+    QLX_CHECK(vf[v + 1] - vf[v] <= kAdamMaxPartials && kSqSlots[v] <= kAdamMaxPartials, QLX_E_STATE, "k_adam partial bound");
+  n.n_ranges = (int)rb.size();
+  QLX_HIP(hipMalloc(&n.d_rbeg, rb.size() * 8));
+  QLX_HIP(hipMalloc(&n.d_rend, re.size() * 8));
+  QLX_HIP(hipMalloc(&n.d_partial, rb.size() * 4));
+  QLX_HIP(hipMalloc(&n.d_var_first, vf.size() * 4));
+  std::vector<int> sf(kNumVars + 1);
+  for (int v = 0; v <= kNumVars; ++v) sf[v] = v < kNumVars ? sq_first(v) : sq_first(kNumVars - 1) + kSqSlots[kNumVars - 1];
+  QLX_HIP(hipMalloc(&n.d_sqf, sf[kNumVars] * 4));
+  QLX_HIP(hipMalloc(&n.d_sqf_first, sf.size() * 4));
+  QLX_HIP(hipMemcpy(n.d_sqf_first, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
+  QLX_HIP(hipMemset(n.d_sqf, 0, sf[kNumVars] * 4));
+  QLX_HIP(hipMemcpy(n.d_rbeg, rb.data(), rb.size() * 8, hipMemcpyHostToDevice));
+  QLX_HIP(hipMemcpy(n.d_rend, re.data(), re.size() * 8, hipMemcpyHostToDevice));
+  QLX_HIP(hipMemcpy(n.d_var_first, vf.data(), vf.size() * 4, hipMemcpyHostToDevice));
+}
+
+void bf16_destroy(qlx_model* m) {
+  Bf16Net* n = m->bf16;
+  if (!n) return;
+  for (void* p : {(void*)n->wf0, (void*)n->wf1, (void*)n->wb1, (void*)n->wf2, (void*)n->wb2, (void*)n->wb3, (void*)n->d_rbeg,
+                  (void*)n->d_rend, (void*)n->d_partial, (void*)n->d_var_first, (void*)n->d_sqf, (void*)n->d_sqf_first,
+                  (void*)n->d_fc1bwd_map})
+    (void)hipFree(p);
+  delete n;
+  m->bf16 = nullptr;
+}
+
+void bf16_workspace(qlx_model* m, int B) {
+  Bf16Net& w = *m->bf16;
+  ws_alloc(m, B, [&](Arena& a) {
+    w.a1 = a.take<bf16>((size_t)B * 12800); w.a2 = a.take<bf16>((size_t)B * 5184); w.a3 = a.take<bf16>((size_t)B * kA3Ld);
+    w.a4 = a.take<bf16>((size_t)B * 512);
+    w.dz1 = a.take<bf16>((size_t)B * 12800); w.dz2 = a.take<bf16>((size_t)B * 5184); w.dz3 = a.take<bf16>((size_t)B * 3136);
+    w.dz4 = a.take<bf16>((size_t)B * 512);
+    w.fc1slab = a.take<float>((size_t)kFc1Split * B * 512);
+    w.slab = a.take<float>(kWgradSlabFloats);
+  });
   hipLaunchKernelGGL(k_a3_pad, dim3((B * 8 + 255) / 256), dim3(256), 0, m->stream, w.a3, B);
   QLX_HIP(hipGetLastError());
-  m->ws_batch = B;
 }
 
-static PackPtrs pack_ptrs(qlx_model* m) {
-  PackPtrs P;
-  P.wf0 = m->wf0; P.wf1 = m->wf1; P.wb1 = m->wb1; P.wf2 = m->wf2; P.wb2 = m->wb2; P.wb3 = m->wb3;
-  return P;
-}
+static PackPtrs pack_ptrs(const Bf16Net& n) { return PackPtrs{n.wf0, n.wf1, n.wb1, n.wf2, n.wb2, n.wb3}; }
 
-void model_pack(qlx_model* m) {
-  m->version += 1;
-  if (m->f32) return;   // the fp32 path reads the master weights directly
-  hipLaunchKernelGGL(k_pack_all, dim3(2048), dim3(256), 0, m->stream, m->d_params, (int64_t)kNumParams, pack_ptrs(m));
+void bf16_pack(qlx_model* m) {
+  hipLaunchKernelGGL(k_pack_all, dim3(2048), dim3(256), 0, m->stream, m->d_params, (int64_t)kNumParams, pack_ptrs(*m->bf16));
   QLX_HIP(hipGetLastError());
 }
+
+void bf16_set_batch_invariant(qlx_model* m) { m->bf16->fc1_single = true; }
 
 // one block per CU (LDS-limited), persistent over samples
 static int trunk_grid(int B) { return std::max(1, std::min(B, 256)); }
@@ -617,9 +649,8 @@ static void launch_bgemm(const BGemmProblem<Epi>& P, hipStream_t s) {
   hipLaunchKernelGGL((k_bgemm<C, Epi>), dim3(xcd_grid(P.tiles())), dim3(C::T), C::LDS, s, P, 1);
 }
 
-void model_forward_trunk(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool store_acts) {
-  if (m->f32) { f32_forward(m, table, B, s); return; }
-  ModelWs& w = m->w;
+void bf16_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool store_acts) {
+  Bf16Net& w = *m->bf16;
   m->last_batch = B;
   const float* p = m->d_params;
   {  // conv1 -> conv2 -> conv3 fused per sample (trunk_kernels.h)
@@ -632,14 +663,14 @@ void model_forward_trunk(qlx_model* m, const uint8_t* const* table, int B, hipSt
     set_lds_attr(k_trunk_fwd<true>, kTrunkFwdLds);
     set_lds_attr(k_trunk_fwd<false>, kTrunkFwdLds);
     auto kern = store_acts ? k_trunk_fwd<true> : k_trunk_fwd<false>;
-    hipExtLaunchKernelGGL(kern, dim3(trunk_grid(B)), dim3(kTrunkThreads), kTrunkFwdLds, s, ea, eb, 0u, table, B, m->wf0, m->wf1,
-                          m->wf2, p + var_offset(1), p + var_offset(3), p + var_offset(5), w.a1, w.a2, w.a3);
+    hipExtLaunchKernelGGL(kern, dim3(trunk_grid(B)), dim3(kTrunkThreads), kTrunkFwdLds, s, ea, eb, 0u, table, B, w.wf0, w.wf1,
+                          w.wf2, p + var_offset(1), p + var_offset(3), p + var_offset(5), w.a1, w.a2, w.a3);
   }
   {  // fc1: M = B, N = 512, K = 3136.  Small batches split K into kFc1Split fp32 slabs (reduced with bias +
      // ReLU in fixed order) to fill the chip; from 64 M tiles on (B >= 8192) one pass with the epilogue fused
     ProfScope ps(m->prof, "fc1_fwd", s, 2.0 * B * 512 * 3136);
-    const BOp A{w.a3, kA3Ld, B}, W{m->wb3, 512, 512};
-    if (B >= 64 * 128 || m->fc1_single) {
+    const BOp A{w.a3, kA3Ld, B}, W{w.wb3, 512, 512};
+    if (B >= 64 * 128 || w.fc1_single) {
       launch_bgemm<CfgFc1FwdBig>(bproblem(A, W, B, 512, 3136, 1, CfgFc1FwdBig::BM, CfgFc1FwdBig::BN,
                                           Epi4BiasRelu{w.a4, p + var_offset(7), 512}), s);
       w.a4_splits = 0;
@@ -653,44 +684,32 @@ void model_forward_trunk(qlx_model* m, const uint8_t* const* table, int B, hipSt
   QLX_HIP(hipGetLastError());
 }
 
-Fc2Args fc2_args(qlx_model* m, int B) {
-  Fc2Args a{};
-  a.a4 = m->w.a4;
-  a.a4f = m->f32 ? m->w.fa4 : nullptr;
-  a.w4 = m->d_params + var_offset(8);
-  a.b4 = m->d_params + var_offset(9);
-  a.B = B;
-  a.q = m->w.q;
-  a.slab = m->w.fc1slab;
-  a.zstride = (size_t)B * 512;
-  a.splits = m->w.a4_splits;
-  a.b3 = m->d_params + var_offset(7);
-  a.a4_out = m->w.a4;
-  m->w.a4_splits = 0;
+// head arguments for the last forward; consumes pending fc1 partials (the head launch that follows materialises a4)
+Fc2Args bf16_fc2_args(qlx_model* m, int B) {
+  Bf16Net& w = *m->bf16;
+  Fc2Args a = fc2_common(m, B);
+  a.a4 = w.a4;
+  a.slab = w.fc1slab;
+  a.splits = w.a4_splits;
+  a.a4_out = w.a4;
+  w.a4_splits = 0;
   return a;
 }
 
-// Huber loss (mean over the batch -> *loss_dev) and its raw, unclipped gradients into m->d_grads, after
-// model_forward_trunk on the same batch; actions / y are device arrays [B]
-void model_backward(qlx_model* m, const uint8_t* const* table, int B, const uint8_t* actions, const float* y, float* loss_dev,
-                    hipStream_t s, const float* weights, float* td_abs, bool fuse_update) {
-  model_backward_dense(m, B, actions, y, loss_dev, s, weights, td_abs);
-  model_backward_conv(m, table, B, s, fuse_update);
-}
-
 // the head and dense part of the backward: Huber (+ dz4), dW4 / db4 / loss, dW3 / db3 and dz3
-void model_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
-                          const float* weights, float* td_abs) {
-  if (m->f32) { f32_backward_dense(m, B, actions, y, loss_dev, s, weights, td_abs); return; }
-  ModelWs& w = m->w;
+void bf16_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
+                         const float* weights, float* td_abs) {
+  Bf16Net& w = *m->bf16;
+  w.fused_valid = false;   // d_grads and d_sqf are half rewritten until bf16_backward_conv ends
   float* G = m->d_grads;
+  float *gs = m->w.gs, *hs = m->w.hs;
   {  // head: q, Huber, dz4 (one wave per sample)
     ProfScope ps(m->prof, "fc2_head", s);
-    Fc2Args a = fc2_args(m, B);
+    Fc2Args a = bf16_fc2_args(m, B);
     a.actions = actions;
     a.y = y;
-    a.gsample = w.gs;
-    a.hsample = w.hs;
+    a.gsample = gs;
+    a.hsample = hs;
     a.weights = weights;
     a.td_abs = td_abs;
     hipLaunchKernelGGL(k_fc2_train, dim3((B + 3) / 4), dim3(256), 0, s, a, w.dz4);
@@ -700,41 +719,39 @@ void model_backward_dense(qlx_model* m, int B, const uint8_t* actions, const flo
   //   dz3 = (dz4 W3^T) * (a3 > 0)
   {
     ProfScope ps(m->prof, "fc1_bwd", s, 2.0 * 2.0 * B * 512 * 3136);
-    const auto Pd = bproblem(BOp{w.dz4, 512, B}, BOp{m->wb3, 512, 3136}, B, 3136, 512, 1, 128, 128,
+    const auto Pd = bproblem(BOp{w.dz4, 512, B}, BOp{w.wb3, 512, 3136}, B, 3136, 512, 1, 128, 128,
                              Epi4ReluMask{w.dz3, w.a3, 3136, kA3Ld});
-    const Fc2WgradArgs F{w.a4, actions, w.gs, w.hs, B, G + var_offset(8), G + var_offset(9), loss_dev,
-                         m->d_sqf + sq_first(8), m->d_sqf + sq_first(9)};
+    const Fc2WgradArgs F{w.a4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev,
+                         w.d_sqf + sq_first(8), w.d_sqf + sq_first(9)};
     auto launch = [&](const auto& Pw, auto kern) {
       QLX_CHECK(Pw.tiles() == kFc1WgradTiles, QLX_E_STATE, "fc1 wgrad tiling changed: update kSqSlots");
       bgemm_check<CfgFc1Wg>(Pw);
       bgemm_check<CfgFc1Dg>(Pd);
-      fc1_bwd_map(m, Pw, Pd, kFc2WgradBlocks, s);
+      fc1_bwd_map(w, Pw, Pd, kFc2WgradBlocks, s);
       constexpr size_t lds_req = CfgFc1Wg::LDS;
       static_assert(lds_req >= (kFc1BwdThreads / 64 + 1) * 24 * sizeof(float), "fc2 wgrad block scratch");
       set_lds_attr(kern, lds_req);
-      hipLaunchKernelGGL(kern, dim3(m->fc1bwd_grid), dim3(kFc1BwdThreads), lds_req, s, Pw, Pd, F, (const int*)m->d_fc1bwd_map);
+      hipLaunchKernelGGL(kern, dim3(w.fc1bwd_grid), dim3(kFc1BwdThreads), lds_req, s, Pw, Pd, F, (const int*)w.d_fc1bwd_map);
     };
     // dW3 rows 0..3135 and db3 as row 3136 (a3's ones column), written straight into the flat gradient (b3 follows W3)
     launch(bproblem(BOp{w.a3, kA3Ld, 3137}, BOp{w.dz4, 512, 512}, 3137, 512, B, 1, 128, 128,
-                    Epi4StoreF32{G + var_offset(6), 512, m->d_sqf + sq_first(6)}, 3136),
+                    Epi4StoreF32{G + var_offset(6), 512, w.d_sqf + sq_first(6)}, 3136),
            k_fc1_bwd<Epi4StoreF32, Epi4ReluMask>);
   }
   QLX_HIP(hipGetLastError());
 }
 
-// the conv part of the backward (after model_backward_dense on the same batch): dz3 -> dz2 -> dz1 and the
+// the conv part of the backward (after bf16_backward_dense on the same batch): dz3 -> dz2 -> dz1 and the
 // three conv weight gradients into m->d_grads
-void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update, hipEvent_t dense_ready,
-                         float dense_scale) {
-  if (m->f32) { f32_backward_conv(m, table, B, s, fuse_update, dense_ready, dense_scale); return; }
-  ModelWs& w = m->w;
+void bf16_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s) {
+  Bf16Net& w = *m->bf16;
   float* G = m->d_grads;
   // dz2 = convT(dz3, W2) * (a2 > 0); dz1 = convT(dz2, W1) * (a1 > 0), fused per sample (trunk_kernels.h)
   {
     ProfScope ps(m->prof, "trunk_bwd_data", s, 2.0 * B * (49.0 * 64 * 576 + 81.0 * 64 * 512));
     set_lds_attr(k_trunk_bwd_data, kTrunkBwdLds);
     hipLaunchKernelGGL(k_trunk_bwd_data, dim3(trunk_grid(B)), dim3(kTrunkThreads), kTrunkBwdLds, s, w.dz3, w.a2, w.a1, B,
-                       m->wb2, m->wb1, w.dz2, w.dz1);
+                       w.wb2, w.wb1, w.dz2, w.dz1);
   }
   // conv3 (3 tap groups of 3 taps) + conv2 (2 groups of 8 taps) weight gradients in one launch, then
   // conv1's; per-block fp32 partials of [dW | db] rows, reduced in fixed order by one grouped launch
@@ -763,7 +780,7 @@ void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipSt
   const int grid1 = trunk_grid(B);
   {  // conv1: dW0 = im2col_s2d(x)^T dz1 per sample from the LDS-staged frames
     ProfScope ps(m->prof, "conv1_wgrad", s, 2.0 * B * 400 * 256 * 32);
-    if (m->conv1_halves) {   // two channel-half blocks per sample chunk, two blocks per CU
+    if (w.conv1_halves) {   // two channel-half blocks per sample chunk, two blocks per CU
       set_lds_attr(k_conv1_wgrad_h, kConv1WgradHLds);
       hipLaunchKernelGGL(k_conv1_wgrad_h, dim3(2 * grid1), dim3(kTrunkThreads), kConv1WgradHLds, s, table, w.dz1, B, grid1,
                          w.slab + kSlabConv1);
@@ -778,9 +795,9 @@ void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipSt
     // slot ranges: each layer's weight blocks then its one bias block (sq_first(W) + blocks == sq_first(b))
     static_assert(CW3::ZS == 576 * 64 + 64 && CW2::ZS == 512 * 64 + 64 && kConv1SlabStride == 128 * 64 + 32, "slab blocks");
     SlabSeg segs[3] = {
-        {w.slab + kSlabConv3, CW3::ZS, used3, CW3::ZS, G + var_offset(4), 0, m->d_sqf + sq_first(4)},
-        {w.slab + kSlabConv2, CW2::ZS, used2, CW2::ZS, G + var_offset(2), 0, m->d_sqf + sq_first(2)},
-        {w.slab + kSlabConv1, (size_t)kConv1SlabStride, grid1, (size_t)kConv1SlabStride, G, 1, m->d_sqf + sq_first(0)},
+        {w.slab + kSlabConv3, CW3::ZS, used3, CW3::ZS, G + var_offset(4), 0, w.d_sqf + sq_first(4)},
+        {w.slab + kSlabConv2, CW2::ZS, used2, CW2::ZS, G + var_offset(2), 0, w.d_sqf + sq_first(2)},
+        {w.slab + kSlabConv1, (size_t)kConv1SlabStride, grid1, (size_t)kConv1SlabStride, G, 1, w.d_sqf + sq_first(0)},
     };
     SlabSegs3 a;
     int blocks = 0;
@@ -793,31 +810,36 @@ void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipSt
     hipLaunchKernelGGL(k_slab_reduce3, dim3(blocks), dim3(256), 0, s, a);
   }
   QLX_HIP(hipGetLastError());
+  w.fused_valid = true;   // d_sqf now holds the partials of every variable of the gradient in d_grads
 }
 
+void bf16_gradient_replaced(qlx_model* m) { m->bf16->fused_valid = false; }
 
-void model_norms(qlx_model* m, hipStream_t s, float scale) {
-  if (m->f32) { f32_norms(m, s, scale); return; }
-  m->norms_fused = scale == 1.0f;   // the gradients are exactly what model_backward produced
-  if (m->norms_fused) return;
+// per-variable norm partials for Adam: the producers' fused partials as they are when they belong to d_grads and
+// scale == 1 (an all-reduce in between comes with another scale, or is the identity), otherwise per-range sums of
+// squares of the scaled gradients
+void bf16_norms(qlx_model* m, hipStream_t s, float scale) {
+  Bf16Net& n = *m->bf16;
+  n.norms_fused = n.fused_valid && scale == 1.0f;
+  if (n.norms_fused) return;
   ProfScope ps(m->prof, "norms", s);
-  hipLaunchKernelGGL(k_sumsq, dim3(m->n_ranges), dim3(256), 0, s, m->d_grads, m->d_rbeg, m->d_rend, scale, m->d_partial);
+  hipLaunchKernelGGL(k_sumsq, dim3(n.n_ranges), dim3(256), 0, s, m->d_grads, n.d_rbeg, n.d_rend, scale, n.d_partial);
   QLX_HIP(hipGetLastError());
 }
 
-void model_adam(qlx_model* m, hipStream_t s, float scale) {
-  if (m->f32) { f32_adam(m, s, scale); return; }
+void bf16_adam(qlx_model* m, hipStream_t s, float scale) {
+  Bf16Net& n = *m->bf16;
   const int64_t t = m->iterations + 1;
   const float tf = (float)t;
   const float b1p = std::pow(m->beta1, tf), b2p = std::pow(m->beta2, tf);
   AdamArgs a;
   a.w = m->d_params; a.m = m->d_m; a.v = m->d_v; a.g = m->d_grads; a.norms = m->d_norms;
-  a.partial = m->norms_fused ? m->d_sqf : m->d_partial;
-  a.var_first = m->norms_fused ? m->d_sqf_first : m->d_var_first;
+  a.partial = n.norms_fused ? n.d_sqf : n.d_partial;
+  a.var_first = n.norms_fused ? n.d_sqf_first : n.d_var_first;
   a.count = kNumParams; a.scale = scale;
   a.alpha = m->lr * std::sqrt(1.0f - b2p) / (1.0f - b1p);
   a.beta1 = m->beta1; a.beta2 = m->beta2; a.eps = m->eps; a.clipnorm = m->clipnorm;
-  a.pack = pack_ptrs(m);
+  a.pack = pack_ptrs(n);
   ProfScope ps(m->prof, "adam", s, 32.0 * kNumParams);
   const int64_t groups = kNumParams / 4 + 1;   // float4 groups + the tail group
   hipLaunchKernelGGL(k_adam, dim3((unsigned)((groups + 256 * kAdamGroups - 1) / (256 * kAdamGroups))), dim3(256), 0, s, a);
@@ -825,356 +847,30 @@ void model_adam(qlx_model* m, hipStream_t s, float scale) {
   m->iterations = t;
 }
 
-void model_frame_table_from_host(qlx_model* m, const uint8_t* obs_host, int B) {
-  model_workspace(m, B);
-  uint8_t* d_obs = nullptr;
-  const size_t bytes = (size_t)B * kFramePix * 4;
-  QLX_HIP(hipMalloc(&d_obs, bytes));
-  QLX_HIP(hipMemcpyAsync(d_obs, obs_host, bytes, hipMemcpyHostToDevice, m->stream));
-  hipLaunchKernelGGL(k_pack_obs, dim3((B * kFramePix + 255) / 256), dim3(256), 0, m->stream, d_obs, B, m->w.frames);
-  hipLaunchKernelGGL(k_frame_table, dim3((B * 4 + 255) / 256), dim3(256), 0, m->stream, m->w.frames, B, m->w.table);
-  QLX_HIP(hipGetLastError());
+// layer 1..4 of the last forward, widened to fp32
+void bf16_last_activation(qlx_model* m, int layer, float* out) {
+  Bf16Net& w = *m->bf16;
+  if (layer == 4 && w.a4_splits > 0) {   // forward without a head yet: finish a4 from the fc1 partials
+    const int B = m->last_batch;
+    hipLaunchKernelGGL(k_slab_reduce_bias_relu, dim3(std::min(2048, (B * 512 + 255) / 256)), dim3(256), 0, m->stream,
+                       w.fc1slab, (size_t)B * 512, w.a4_splits, B, 512, m->d_params + var_offset(7), w.a4);
+    QLX_HIP(hipGetLastError());
+    w.a4_splits = 0;
+  }
   QLX_HIP(hipStreamSynchronize(m->stream));
-  QLX_HIP(hipFree(d_obs));
-}
-
-static void glorot_host(std::vector<float>& params, uint64_t seed) {
-  const int fan_in[5] = {8 * 8 * 4, 4 * 4 * 32, 3 * 3 * 64, 3136, 512};
-  const int fan_out[5] = {8 * 8 * 32, 4 * 4 * 64, 3 * 3 * 64, 512, 3};
-  params.assign(kNumParams, 0.0f);
-  int64_t off = 0;
-  for (int v = 0; v < kNumVars; ++v) {
-    if (v % 2 == 0) {
-      const int l = v / 2;
-      const float limit = std::sqrt(6.0f / (float)(fan_in[l] + fan_out[l]));
-      RngStream s(seed, (uint32_t)v, 0, P_INIT);
-      for (int i = 0; i < kVarSize[v]; ++i) params[off + i] = uniform_f32(s, -limit, limit);
-    }
-    off += kVarSize[v];
+  const size_t per[5] = {0, 12800, 5184, 3136, 512};
+  const bf16* src = layer == 1 ? w.a1 : layer == 2 ? w.a2 : layer == 3 ? w.a3 : w.a4;
+  const size_t count = per[layer] * (size_t)m->last_batch;
+  std::vector<uint16_t> tmp(count);
+  if (layer == 3)   // rows kA3Ld apart
+    QLX_HIP(hipMemcpy2D(tmp.data(), 3136 * 2, src, (size_t)kA3Ld * 2, 3136 * 2, (size_t)m->last_batch, hipMemcpyDeviceToHost));
+  else
+    QLX_HIP(hipMemcpy(tmp.data(), src, count * 2, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < count; ++i) {
+    const uint32_t b = (uint32_t)tmp[i] << 16;
+    std::memcpy(&out[i], &b, 4);
   }
 }
 
 }  // namespace qlx
 
-using namespace qlx;
-
-extern "C" {
-
-int32_t qlx_model_num_vars(void) { return kNumVars; }
-
-int32_t qlx_model_hparams(float* out) {
-  return guard([&] {
-    QLX_CHECK(out, QLX_E_INVALID, "null out");
-    const qlx_model m;   // the defaults every created model starts from (no device state is touched)
-    out[0] = m.lr; out[1] = m.beta1; out[2] = m.beta2; out[3] = m.eps; out[4] = m.clipnorm;
-  });
-}
-int64_t qlx_model_var_size(int32_t v) { return (v >= 0 && v < kNumVars) ? kVarSize[v] : -1; }
-
-int32_t qlx_model_create(int32_t arch, uint64_t seed, int32_t device, qlx_model** out) {
-  return guard([&] {
-    QLX_CHECK((arch == QLX_ARCH_NATURE_DQN || arch == QLX_ARCH_NATURE_DQN_BF16) && out, QLX_E_INVALID, "unknown model arch");
-    current_device_checked(device);
-    auto* m = new qlx_model;
-    m->f32 = arch == QLX_ARCH_NATURE_DQN;
-    const char* ch = std::getenv("QLX_CONV1_HALVES");
-    m->conv1_halves = !(ch && ch[0] == '0');
-    const char* bg = std::getenv("QLX_F32_BG");
-    m->f32_bg_rows = !(bg && bg[0] == '0');
-    const char* sk = std::getenv("QLX_F32_C1_SKIP");
-    m->f32_c1_skip = (sk && sk[0] == '0') ? 0 : 1;
-    try {   // a failure part-way releases what was built
-      m->device = device;
-      QLX_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-      const size_t pb = kNumParams * sizeof(float);
-      QLX_HIP(hipMalloc(&m->d_params, pb));
-      QLX_HIP(hipMalloc(&m->d_m, pb));
-      QLX_HIP(hipMalloc(&m->d_v, pb));
-      QLX_HIP(hipMalloc(&m->d_grads, pb));
-      if (!m->f32) {   // bf16 MFMA operand copies
-        QLX_HIP(hipMalloc(&m->wf0, 32 * 256 * 2));
-        QLX_HIP(hipMalloc(&m->wf1, 64 * 512 * 2));
-        QLX_HIP(hipMalloc(&m->wb1, 32 * 1024 * 2));
-        QLX_HIP(hipMalloc(&m->wf2, 64 * 576 * 2));
-        QLX_HIP(hipMalloc(&m->wb2, 64 * 576 * 2));
-        QLX_HIP(hipMalloc(&m->wb3, 3136 * 512 * 2));
-      }
-      // norm ranges: chunks of <= 2048 elements (~830 blocks) that never cross a variable
-      std::vector<int64_t> rb, re;
-      std::vector<int> vf(kNumVars + 1, 0);
-      int64_t off = 0;
-      for (int v = 0; v < kNumVars; ++v) {
-        vf[v] = (int)rb.size();
-        for (int64_t i = 0; i < kVarSize[v]; i += 2048) {
-          rb.push_back(off + i);
-          re.push_back(off + std::min<int64_t>(kVarSize[v], i + 2048));
-        }
-        off += kVarSize[v];
-      }
-      vf[kNumVars] = (int)rb.size();
-      for (int v = 0; v < kNumVars; ++v)
-        QLX_CHECK(vf[v + 1] - vf[v] <= kAdamMaxPartials && kSqSlots[v] <= kAdamMaxPartials, QLX_E_STATE, "k_adam partial bound");
-      m->n_ranges = (int)rb.size();
-      QLX_HIP(hipMalloc(&m->d_rbeg, rb.size() * 8));
-      QLX_HIP(hipMalloc(&m->d_rend, re.size() * 8));
-      QLX_HIP(hipMalloc(&m->d_partial, rb.size() * 4));
-      QLX_HIP(hipMalloc(&m->d_var_first, vf.size() * 4));
-      QLX_HIP(hipMalloc(&m->d_norms, 64));
-      std::vector<int> sf(kNumVars + 1);
-      for (int v = 0; v <= kNumVars; ++v) sf[v] = v < kNumVars ? sq_first(v) : sq_first(kNumVars - 1) + kSqSlots[kNumVars - 1];
-      QLX_HIP(hipMalloc(&m->d_sqf, sf[kNumVars] * 4));
-      QLX_HIP(hipMalloc(&m->d_sqf_first, sf.size() * 4));
-      QLX_HIP(hipMemcpy(m->d_sqf_first, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
-      QLX_HIP(hipMemset(m->d_sqf, 0, sf[kNumVars] * 4));
-      QLX_HIP(hipMemcpy(m->d_rbeg, rb.data(), rb.size() * 8, hipMemcpyHostToDevice));
-      QLX_HIP(hipMemcpy(m->d_rend, re.data(), re.size() * 8, hipMemcpyHostToDevice));
-      QLX_HIP(hipMemcpy(m->d_var_first, vf.data(), vf.size() * 4, hipMemcpyHostToDevice));
-      std::vector<float> params;
-      glorot_host(params, seed);
-      QLX_HIP(hipMemcpy(m->d_params, params.data(), pb, hipMemcpyHostToDevice));
-      QLX_HIP(hipMemset(m->d_m, 0, pb));
-      QLX_HIP(hipMemset(m->d_v, 0, pb));
-      QLX_HIP(hipMemset(m->d_grads, 0, pb));
-      model_pack(m);
-      QLX_HIP(hipStreamSynchronize(m->stream));
-    } catch (...) {
-      qlx_model_destroy(m);
-      throw;
-    }
-    *out = m;
-  });
-}
-
-int32_t qlx_model_destroy(qlx_model* m) {
-  return guard([&] {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    (void)hipStreamSynchronize(m->stream);
-    void* ptrs[] = {m->d_params, m->d_m, m->d_v, m->d_grads, m->wf0, m->wf1, m->wb1, m->wf2, m->wb2, m->wb3,
-                    m->d_rbeg, m->d_rend, m->d_partial, m->d_var_first, m->d_norms, m->d_sqf, m->d_sqf_first, m->ws, m->d_fc1bwd_map,
-                    m->w.fgrad};
-    for (void* p : ptrs) (void)hipFree(p);
-    if (m->own_stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-  });
-}
-
-int32_t qlx_model_get_var(qlx_model* m, int32_t var, int32_t which, float* out) {
-  return guard([&] {
-    QLX_CHECK(m && out && var >= 0 && var < kNumVars && which >= 0 && which <= 2, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipSetDevice(m->device));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    const float* src = (which == 0 ? m->d_params : which == 1 ? m->d_m : m->d_v) + var_offset(var);
-    QLX_HIP(hipMemcpy(out, src, kVarSize[var] * sizeof(float), hipMemcpyDeviceToHost));
-  });
-}
-
-int32_t qlx_model_set_var(qlx_model* m, int32_t var, int32_t which, const float* in) {
-  return guard([&] {
-    QLX_CHECK(m && in && var >= 0 && var < kNumVars && which >= 0 && which <= 2, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipSetDevice(m->device));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    float* dst = (which == 0 ? m->d_params : which == 1 ? m->d_m : m->d_v) + var_offset(var);
-    QLX_HIP(hipMemcpy(dst, in, kVarSize[var] * sizeof(float), hipMemcpyHostToDevice));
-    if (which == 0) {
-      model_pack(m);
-      QLX_HIP(hipStreamSynchronize(m->stream));
-    }
-  });
-}
-
-int64_t qlx_model_iterations(qlx_model* m) { return m ? m->iterations : -1; }
-
-int32_t qlx_model_copy_weights(qlx_model* dst, const qlx_model* src) {
-  return guard([&] {
-    QLX_CHECK(dst && src, QLX_E_INVALID, "null model");
-    QLX_HIP(hipSetDevice(dst->device));
-    QLX_HIP(hipStreamSynchronize(src->stream));
-    QLX_HIP(hipMemcpyAsync(dst->d_params, src->d_params, kNumParams * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
-    model_pack(dst);
-    QLX_HIP(hipStreamSynchronize(dst->stream));
-  });
-}
-
-int32_t qlx_model_predict(qlx_model* m, const uint8_t* obs, uint32_t n, float* q_out, uint8_t* actions) {
-  return guard([&] {
-    QLX_CHECK(m && obs && n > 0, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipSetDevice(m->device));
-    model_frame_table_from_host(m, obs, (int)n);
-    model_forward_trunk(m, m->w.table, (int)n, m->stream);
-    Fc2Args a = fc2_args(m, (int)n);
-    a.argmax = m->w.argmax;
-    launch_fc2(1, a, (int)n, m->stream);
-    if (q_out) QLX_HIP(hipMemcpyAsync(q_out, m->w.q, n * 3 * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    if (actions) QLX_HIP(hipMemcpyAsync(actions, m->w.argmax, n, hipMemcpyDeviceToHost, m->stream));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-  });
-}
-
-int32_t qlx_model_batch_max_q(qlx_model* m, const uint8_t* obs, uint32_t n, float* out) {
-  return guard([&] {
-    QLX_CHECK(m && obs && out && n > 0, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipSetDevice(m->device));
-    model_frame_table_from_host(m, obs, (int)n);
-    model_forward_trunk(m, m->w.table, (int)n, m->stream);
-    // y = 0 + max * 1 with done = 0: the bare reduce_max of the reference signature
-    QLX_HIP(hipMemsetAsync(m->w.rew, 0, n * 4, m->stream));
-    QLX_HIP(hipMemsetAsync(m->w.done, 0, n, m->stream));
-    Fc2Args a = fc2_args(m, (int)n);
-    a.rewards = m->w.rew; a.dones = m->w.done; a.gamma = 1.0f; a.y_out = m->w.y;
-    launch_fc2(2, a, (int)n, m->stream);
-    QLX_HIP(hipMemcpyAsync(out, m->w.y, n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-  });
-}
-
-int32_t qlx_model_train(qlx_model* m, const uint8_t* obs, const uint8_t* actions, const float* y, uint32_t B,
-                        float* loss_out, float* grads_out, float* norms_out) {
-  return guard([&] {
-    QLX_CHECK(m && obs && actions && y && B > 0, QLX_E_INVALID, "bad argument");
-    for (uint32_t b = 0; b < B; ++b) QLX_CHECK(actions[b] < kActions, QLX_E_INVALID, "action out of range");
-    QLX_HIP(hipSetDevice(m->device));
-    model_frame_table_from_host(m, obs, (int)B);
-    hipStream_t s = m->stream;
-    QLX_HIP(hipMemcpyAsync(m->w.act, actions, B, hipMemcpyHostToDevice, s));
-    QLX_HIP(hipMemcpyAsync(m->w.y, y, B * 4, hipMemcpyHostToDevice, s));
-    model_forward_trunk(m, m->w.table, (int)B, s);
-    model_backward(m, m->w.table, (int)B, m->w.act, m->w.y, m->w.loss, s, nullptr, nullptr, true);
-    if (grads_out) QLX_HIP(hipMemcpyAsync(grads_out, m->d_grads, kNumParams * 4, hipMemcpyDeviceToHost, s));
-    model_norms(m, s, 1.0f);
-    model_adam(m, s, 1.0f);
-    if (norms_out) QLX_HIP(hipMemcpyAsync(norms_out, m->d_norms, kNumVars * 4, hipMemcpyDeviceToHost, s));
-    if (loss_out) QLX_HIP(hipMemcpyAsync(loss_out, m->w.loss, 4, hipMemcpyDeviceToHost, s));
-    QLX_HIP(hipStreamSynchronize(s));
-  });
-}
-
-// The update tail alone on a given gradient (test hook of the data-parallel tail, whose all-reduced gradient is scaled by
-// 1 / world): clip_by_norm of (grads x scale) per variable + legacy Adam, exactly as learner_update runs them after an
-// all-reduce (model_norms, then model_adam at that scale).  fp32: the same two launches as a rank's DP tail; bf16: the
-// explicit sum-of-squares pass (the backward's fused partials do not belong to this gradient) and the Adam launch.
-int32_t qlx_model_apply_gradient(qlx_model* m, const float* grads, float scale, float* norms_out) {
-  return guard([&] {
-    QLX_CHECK(m && grads, QLX_E_INVALID, "null argument");
-    QLX_CHECK(std::isfinite(scale) && scale > 0.0f, QLX_E_INVALID, "scale must be finite and > 0");
-    QLX_HIP(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    model_workspace(m, std::max(m->ws_batch, 1));   // (the norm partial buffers)
-    QLX_HIP(hipMemcpyAsync(m->d_grads, grads, kNumParams * 4, hipMemcpyHostToDevice, s));
-    if (m->f32) {
-      m->f32_update_scheduled = false;
-      m->f32_dense_partials = false;   // partials of an earlier gradient (an update that threw before its Adam)
-      model_norms(m, s, scale);
-    } else {
-      m->norms_fused = false;
-      hipLaunchKernelGGL(k_sumsq, dim3(m->n_ranges), dim3(256), 0, s, m->d_grads, m->d_rbeg, m->d_rend, scale, m->d_partial);
-      QLX_HIP(hipGetLastError());
-    }
-    model_adam(m, s, scale);
-    if (norms_out) QLX_HIP(hipMemcpyAsync(norms_out, m->d_norms, kNumVars * 4, hipMemcpyDeviceToHost, s));
-    QLX_HIP(hipStreamSynchronize(s));
-  });
-}
-
-int32_t qlx_model_last_activation(qlx_model* m, int32_t layer, float* out) {
-  return guard([&] {
-    QLX_CHECK(m && out && layer >= 1 && layer <= 4 && m->ws_batch > 0, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipSetDevice(m->device));
-    if (m->f32) {   // a1..a3 of the last forward chunk (the whole batch up to kF32FwdChunk samples), a4 of all
-      QLX_CHECK(layer == 4 || m->last_batch <= m->w.fchunk, QLX_E_STATE, "activations of a chunked forward");
-      QLX_HIP(hipStreamSynchronize(m->stream));
-      const size_t per[5] = {0, 12800, 5184, 3136, 512};
-      const float* src = layer == 1 ? m->w.fa1 : layer == 2 ? m->w.fa2 : layer == 3 ? m->w.fa3 : m->w.fa4;
-      QLX_HIP(hipMemcpy(out, src, per[layer] * (size_t)m->last_batch * 4, hipMemcpyDeviceToHost));
-      return;
-    }
-    if (layer == 4 && m->w.a4_splits > 0) {   // forward without a head yet: finish a4 from the fc1 partials
-      const int B = m->last_batch;
-      hipLaunchKernelGGL(k_slab_reduce_bias_relu, dim3(std::min(2048, (B * 512 + 255) / 256)), dim3(256), 0, m->stream,
-                         m->w.fc1slab, (size_t)B * 512, m->w.a4_splits, B, 512, m->d_params + var_offset(7), m->w.a4);
-      QLX_HIP(hipGetLastError());
-      m->w.a4_splits = 0;
-    }
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    const size_t per[5] = {0, 12800, 5184, 3136, 512};
-    const bf16* src = layer == 1 ? m->w.a1 : layer == 2 ? m->w.a2 : layer == 3 ? m->w.a3 : m->w.a4;
-    const size_t count = per[layer] * (size_t)m->last_batch;
-    std::vector<uint16_t> tmp(count);
-    if (layer == 3)   // rows kA3Ld apart
-      QLX_HIP(hipMemcpy2D(tmp.data(), 3136 * 2, src, (size_t)kA3Ld * 2, 3136 * 2, (size_t)m->last_batch, hipMemcpyDeviceToHost));
-    else
-      QLX_HIP(hipMemcpy(tmp.data(), src, count * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) {
-      const uint32_t b = (uint32_t)tmp[i] << 16;
-      std::memcpy(&out[i], &b, 4);
-    }
-  });
-}
-
-int32_t qlx_model_write_checkpoint(qlx_model* m, const char* path) {
-  return guard([&] {
-    QLX_CHECK(m && path, QLX_E_INVALID, "bad argument");
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    std::vector<float> buf(kNumParams * 3);
-    QLX_HIP(hipMemcpy(buf.data(), m->d_params, kNumParams * 4, hipMemcpyDeviceToHost));
-    QLX_HIP(hipMemcpy(buf.data() + kNumParams, m->d_m, kNumParams * 4, hipMemcpyDeviceToHost));
-    QLX_HIP(hipMemcpy(buf.data() + 2 * kNumParams, m->d_v, kNumParams * 4, hipMemcpyDeviceToHost));
-    FILE* f = std::fopen(path, "wb");
-    QLX_CHECK(f, QLX_E_IO, std::string("cannot open ") + path);
-    const char magic[8] = {'Q', 'L', 'X', 'C', 'K', 'P', 'T', '1'};
-    const int64_t hdr[2] = {kNumParams, m->iterations};
-    bool ok = std::fwrite(magic, 1, 8, f) == 8 && std::fwrite(hdr, 8, 2, f) == 2 &&
-              std::fwrite(buf.data(), 4, buf.size(), f) == buf.size();
-    ok = (std::fclose(f) == 0) && ok;
-    QLX_CHECK(ok, QLX_E_IO, "checkpoint write failed");
-  });
-}
-
-int32_t qlx_model_load_tf(qlx_model* m, const char* prefix) {
-  return guard([&] {
-    QLX_CHECK(m && prefix, QLX_E_INVALID, "null argument");
-    std::vector<float> w, mm, vv;
-    int64_t it = 0;
-    load_keras_bundle(prefix, 5, kVarSize, w, mm, vv, &it);
-    QLX_HIP(hipSetDevice(m->device));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    QLX_HIP(hipMemcpy(m->d_params, w.data(), kNumParams * 4, hipMemcpyHostToDevice));
-    QLX_HIP(hipMemcpy(m->d_m, mm.data(), kNumParams * 4, hipMemcpyHostToDevice));
-    QLX_HIP(hipMemcpy(m->d_v, vv.data(), kNumParams * 4, hipMemcpyHostToDevice));
-    m->iterations = it;
-    model_pack(m);
-    QLX_HIP(hipStreamSynchronize(m->stream));
-  });
-}
-
-int32_t qlx_model_read_checkpoint(qlx_model* m, const char* path) {
-  return guard([&] {
-    QLX_CHECK(m && path, QLX_E_INVALID, "bad argument");
-    FILE* f = std::fopen(path, "rb");
-    QLX_CHECK(f, QLX_E_IO, std::string("cannot open ") + path);
-    char magic[8];
-    int64_t hdr[2];
-    std::vector<float> buf(kNumParams * 3);
-    bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, "QLXCKPT1", 8) == 0 && std::fread(hdr, 8, 2, f) == 2 &&
-              hdr[0] == kNumParams && std::fread(buf.data(), 4, buf.size(), f) == buf.size();
-    std::fclose(f);
-    QLX_CHECK(ok, QLX_E_IO, "not a qlx checkpoint");
-    QLX_HIP(hipSetDevice(m->device));
-    QLX_HIP(hipStreamSynchronize(m->stream));
-    QLX_HIP(hipMemcpy(m->d_params, buf.data(), kNumParams * 4, hipMemcpyHostToDevice));
-    QLX_HIP(hipMemcpy(m->d_m, buf.data() + kNumParams, kNumParams * 4, hipMemcpyHostToDevice));
-    QLX_HIP(hipMemcpy(m->d_v, buf.data() + 2 * kNumParams, kNumParams * 4, hipMemcpyHostToDevice));
-    m->iterations = hdr[1];
-    model_pack(m);
-    QLX_HIP(hipStreamSynchronize(m->stream));
-  });
-}
-
-int32_t qlx_model_sync(qlx_model* m) {
-  return guard([&] {
-    QLX_CHECK(m, QLX_E_INVALID, "null model");
-    QLX_HIP(hipStreamSynchronize(m->stream));
-  });
-}
-
-}  // extern "C"

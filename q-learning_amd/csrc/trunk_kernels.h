@@ -782,7 +782,7 @@ __device__ __forceinline__ bool wgrad_chunk_group(int t, int used, int& chunk, i
 }
 __host__ __device__ __forceinline__ int wgrad_blocks(int groups, int used) { return (used + 7) / 8 * 8 * groups; }
 
-// samples per LDS round (the chunk sizes are multiples of these, qnet.hip).  Measured at C3 (bf16, gpurun_out/a8): conv3 4 and
+// samples per LDS round (the chunk sizes are multiples of these, qnet_bf16.hip).  Measured at C3 (bf16): conv3 4 and
 // conv2 2 samples per round (95 KB of LDS) took the launch 25.8 -> 34.3 us; one sample per round is kept
 constexpr int kWg3Samples = 1, kWg2Samples = 1;
 // conv3 (blocks [0, wgrad_blocks(3, used3))) and conv2 (the rest) in one launch

@@ -93,7 +93,7 @@ def adam_alpha(hp, t):
 
 
 def adam_step(g, norm, w, m, v, hp, t, scale=1.0):
-    """adam_elem (q-learning_amd/csrc/qnet.hip) in numpy float32, one rounded operation per line."""
+    """adam_elem (q-learning_amd/csrc/qnet_bf16.hip) in numpy float32, one rounded operation per line."""
     f = np.float32
     lr, beta1, beta2, eps, clipnorm = (f(x) for x in hp)
     g, w, m, v = (np.asarray(a, f) for a in (g, w, m, v))

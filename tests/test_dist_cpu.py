@@ -123,7 +123,7 @@ def _worker_f32(rank, world, port, B, steps, out_dir):
 @pytest.mark.timeout(600)
 def test_dp_fp32_chain_two_buckets_world2(tmp_path):
     """The fp32 data-parallel update at world 2, restated on the fp32 chain oracle with the product's bucket order
-    (learner.hip:397-423): (1) both ranks end every update with identical weights and Adam slots, bit for bit; (2) the
+    (learner.hip learner_update, the two-bucket branch): (1) both ranks end every update with identical weights and Adam slots, bit for bit; (2) the
     all-reduced gradient is the fp32 sum of the per-rank chain gradients (a two-term sum: exact IEEE, order-free), so the
     world-2 update is a fixed function of the per-rank batches; (3) against the single-GPU update on the union batch
     (one chain over all 2 B samples) it differs only by fp32 reassociation - the stated multi-rank tolerance (DESIGN.md

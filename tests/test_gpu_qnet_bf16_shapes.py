@@ -67,6 +67,23 @@ def bf16_model(seed, bias_seed):
     return m, w
 
 
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def fresh_copy(live, path):
+    """A new model with the live one's weights, Adam slots and iteration count (through a checkpoint, which carries all)."""
+    qlx = _qlx()
+    live.write_checkpoint(path)
+    m = qlx.DeepQLearningModel(seed=1, precision=qlx.PREC_BF16)
+    m.read_checkpoint(path)
+    assert m.iterations() == live.iterations()
+    for v in range(10):
+        for which in range(3):
+            assert np.array_equal(bits(m.get(v, which)), bits(live.get(v, which)))
+    return m
+
+
 def stored_activations(m, B):
     out = []
     for layer in range(1, 5):

@@ -5,7 +5,7 @@ activation rows, stale weight-gradient slab rows, stale norm partial slots and a
 kernels are fixed-order, so a model with that history must produce the very bytes a fresh model with the same
 weights, Adam slots and iteration count produces: Q, loss, all ten gradients, norms and w / m / v, no tolerance.
 
-Update tail: adam_elem (q-learning_amd/csrc/qnet.hip) restated in numpy float32, one rounded operation per line
+Update tail: adam_elem (q-learning_amd/csrc/qnet_bf16.hip) restated in numpy float32, one rounded operation per line
 (tests/bf16_checks.py adam_step), from the returned raw gradients, the returned norms and w / m / v read before the step;
 w / m / v after the step are equal bit for bit (measured: 0 of 3 x 1,685,667 elements unequal at every step; the device's
 division and square root are correctly rounded.  Before adam_elem kept the compiler from contracting m + d (1 - beta1),
@@ -19,30 +19,13 @@ import numpy as np
 import pytest
 
 import bf16_checks as C
-from test_gpu_qnet_bf16_shapes import _qlx, bf16_model, check_forward, states
+from test_gpu_qnet_bf16_shapes import _qlx, bf16_model, bits, check_forward, fresh_copy, states
 
 pytestmark = pytest.mark.gpu
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def slots(m):
     return [[m.get(v, which) for which in range(3)] for v in range(10)]
-
-
-def fresh_copy(live, path):
-    """A new model with the live one's weights, Adam slots and iteration count (through a checkpoint, which carries all)."""
-    qlx = _qlx()
-    live.write_checkpoint(path)
-    m = qlx.DeepQLearningModel(seed=1, precision=qlx.PREC_BF16)
-    m.read_checkpoint(path)
-    assert m.iterations() == live.iterations()
-    for v in range(10):
-        for which in range(3):
-            assert np.array_equal(bits(m.get(v, which)), bits(live.get(v, which)))
-    return m
 
 
 def test_live_model_equals_fresh_model_bit_for_bit(tmp_path):
