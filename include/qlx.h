@@ -117,6 +117,16 @@ int32_t qlx_replay_sample_distinct(qlx_replay* rb, uint64_t seed, uint32_t updat
 /* ReplayBuffer::get_many + batch_to_multi_dim_array: host outputs, any may be NULL. */
 int32_t qlx_replay_get_many(qlx_replay* rb, const uint64_t* indices, uint32_t batch, uint8_t* s /*[B][84][84][4]*/,
                             uint8_t* s_next, uint8_t* actions, float* rewards, uint8_t* dones);
+/* n-step return windows (beyond the reference; DESIGN.md §6 "n-step returns").  The window of the transition at a
+ * logical index runs over the same env's following transitions (n_envs push positions apart) and ends after n_step
+ * of them, at a done, at the newest pushed transition, or where the episode ended without a done (the next slot's
+ * episode step is not this one's + 1).  Per index: returns = sum_{j<m} gamma^j r_j, discounts = gamma^m (fp32, one
+ * rounding per multiply and per add), last_indices = logical index of the window's last transition, terminals = its
+ * done, steps = m.  Host outputs, any may be NULL; synchronises.  n_step 1 gives (reward, gamma, index, done, 1).
+ * QLX_E_INVALID for n_step 0, n_step > QLX_NSTEP_MAX or an index >= len. */
+#define QLX_NSTEP_MAX 32
+int32_t qlx_replay_nstep(qlx_replay* rb, const uint64_t* indices, uint32_t batch, uint32_t n_step, float gamma,
+                         float* returns, float* discounts, uint64_t* last_indices, uint8_t* terminals, uint32_t* steps);
 
 /* ---------------- Q-network (DeepQLearningModel) ---------------- */
 
@@ -194,7 +204,16 @@ typedef struct qlx_params { /* Parameter (self_driving_tf_q_learner.rs:20-67) + 
                                   breakout_environment.rs:203-206); any other value, 0 included, mocks it.
                                   ABI semantics change in round 4: 0 used to select the env's goal; a zero-filled
                                   struct now mocks a goal of 0 (qlx_learner_create warns on stderr) */
+  uint32_t n_step;             /* n-step returns (beyond the reference): y = sum_{j<m} gamma^j r_{t+j} + gamma^m max_a
+                                  Q_target(s_{t+m}), m <= n_step (qlx_replay_nstep's window).  0 and 1 (zero-filled and
+                                  qlx_params_default structs read 0) = the reference's 1-step target, unchanged;
+                                  2..QLX_NSTEP_MAX = n-step; larger values fail in qlx_learner_create.  Breakout learner
+                                  only: qlx_bg_learner_create fails with n_step > 1.  The field fills what was tail
+                                  padding: sizeof(qlx_params) stays 408 */
 } qlx_params;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_params) == 408, "qlx_params ABI size");
+#endif
 
 #define QLX_PREC_F32 0u
 #define QLX_PREC_BF16 1u
@@ -238,8 +257,8 @@ int32_t qlx_learner_set_log_callback(qlx_learner* l, void (*cb)(const char* text
 int32_t qlx_learner_sync(qlx_learner* l);
 int32_t qlx_learner_stats_get(qlx_learner* l, qlx_learner_stats* out);
 /* Outputs of the last vector step (host copies; synchronises): actions/rewards/dones [n_envs],
- * losses [n_updates], indices [n_updates][B], targets [n_updates][B]; any may be NULL. Returns the
- * number of updates of that step in *n_updates. */
+ * losses [n_updates], indices [n_updates][B], targets [n_updates][B] (with n_step > 1 the n-step y); any may be
+ * NULL. Returns the number of updates of that step in *n_updates. */
 int32_t qlx_learner_last(qlx_learner* l, uint8_t* actions, float* rewards, uint8_t* dones, float* losses,
                          uint64_t* indices, float* targets, uint32_t* n_updates);
 /* Prioritized replay state (learner created with QLX_LEARNER_PER): IS weights of the last vector step's batches
@@ -351,7 +370,8 @@ int32_t qlx_bg_model_train(qlx_bg_model* m, const uint8_t* obs, const uint8_t* a
 int32_t qlx_bg_model_load_tf(qlx_bg_model* m, const char* bundle_prefix);
 
 typedef struct qlx_bg_learner qlx_bg_learner;
-/* SelfDrivingQLearner over BallGame (same qlx_params and vector-step semantics as qlx_learner). */
+/* SelfDrivingQLearner over BallGame (same qlx_params and vector-step semantics as qlx_learner).  n-step returns are
+ * the Breakout learner's (this learner keeps a replay of its own): n_step > 1 fails with QLX_E_INVALID. */
 int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learner** out);
 int32_t qlx_bg_learner_destroy(qlx_bg_learner* l);
 int32_t qlx_bg_learner_run(qlx_bg_learner* l, uint64_t n_vector_steps);

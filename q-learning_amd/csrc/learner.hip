@@ -182,6 +182,41 @@ __global__ void k_gather(ReplayView r, const uint64_t* idx, uint32_t B, const ui
   done[b] = r.done[t];
 }
 
+// k_gather for n-step returns (n_step > 1): each sample's window walk (replay_dev.h replay_nstep), then
+//   vcache != null (the memo holds v = max_a Q_target(s') per slot): y = R + v[last] * g, or R where the window ends
+//     in a done - the whole target, no network pass;
+//   vcache == null: s' frame pointers of the window's last transition and R, g, terminal per sample, for the batched
+//     target pass and k_nstep_combine.
+__global__ __launch_bounds__(256) void k_gather_nstep(ReplayView r, const uint64_t* idx, uint32_t B, uint32_t n_step, float gamma,
+                                                      const uint8_t** tab_s, const uint8_t** tab_sn, uint8_t* act, float* ret,
+                                                      float* disc, uint8_t* term, const float* vcache, float* y) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const uint64_t i = idx[b];
+  const uint8_t* f[4];
+  replay_frames(r, i, 0, f);
+  for (int j = 0; j < 4; ++j) tab_s[b * 4 + j] = f[j];
+  act[b] = r.action[(r.total - r.len + i) % r.cap];
+  const NStepWindow w = replay_nstep(r, i, n_step, gamma);
+  if (vcache) {
+    y[b] = w.terminal ? w.R : __fadd_rn(w.R, __fmul_rn(vcache[w.last_p % r.cap], w.g));
+    return;
+  }
+  replay_frames(r, w.last_i, 1, f);
+  for (int j = 0; j < 4; ++j) tab_sn[b * 4 + j] = f[j];
+  ret[b] = w.R;
+  disc[b] = w.g;
+  term[b] = w.terminal ? 1 : 0;
+}
+
+// y = R + v * g (R where the window ended in a done), in place over the bootstrap values v the target pass left in y
+__global__ __launch_bounds__(256) void k_nstep_combine(uint32_t n, const float* ret, const float* disc, const uint8_t* term, float* y) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const float R = ret[b];
+  y[b] = term[b] ? R : __fadd_rn(R, __fmul_rn(y[b], disc[b]));
+}
+
 // s' frame pointers, reward and done of the logical replay indices [i0, i0 + n)
 __global__ void k_slot_tables(ReplayView r, uint64_t i0, uint32_t n, const uint8_t** tab_sn, float* rew, uint8_t* done) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -282,6 +317,15 @@ struct qlx_learner {
   uint32_t ychunk = 0;
   uint64_t ycache_version = 0;         // target->version the memo was computed with
   uint32_t ycap = 0;                   // allocated chunk of d_ytab / d_yrew / d_ydone / d_ytmp (>= ychunk)
+  // n-step returns (qlx_params.n_step > 1).  The memo then holds the bootstrap value v = max_a Q_target(s')
+  // per slot instead of y, and every target pass runs the head with gamma = 1 over zero rewards / dones (d_zero: zero
+  // bytes, read as both) so that it leaves v; R, g and terminal of the sampled windows are kept only without the memo.
+  uint32_t n_step = 1;
+  void* d_zero = nullptr;              // [zcap * 4 bytes] of zeros
+  uint32_t zcap = 0;
+  float* d_nret = nullptr;             // [max_updates][B] R
+  float* d_ndisc = nullptr;            // [max_updates][B] g = gamma^m
+  uint8_t* d_nterm = nullptr;          // [max_updates][B] done of the window's last transition
   qlx::Profiler prof;
   // statistics events (write_checkpoint + learning_update_log, self_driving_tf_q_learner.rs:204-212,226-230)
   uint64_t stats_events = 0;
@@ -310,7 +354,29 @@ static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, cons
   ta.dones = L->d_bdone + o;
   ta.gamma = L->p.gamma;
   ta.y_out = L->d_targets + o;
+  if (L->n_step > 1) {   // the head leaves the bootstrap value: y = 0 + v * 1 (d_tab_sn holds s' of each window's last transition)
+    ta.rewards = static_cast<const float*>(L->d_zero);
+    ta.dones = static_cast<const uint8_t*>(L->d_zero);
+    ta.gamma = 1.0f;
+  }
   model_head(tg, 2, ta, (int)n, s);
+  if (L->n_step > 1) {
+    hipLaunchKernelGGL(k_nstep_combine, dim3((n + 255) / 256), dim3(256), 0, s, n, L->d_nret + o, L->d_ndisc + o, L->d_nterm + o,
+                       L->d_targets + o);
+    QLX_HIP(hipGetLastError());
+  }
+}
+
+// at least n * 4 zero bytes in d_zero (n-step: the zero rewards / dones of the bootstrap passes)
+static void zero_reserve(qlx_learner* L, uint32_t n) {
+  if (n <= L->zcap) return;
+  QLX_HIP(hipStreamSynchronize(L->stream));
+  if (L->d_zero) QLX_HIP(hipFree(L->d_zero));
+  L->d_zero = nullptr;
+  L->zcap = 0;
+  QLX_HIP(hipMalloc(&L->d_zero, (size_t)n * 4));
+  QLX_HIP(hipMemsetAsync(L->d_zero, 0, (size_t)n * 4, L->stream));
+  L->zcap = n;
 }
 
 // Target memo.  With the target net frozen, y = r + gamma * max_a Q_target(s') (or r if done) of a transition is a
@@ -322,7 +388,11 @@ static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, cons
 // The per-step fill runs chunks of at most ychunk (= min(n_envs, kF32FwdChunk)) transitions; the rebuild of every live slot
 // after a target-weight write runs kF32FwdChunk-sized chunks, growing the memo's chunk buffers and the target workspace
 // on first use (with n_envs = 1 and a 1M replay, chunks of n_envs would be 1M launches of each kernel).
+// n-step returns (n_step > 1): the memo holds v = max_a Q_target(s') per slot instead - the same head at gamma = 1 over zero
+// rewards / dones, as qlx_model_batch_max_q runs it - and the gather combines it with the window's R and gamma^m
+// (k_gather_nstep).  v is as fixed a function of the slot as y is, so the fill and the rebuild are the same.
 static void ycache_reserve(qlx_learner* L, uint32_t chunk) {
+  if (L->n_step > 1) zero_reserve(L, chunk);
   if (chunk <= L->ycap) return;
   QLX_HIP(hipStreamSynchronize(L->stream));
   for (void* p : {(void*)L->d_ytab, (void*)L->d_yrew, (void*)L->d_ydone, (void*)L->d_ytmp})
@@ -351,6 +421,11 @@ static void ycache_fill(qlx_learner* L, uint64_t i0, uint64_t n, uint32_t chunk)
     ta.dones = L->d_ydone;
     ta.gamma = L->p.gamma;
     ta.y_out = L->d_ytmp;
+    if (L->n_step > 1) {
+      ta.rewards = static_cast<const float*>(L->d_zero);
+      ta.dones = static_cast<const uint8_t*>(L->d_zero);
+      ta.gamma = 1.0f;
+    }
     model_head(tg, 2, ta, (int)m, s);
     hipLaunchKernelGGL(k_slot_put, dim3((m + 255) / 256), dim3(256), 0, s, rv, i0 + c0, m, L->d_ytmp, L->d_ycache);
     QLX_HIP(hipGetLastError());
@@ -364,8 +439,14 @@ static void learner_targets(qlx_learner* L, uint32_t U) {
   const ReplayView rv = replay_view(L->rb);
   {
     ProfScope ps(&L->prof, "gather", s);
-    hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), dim3(256), 0, s, rv, L->d_idx, n, L->d_tab_s, L->d_tab_sn, L->d_bact,
-                       L->d_brew, L->d_bdone, L->ycache ? L->d_ycache : nullptr, L->d_targets);
+    if (L->n_step > 1) {
+      hipLaunchKernelGGL(k_gather_nstep, dim3((n + 255) / 256), dim3(256), 0, s, rv, L->d_idx, n, L->n_step, L->p.gamma, L->d_tab_s,
+                         L->d_tab_sn, L->d_bact, L->d_nret, L->d_ndisc, L->d_nterm, L->ycache ? L->d_ycache : nullptr, L->d_targets);
+      QLX_HIP(hipGetLastError());
+    } else {
+      hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), dim3(256), 0, s, rv, L->d_idx, n, L->d_tab_s, L->d_tab_sn, L->d_bact,
+                         L->d_brew, L->d_bdone, L->ycache ? L->d_ycache : nullptr, L->d_targets);
+    }
   }
   debug_sync(s, "gather");
   if (L->ycache) return;
@@ -589,6 +670,7 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
     QLX_CHECK(p->qnet_precision == QLX_PREC_F32 || p->qnet_precision == QLX_PREC_BF16, QLX_E_INVALID, "unknown qnet_precision");
     QLX_CHECK(p->qnet_precision == QLX_PREC_BF16 || p->batch_size <= (uint32_t)kF32FwdChunk, QLX_E_INVALID,
               "fp32 batch_size above the forward chunk");
+    QLX_CHECK(p->n_step <= QLX_NSTEP_MAX, QLX_E_INVALID, "n_step above QLX_NSTEP_MAX");
     QLX_CHECK(!(p->flags & QLX_LEARNER_PER) || (std::isfinite(p->per_alpha) && std::isfinite(p->per_beta) && std::isfinite(p->per_eps) &&
                                                  p->per_alpha >= 0.0f && p->per_beta >= 0.0f && p->per_eps > 0.0f),
               QLX_E_INVALID, "prioritized replay needs finite alpha >= 0, beta >= 0, eps > 0");
@@ -607,6 +689,7 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
       L->N = p->n_envs;
       L->B = p->batch_size;
       L->rank = (int)p->rank;
+      L->n_step = std::max<uint32_t>(p->n_step, 1);
       QLX_HIP(hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
       int32_t st;
       st = qlx_env_create(QLX_ENV_BREAKOUT, L->N, p->env_seed, device, &L->env);
@@ -676,6 +759,12 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
         L->ycache_version = L->target->version;
       } else {
         model_workspace(L->target, (int)(L->max_updates * B));   // batched target pass (learner_targets)
+        if (L->n_step > 1) {
+          zero_reserve(L, (uint32_t)UB);
+          QLX_HIP(hipMalloc(&L->d_nret, UB * sizeof(float)));
+          QLX_HIP(hipMalloc(&L->d_ndisc, UB * sizeof(float)));
+          QLX_HIP(hipMalloc(&L->d_nterm, UB));
+        }
       }
       if (L->ddqn) model_workspace(L->online, (int)(L->max_updates * B));   // + the online pass over s'
       if (L->per) L->prio.init(p->history_buffer_len, UB);
@@ -705,7 +794,8 @@ int32_t qlx_learner_destroy(qlx_learner* L) {
     void* ptrs[] = {L->d_actions, L->d_rewards, L->d_dones, L->d_reset, (void*)L->d_obs_table, L->d_eps, L->d_ep_reward,
                     L->d_hist, L->d_book, L->d_idx, (void*)L->d_tab_s, (void*)L->d_tab_sn, L->d_bact, L->d_brew,
                     L->d_bdone, L->d_losses, L->d_targets, L->d_gsum, L->d_gmin, L->d_ycache, (void*)L->d_ytab,
-                    L->d_yrew, L->d_ydone, L->d_ytmp, L->d_sparsity};
+                    L->d_yrew, L->d_ydone, L->d_ytmp, L->d_sparsity, L->d_zero, L->d_nret,
+                    L->d_ndisc, L->d_nterm};
     for (void* p : ptrs) (void)hipFree(p);
     for (void* p : {(void*)L->h_book, (void*)L->h_gsum, (void*)L->h_sparsity})
       if (p) (void)hipHostFree(p);

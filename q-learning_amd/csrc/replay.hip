@@ -126,6 +126,19 @@ __global__ void k_replay_meta(ReplayView r, const uint64_t* idx, uint32_t B, uin
   d[b] = r.done[t];
 }
 
+// n-step windows of a list of logical indices (replay_dev.h replay_nstep), one thread per sample; outputs may be null
+__global__ __launch_bounds__(256) void k_replay_nstep(ReplayView r, const uint64_t* idx, uint32_t B, uint32_t n_step, float gamma,
+                                                      float* ret, float* disc, uint64_t* last, uint8_t* term, uint32_t* steps) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const NStepWindow w = replay_nstep(r, idx[b], n_step, gamma);
+  if (ret) ret[b] = w.R;
+  if (disc) disc[b] = w.g;
+  if (last) last[b] = w.last_i;
+  if (term) term[b] = w.terminal ? 1 : 0;
+  if (steps) steps[b] = w.m;
+}
+
 ReplayView replay_view(const qlx_replay* rb) {
   ReplayView v;
   v.frames = rb->d_frames; v.action = rb->d_action; v.reward = rb->d_reward; v.done = rb->d_done;
@@ -288,6 +301,42 @@ int32_t qlx_replay_get_many(qlx_replay* r, const uint64_t* indices, uint32_t B, 
     if (dones) QLX_HIP(hipMemcpyAsync(dones, d_d, B, hipMemcpyDeviceToHost, r->stream));
     QLX_HIP(hipStreamSynchronize(r->stream));
     (void)hipFree(d_idx); (void)hipFree(d_out); (void)hipFree(d_r); (void)hipFree(d_a); (void)hipFree(d_d);
+  });
+}
+
+int32_t qlx_replay_nstep(qlx_replay* r, const uint64_t* indices, uint32_t B, uint32_t n_step, float gamma, float* returns,
+                         float* discounts, uint64_t* last_indices, uint8_t* terminals, uint32_t* steps) {
+  return guard([&] {
+    QLX_CHECK(r && indices && B > 0, QLX_E_INVALID, "null argument");
+    QLX_CHECK(n_step >= 1 && n_step <= QLX_NSTEP_MAX, QLX_E_INVALID, "n_step must be in 1..QLX_NSTEP_MAX");
+    for (uint32_t b = 0; b < B; ++b) QLX_CHECK(indices[b] < r->len(), QLX_E_INVALID, "index out of range");
+    QLX_HIP(hipSetDevice(r->device));
+    QLX_HIP(hipDeviceSynchronize());
+    // one allocation: idx u64 [B] | last u64 [B] | ret f32 [B] | disc f32 [B] | steps u32 [B] | term u8 [B]
+    uint8_t* d = nullptr;
+    QLX_HIP(hipMalloc(&d, (size_t)B * 29));
+    uint64_t* d_idx = reinterpret_cast<uint64_t*>(d);
+    uint64_t* d_last = d_idx + B;
+    float* d_ret = reinterpret_cast<float*>(d_last + B);
+    float* d_disc = d_ret + B;
+    uint32_t* d_steps = reinterpret_cast<uint32_t*>(d_disc + B);
+    uint8_t* d_term = reinterpret_cast<uint8_t*>(d_steps + B);
+    try {
+      QLX_HIP(hipMemcpyAsync(d_idx, indices, B * sizeof(uint64_t), hipMemcpyHostToDevice, r->stream));
+      hipLaunchKernelGGL(k_replay_nstep, dim3((B + 255) / 256), dim3(256), 0, r->stream, replay_view(r), d_idx, B, n_step, gamma,
+                         d_ret, d_disc, d_last, d_term, d_steps);
+      QLX_HIP(hipGetLastError());
+      if (returns) QLX_HIP(hipMemcpyAsync(returns, d_ret, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+      if (discounts) QLX_HIP(hipMemcpyAsync(discounts, d_disc, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+      if (last_indices) QLX_HIP(hipMemcpyAsync(last_indices, d_last, B * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+      if (terminals) QLX_HIP(hipMemcpyAsync(terminals, d_term, B, hipMemcpyDeviceToHost, r->stream));
+      if (steps) QLX_HIP(hipMemcpyAsync(steps, d_steps, B * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+      QLX_HIP(hipStreamSynchronize(r->stream));
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    (void)hipFree(d);
   });
 }
 

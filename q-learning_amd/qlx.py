@@ -70,8 +70,10 @@ class Params(C.Structure):
         ("stats_after_steps", C.c_uint64),
         ("checkpoint_file", C.c_char * 256),
         ("episode_reward_goal", C.c_float),
+        ("n_step", C.c_uint32),   # n-step returns: 0 / 1 = the reference's 1-step target, 2..NSTEP_MAX = n-step
     ]
 
+NSTEP_MAX = 32  # QLX_NSTEP_MAX
 DOUBLE_DQN = 1
 PER = 2
 PREC_F32 = 0    # QLX_PREC_F32: the reference's fp32 arithmetic (bit-exact against the oracle)
@@ -93,7 +95,7 @@ def Parameter(**kw):
                history_buffer_len=1_000_000, update_after_actions=4, target_sync_steps=0,
                episode_reward_history_buffer_len=100, n_envs=1, batch_size=32, env_seed=0x51A5EED, learner_seed=1,
                init_seed=2, rank=0, flags=0, per_alpha=0.6, per_beta=0.4, per_eps=1e-6, qnet_precision=PREC_F32,
-               stats_after_steps=25_000, checkpoint_file=b"", episode_reward_goal=float("nan"))
+               stats_after_steps=25_000, checkpoint_file=b"", episode_reward_goal=float("nan"), n_step=1)
     for k, v in kw.items():
         if k == "checkpoint_file" and isinstance(v, str):
             v = v.encode()
@@ -126,6 +128,7 @@ def lib():
         "qlx_replay_push": ([vp, vp, vp, vp, vp], i32),
         "qlx_replay_sample_distinct": ([vp, u64, u32, u32, u32, vp], i32),
         "qlx_replay_get_many": ([vp, vp, u32, vp, vp, vp, vp, vp], i32),
+        "qlx_replay_nstep": ([vp, vp, u32, u32, f32, vp, vp, vp, vp, vp], i32),
         "qlx_model_create": ([i32, u64, i32, C.POINTER(vp)], i32), "qlx_model_destroy": ([vp], i32),
         "qlx_model_num_vars": ([], i32), "qlx_model_var_size": ([i32], C.c_int64), "qlx_model_hparams": ([vp], i32),
         "qlx_bg_model_hparams": ([vp], i32),
@@ -358,6 +361,20 @@ class ReplayBuffer:
         d = np.zeros(B, np.uint8)
         _check(lib().qlx_replay_get_many(self.h, _p(idx), B, _p(s), _p(sn), _p(a), _p(r), _p(d)))
         return dict(state=s, state_next=sn, action=a, reward=r, done=d.astype(bool))
+
+    def nstep(self, indices, n_step, gamma):
+        """n-step return windows of the transitions at `indices` (qlx_replay_nstep): returns = sum_{j<m} gamma^j r_j,
+        discounts = gamma^m, last_indices = logical index of each window's last transition, terminals = its done,
+        steps = m <= n_step."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        B = idx.size
+        ret = np.zeros(B, np.float32)
+        disc = np.zeros(B, np.float32)
+        last = np.zeros(B, np.uint64)
+        term = np.zeros(B, np.uint8)
+        steps = np.zeros(B, np.uint32)
+        _check(lib().qlx_replay_nstep(self.h, _p(idx), B, n_step, gamma, _p(ret), _p(disc), _p(last), _p(term), _p(steps)))
+        return dict(returns=ret, discounts=disc, last_indices=last, terminals=term.astype(bool), steps=steps)
 
 
 class DeepQLearningModel:
