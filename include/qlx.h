@@ -300,6 +300,54 @@ int32_t qlx_learner_profile_get(qlx_learner* l, const char* name, double* total_
                                 uint64_t* launches);
 int32_t qlx_learner_profile_names(qlx_learner* l, char* buf, size_t cap);
 
+/* ---------------- Policy evaluation (beyond the reference) ----------------
+ * n_envs fresh Breakout envs play episodes_per_env episodes each with a model's current weights, greedily or at a
+ * fixed epsilon, entirely on the GPU; nearest reference interfaces: render_ballgame_cases.rs (a trained model replayed
+ * over initial states) and learn_episode's acting branch (self_driving_tf_q_learner.rs:153-167).  Per vector step
+ * t = 0, 1, ... and env e still playing: q = Q(obs_e); the action is random (uniform over 3, word 2 of stream
+ * (policy_seed, e, t, purpose 8)) when epsilon > 0 and epsilon > the f64 from words 0-1 of that stream, else the first
+ * argmax of q; return and max_a q accumulate in fp32 in step order; an episode ends at done or after
+ * max_steps_per_episode steps, is recorded, and the env resets; an env retires after its last episode (it is still
+ * stepped with action 0, nothing of it is counted).  The Q-net forward runs over the envs still playing only, as
+ * counted at the last poll (DESIGN.md "Policy evaluation"). */
+#define QLX_EVAL_MAX_ENVS 8192            /* one forward chunk (kF32FwdChunk) */
+typedef struct qlx_eval_config {
+  uint32_t n_envs;                  /* 1..QLX_EVAL_MAX_ENVS */
+  uint32_t episodes_per_env;        /* K >= 1; n_envs * K <= 1<<24 */
+  uint64_t max_steps_per_episode;   /* >= 1; an episode ends without done at this many steps, as in the learner */
+  double   epsilon;                 /* finite, 0..1; 0 = greedy */
+  uint64_t env_seed;                /* ball launch stream, env ids 0..n_envs-1, reset_count from 0 each run */
+  uint64_t policy_seed;             /* epsilon draws */
+  uint32_t poll_steps;              /* host reads the active count every this many vector steps; 0 = the default */
+  uint32_t flags;                   /* must be 0 */
+} qlx_eval_config;
+
+typedef struct qlx_eval_summary {
+  uint64_t episodes, env_steps, vector_steps, forward_samples, terminal_episodes;
+  uint64_t action_counts[3];
+  double   mean_return, mean_length, mean_max_q;   /* mean_max_q = sum of max_a q over all counted steps / env_steps */
+  float    min_return, max_return;
+} qlx_eval_summary;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_eval_config) == 48, "qlx_eval_config ABI size");
+static_assert(sizeof(qlx_eval_summary) == 96, "qlx_eval_summary ABI size");
+#endif
+
+typedef struct qlx_evaluator qlx_evaluator;
+/* Argument errors (QLX_E_INVALID, the field named in qlx_last_error) are reported before the device is touched. */
+int32_t qlx_evaluator_create(const qlx_eval_config* cfg, int32_t device, qlx_evaluator** out);
+int32_t qlx_evaluator_destroy(qlx_evaluator* ev);
+/* plays K episodes per env with m's current weights (either arch) on m's stream; m is not modified; synchronises.
+ * Every run starts from the same env and draw state: equal config and weights give equal results.  vector_steps = the
+ * first multiple of poll_steps at which no env was playing; forward_samples = the rows the Q-net forward ran over. */
+int32_t qlx_evaluator_run(qlx_evaluator* ev, qlx_model* m, qlx_eval_summary* out);
+/* records of the last run, [n_envs][K] env-major, any may be NULL: return, length, ended by done, sum of max_a q */
+int32_t qlx_evaluator_episodes(qlx_evaluator* ev, float* returns, uint32_t* lengths, uint8_t* terminals, float* max_q_sums);
+qlx_env* qlx_evaluator_env(qlx_evaluator* ev);
+/* evaluates the learner's online model on the learner's stream with a temporary evaluator; the learner's own
+ * env, replay, counters, RNG positions, memo and profiler scopes are untouched.  Local to the rank (no collective). */
+int32_t qlx_learner_evaluate(qlx_learner* l, const qlx_eval_config* cfg, qlx_eval_summary* out);
+
 /* ---------------- DBSCAN over f32 (src/ql/src/util/dbscan.rs:209-341) ----------------
  * cluster_analysis(values, max_neighbor_distance, core_point_min_neighbors) with Distance = |a - b|, exact, in
  * O(n log n): labels[i] = cluster position (clusters ordered by lowest member index, as the reference returns

@@ -1087,6 +1087,22 @@ static void learner_step_full(qlx_learner* L, bool train) {
 extern "C" {
 
 qlx_env* qlx_learner_env(qlx_learner* L) { return L ? L->env : nullptr; }
+
+// Policy evaluation of the online model (evaluator.hip) between vector steps: a temporary evaluator with an env batch of
+// its own runs on the learner's stream (the model's), so it is ordered after the steps enqueued so far; nothing of the
+// learner but the online model's workspace (regrown when cfg->n_envs is above its batch) is touched.
+int32_t qlx_learner_evaluate(qlx_learner* L, const qlx_eval_config* cfg, qlx_eval_summary* out) {
+  return guard([&] {
+    QLX_CHECK(L && cfg && out, QLX_E_INVALID, "null argument");
+    qlx_evaluator* ev = nullptr;
+    int32_t st = qlx_evaluator_create(cfg, L->device, &ev);
+    QLX_CHECK(st == QLX_OK, st, qlx_last_error());
+    st = qlx_evaluator_run(ev, L->online, out);
+    const std::string msg = st == QLX_OK ? "" : qlx_last_error();
+    qlx_evaluator_destroy(ev);
+    QLX_CHECK(st == QLX_OK, st, msg);
+  });
+}
 qlx_replay* qlx_learner_replay(qlx_learner* L) { return L ? L->rb : nullptr; }
 qlx_model* qlx_learner_model(qlx_learner* L, int32_t which) { return L ? (which == 0 ? L->online : L->target) : nullptr; }
 

@@ -88,6 +88,36 @@ class LearnerStats(C.Structure):
         ("epsilon", C.c_double), ("running_reward", C.c_float), ("last_loss", C.c_float)]
 
 
+class EvalConfig(C.Structure):
+    """qlx_eval_config (policy evaluation, beyond the reference)"""
+    _fields_ = [("n_envs", C.c_uint32), ("episodes_per_env", C.c_uint32), ("max_steps_per_episode", C.c_uint64),
+                ("epsilon", C.c_double), ("env_seed", C.c_uint64), ("policy_seed", C.c_uint64),
+                ("poll_steps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class EvalSummary(C.Structure):
+    """qlx_eval_summary"""
+    _fields_ = [(k, C.c_uint64) for k in ("episodes", "env_steps", "vector_steps", "forward_samples",
+                                          "terminal_episodes")] + [
+        ("action_counts", C.c_uint64 * 3), ("mean_return", C.c_double), ("mean_length", C.c_double),
+        ("mean_max_q", C.c_double), ("min_return", C.c_float), ("max_return", C.c_float)]
+
+
+EVAL_MAX_ENVS = 8192   # QLX_EVAL_MAX_ENVS
+
+
+def _eval_config(n_envs, episodes_per_env=1, max_steps_per_episode=10_000, epsilon=0.0, env_seed=0x51A5EED,
+                 policy_seed=1, poll_steps=0, flags=0):
+    return EvalConfig(n_envs=n_envs, episodes_per_env=episodes_per_env, max_steps_per_episode=max_steps_per_episode,
+                      epsilon=epsilon, env_seed=env_seed, policy_seed=policy_seed, poll_steps=poll_steps, flags=flags)
+
+
+def _eval_summary(s):
+    d = {k: getattr(s, k) for k, _ in EvalSummary._fields_}
+    d["action_counts"] = np.array(list(s.action_counts), np.uint64)
+    return d
+
+
 def Parameter(**kw):
     """Parameter::default() with overrides (self_driving_tf_q_learner.rs:50-67)."""
     p = Params(gamma=0.99, lowest_episode_reward_goal_threshold_pct=0.9, epsilon_max=1.0, epsilon_min=0.1,
@@ -156,6 +186,10 @@ def lib():
         "qlx_bg_learner_episode_rewards": ([vp, vp, u64, C.POINTER(u64)], i32),
         "qlx_learner_update_log": ([vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)], i32),
         "qlx_bg_learner_update_log": ([vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)], i32),
+        "qlx_evaluator_create": ([C.POINTER(EvalConfig), i32, C.POINTER(vp)], i32), "qlx_evaluator_destroy": ([vp], i32),
+        "qlx_evaluator_run": ([vp, vp, C.POINTER(EvalSummary)], i32),
+        "qlx_evaluator_episodes": ([vp, vp, vp, vp, vp], i32), "qlx_evaluator_env": ([vp], vp),
+        "qlx_learner_evaluate": ([vp, C.POINTER(EvalConfig), C.POINTER(EvalSummary)], i32),
         "qlx_dbscan_f32": ([vp, u64, C.c_float, u64, vp, C.POINTER(u64)], i32),
         "qlx_dbscan_f32_format": ([vp, u64, C.c_float, u64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)], i32),
         "qlx_sumtree_create": ([u64, i32, C.POINTER(vp)], i32), "qlx_sumtree_destroy": ([vp], i32),
@@ -477,6 +511,43 @@ class DeepQLearningModel:
         _check(lib().qlx_model_read_checkpoint(self.h, path.encode()))
 
 
+class Evaluator:
+    """Policy evaluation on the GPU (qlx_evaluator, beyond the reference): n_envs fresh Breakout envs play
+    episodes_per_env episodes each with a model's current weights, greedily (epsilon 0) or at a fixed epsilon; the
+    Q-net forward runs over the envs still playing only (DESIGN.md "Policy evaluation")."""
+
+    def __init__(self, n_envs, episodes_per_env=1, max_steps_per_episode=10_000, epsilon=0.0, env_seed=0x51A5EED,
+                 policy_seed=1, poll_steps=0, device=0, flags=0):
+        self.h = None
+        self.config = _eval_config(n_envs, episodes_per_env, max_steps_per_episode, epsilon, env_seed, policy_seed,
+                                   poll_steps, flags)
+        h = C.c_void_p()
+        _check(lib().qlx_evaluator_create(C.byref(self.config), device, C.byref(h)))
+        self.h = h.value
+        self.environment = BreakoutEnvironment(handle=lib().qlx_evaluator_env(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().qlx_evaluator_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def run(self, model):
+        """K episodes per env with `model`'s current weights (not modified); the summary as a dict"""
+        s = EvalSummary()
+        _check(lib().qlx_evaluator_run(self.h, model.h, C.byref(s)))
+        return _eval_summary(s)
+
+    def episodes(self):
+        """records of the last run, each [n_envs][K]: returns, lengths, terminals (ended by done), max_q_sums"""
+        shape = (self.config.n_envs, self.config.episodes_per_env)
+        ret, length = np.zeros(shape, np.float32), np.zeros(shape, np.uint32)
+        term, qs = np.zeros(shape, np.uint8), np.zeros(shape, np.float32)
+        _check(lib().qlx_evaluator_episodes(self.h, _p(ret), _p(length), _p(term), _p(qs)))
+        return dict(returns=ret, lengths=length, terminals=term.astype(bool), max_q_sums=qs)
+
+
 class SelfDrivingQLearner(_LearningStats):
     """SelfDrivingQLearner with n parallel envs on one GPU (vector-step generalisation)."""
     _n_actions = 3
@@ -569,6 +640,14 @@ class SelfDrivingQLearner(_LearningStats):
         out = np.zeros(8, np.float64)
         _check(lib().qlx_learner_frame_sparsity(self.h, _p(out)))
         return {"train": out[:4].tolist(), "act": out[4:].tolist()}
+
+    def evaluate(self, **cfg):
+        """Policy evaluation of the online model between vector steps (Evaluator's arguments but `device`); the
+        learner's env, replay, counters and draws are untouched"""
+        c = _eval_config(**cfg)
+        s = EvalSummary()
+        _check(lib().qlx_learner_evaluate(self.h, C.byref(c), C.byref(s)))
+        return _eval_summary(s)
 
     def dist_init(self, world, rank, uid):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(uid))

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""A/B measurement of the policy evaluator's active-env compaction (DESIGN.md "Policy evaluation").
+
+Shape: 1,024 envs, one episode each, max 10,000 steps per episode, fp32 and bf16; two models: the zero-weight action-0
+model (Q = b4 = [1, 0, 0]: short episodes with a long tail) and a seed-2 random-init model.  Evaluator.run is timed
+with a host clock around the synchronising call, after a warm-up run.  QLX_EVAL_COMPACT is read when an evaluator is
+created, so the two arms are two evaluators of one process, run alternately (on, off, on, off, ...); the poll_steps
+sweep alternates its values the same way.  One JSON line per (precision, model, arm) with every wall time, and one
+summary line per comparison; nothing is asserted.
+
+  python scripts/eval_bench.py [--pairs 5] [--envs 1024] [--max-steps 10000] [--precisions f32,bf16]
+                               [--models zero,random] [--polls 1,8,32] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "q-learning_amd"))
+import qlx  # noqa: E402
+
+
+def make_model(kind, precision):
+    if kind == "random":
+        return qlx.DeepQLearningModel(seed=2, precision=precision)
+    m = qlx.DeepQLearningModel(seed=1, precision=precision)
+    for v, shape in enumerate(qlx.VAR_SHAPES):
+        m.set(v, np.zeros(shape, np.float32))
+    m.set(9, np.float32([1, 0, 0]))
+    return m
+
+
+def make_evaluator(compact, poll, args):
+    os.environ["QLX_EVAL_COMPACT"] = "1" if compact else "0"   # read once, at create
+    try:
+        return qlx.Evaluator(args.envs, episodes_per_env=1, max_steps_per_episode=args.max_steps, poll_steps=poll)
+    finally:
+        del os.environ["QLX_EVAL_COMPACT"]
+
+
+def timed(ev, model):
+    t0 = time.perf_counter()
+    s = ev.run(model)
+    return time.perf_counter() - t0, s
+
+
+def alternate(arms, model, pairs):
+    """arms: {name: evaluator}; a warm-up run each, then `pairs` rounds of one run per arm in turn"""
+    out = {k: dict(wall_s=[]) for k in arms}
+    for k, ev in arms.items():
+        _, s = timed(ev, model)
+        out[k].update(vector_steps=int(s["vector_steps"]), forward_samples=int(s["forward_samples"]),
+                      env_steps=int(s["env_steps"]), mean_return=s["mean_return"], mean_length=s["mean_length"])
+    for _ in range(pairs):
+        for k, ev in arms.items():
+            out[k]["wall_s"].append(timed(ev, model)[0])
+    for k, o in out.items():
+        w = o["wall_s"]
+        o.update(median_s=statistics.median(w), min_s=min(w), max_s=max(w),
+                 env_steps_per_s=o["env_steps"] / statistics.median(w))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--max-steps", type=int, default=10_000)
+    ap.add_argument("--precisions", default="f32,bf16")
+    ap.add_argument("--models", default="zero,random")
+    ap.add_argument("--polls", default="1,8,32")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    sink = open(args.out, "w") if args.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    polls = [int(p) for p in args.polls.split(",") if p]
+    for prec_name in args.precisions.split(","):
+        precision = qlx.PREC_BF16 if prec_name == "bf16" else qlx.PREC_F32
+        for kind in args.models.split(","):
+            model = make_model(kind, precision)
+            # compaction on / off at the default poll_steps
+            arms = {"compact": make_evaluator(True, 0, args), "full": make_evaluator(False, 0, args)}
+            res = alternate(arms, model, args.pairs)
+            for ev in arms.values():
+                ev.close()
+            for k, o in res.items():
+                emit(dict(kind="ab", precision=prec_name, model=kind, arm=k, **o))
+            on, off = res["compact"], res["full"]
+            emit(dict(kind="ab_summary", precision=prec_name, model=kind, speedup_median=off["median_s"] / on["median_s"],
+                      compact_range_s=[on["min_s"], on["max_s"]], full_range_s=[off["min_s"], off["max_s"]],
+                      separated=on["max_s"] < off["min_s"], forward_samples_ratio=on["forward_samples"] / off["forward_samples"]))
+            # poll_steps sweep, compaction on
+            if polls:
+                arms = {f"poll{p}": make_evaluator(True, p, args) for p in polls}
+                res = alternate(arms, model, args.pairs)
+                for ev in arms.values():
+                    ev.close()
+                for k, o in res.items():
+                    emit(dict(kind="poll", precision=prec_name, model=kind, arm=k, **o))
+            model.close()
+    if sink:
+        sink.close()
+
+
+if __name__ == "__main__":
+    main()
