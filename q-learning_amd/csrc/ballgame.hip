@@ -9,8 +9,11 @@
 //                             :71-85 (Conv2D 32 2x2 'same' relu, Conv2D 32 1x1 relu, Dense 512 relu, Dense 5;
 //                             MSE of q_a = sum(Q(s) * one_hot(a)); Adam(2.5e-4, clipnorm 1))
 //   learner                   self_driving_tf_q_learner.rs:141-233, vectorised as the Breakout learner
-// The net is 0.33 MFLOP per sample: fp32 SIMT kernels (LDS-tiled GEMM for the dense layers), every reduction in
-// a fixed order.  Tolerances against the fp32 oracle are stated in tests/test_gpu_ballgame.py.
+// The net is 0.33 MFLOP per sample: SIMT kernels on fp32 data (LDS-tiled GEMM for the dense layers), every reduction in
+// a fixed order and accumulated in double, rounded to fp32 once where it is stored - the oracle's arithmetic
+// (oracle/ballgame_ref.cpp).  fp32 accumulation left ~3e-9 on a weight-gradient element that nearly cancels, and the
+// first Adam steps move a weight by lr g / (|g| + 3.2e-6): 79 times that (tests/test_gpu_ballgame_shapes.py, B = 63).
+// Tolerances against the oracle are stated in tests/test_gpu_ballgame.py.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -138,22 +141,22 @@ __global__ __launch_bounds__(288) void k_conv_fwd(const uint8_t* obs, int B, con
   if (t < kObs) x[t] = (float)obs[(size_t)b * kObs + t];
   __syncthreads();
   const float* k0 = prm + var_off(0);
-  float s = 0.0f;
+  double s = 0.0;
   for (int di = 0; di < 2; ++di)
     for (int dj = 0; dj < 2; ++dj)
       if (i + di < 3 && j + dj < 3)
-        for (int c = 0; c < 4; ++c) s += x[((i + di) * 3 + j + dj) * 4 + c] * k0[((di * 2 + dj) * 4 + c) * 32 + o];
-  const float v1 = fmaxf(s + prm[var_off(1) + o], 0.0f);
+        for (int c = 0; c < 4; ++c) s += (double)x[((i + di) * 3 + j + dj) * 4 + c] * (double)k0[((di * 2 + dj) * 4 + c) * 32 + o];
+  const float v1 = fmaxf((float)s + prm[var_off(1) + o], 0.0f);
   s1[t] = v1;
   a1[(size_t)b * 288 + t] = v1;
   __syncthreads();
   const float* k1 = prm + var_off(2);
-  float s2 = 0.0f;
-  for (int c = 0; c < 32; ++c) s2 += s1[p * 32 + c] * k1[c * 32 + o];
-  a2[(size_t)b * 288 + t] = fmaxf(s2 + prm[var_off(3) + o], 0.0f);
+  double s2 = 0.0;
+  for (int c = 0; c < 32; ++c) s2 += (double)s1[p * 32 + c] * (double)k1[c * 32 + o];
+  a2[(size_t)b * 288 + t] = fmaxf((float)s2 + prm[var_off(3) + o], 0.0f);
 }
 
-// C[M][N] = op(A)[M][K] op(B)[K][N] in fp32, 64 x 64 tiles, 256 threads x 4 x 4 outputs, k through LDS in
+// C[M][N] = op(A)[M][K] op(B)[K][N] on fp32 data with double accumulators, 64 x 64 tiles, 256 threads x 4 x 4 outputs, k through LDS in
 // steps of 16 (fixed order per output).  A(m, k) = TA ? A[k lda + m] : A[m lda + k];  B(k, n) = TB ?
 // B[n ldb + k] : B[k ldb + n].  EPI 0: store; 1: + bias[n], ReLU; 2: * (mask[m ldc + n] > 0).
 template <bool TA, bool TB, int EPI>
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(int M, int N, int K, const flo
   __shared__ float sb[16][64 + 1];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int m0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
-  float acc[4][4] = {};
+  double acc[4][4] = {};   // a product of two floats is exact in double: one rounding per output, at the store
   for (int k0 = 0; k0 < K; k0 += 16) {
     for (int i = tid; i < 16 * 64; i += 256) {
       const int kk = i >> 6, mm = i & 63;
@@ -176,9 +179,9 @@ __global__ __launch_bounds__(256) void k_gemm_f32(int M, int N, int K, const flo
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) {
-      float av[4], bv[4];
+      double av[4], bv[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { av[r] = sa[kk][ty * 4 + r]; bv[r] = sb[kk][tx * 4 + r]; }
+      for (int r = 0; r < 4; ++r) { av[r] = (double)sa[kk][ty * 4 + r]; bv[r] = (double)sb[kk][tx * 4 + r]; }
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(int M, int N, int K, const flo
     for (int c = 0; c < 4; ++c) {
       const int m = m0 + ty * 4 + r, n = n0 + tx * 4 + c;
       if (m >= M || n >= N) continue;
-      float v = acc[r][c];
+      float v = (float)acc[r][c];
       if (EPI == 1) v = fmaxf(v + aux[n], 0.0f);
       if (EPI == 2) v = aux[(size_t)m * ldc + n] > 0.0f ? v : 0.0f;
       C[(size_t)m * ldc + n] = v;
@@ -235,18 +238,18 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs H) {
   if (b >= H.B) return;
   const float* w = H.prm + var_off(6);
   const float* a = H.a3 + (size_t)b * 512;
-  float s[kA] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  double s[kA] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int n = lane; n < 512; n += 64) {
-    const float x = a[n];
+    const double x = (double)a[n];
 #pragma unroll
-    for (int k = 0; k < kA; ++k) s[k] += x * w[n * kA + k];
+    for (int k = 0; k < kA; ++k) s[k] += x * (double)w[n * kA + k];
   }
 #pragma unroll
   for (int k = 0; k < kA; ++k)
     for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
   float q[kA];
 #pragma unroll
-  for (int k = 0; k < kA; ++k) q[k] = s[k] + H.prm[var_off(7) + k];
+  for (int k = 0; k < kA; ++k) q[k] = (float)s[k] + H.prm[var_off(7) + k];
   if (lane == 0 && H.q)
     for (int k = 0; k < kA; ++k) H.q[(size_t)b * kA + k] = q[k];
   if (MODE == 1 && lane == 0) {
@@ -283,14 +286,14 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs H) {
 // out[j] = sum_r A[r][j] (rows x cols, row stride lda); column j of block blockIdx.x * 64 + (t & 63), 4 row
 // phases combined in order.  scale multiplies the result (loss = sum / B).
 __global__ __launch_bounds__(256) void k_colsum(const float* A, int rows, int cols, int lda, float scale, float* out) {
-  __shared__ float part[4][64];
+  __shared__ double part[4][64];
   const int t = threadIdx.x, j = blockIdx.x * 64 + (t & 63), ph = t >> 6;
-  float s = 0.0f;
+  double s = 0.0;
   if (j < cols)
-    for (int r = ph; r < rows; r += 4) s += A[(size_t)r * lda + j];
+    for (int r = ph; r < rows; r += 4) s += (double)A[(size_t)r * lda + j];
   part[ph][t & 63] = s;
   __syncthreads();
-  if (t < 64 && j < cols) out[j] = (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]) * scale;
+  if (t < 64 && j < cols) out[j] = (float)((((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]) * (double)scale);
 }
 
 static void colsum(hipStream_t s, const float* A, int rows, int cols, int lda, float* out, float scale = 1.0f) {
@@ -301,37 +304,40 @@ static void colsum(hipStream_t s, const float* A, int rows, int cols, int lda, f
 // dK0[(di*2+dj)*4 + c][o] = sum_(b,i,j) x[b][i+di][j+dj][c] dz1[b][i*3+j][o] over in-range taps; block = one
 // (di, dj, c) row, thread = (o, row phase r of 8), phases combined in order
 __global__ __launch_bounds__(256) void k_conv1_wgrad(const uint8_t* obs, const float* dz1, int B, float* g0) {
-  __shared__ float part[8][32];
+  __shared__ double part[8][32];
   const int kr = blockIdx.x, tap = kr >> 2, c = kr & 3, di = tap >> 1, dj = tap & 1;
   const int t = threadIdx.x, o = t & 31, ph = t >> 5;
-  float s = 0.0f;
+  double s = 0.0;
   for (int q = ph; q < B * 9; q += 8) {
     const int b = q / 9, p = q - b * 9, i = p / 3, j = p - i * 3;
-    if (i + di < 3 && j + dj < 3) s += (float)obs[(size_t)b * kObs + ((i + di) * 3 + j + dj) * 4 + c] * dz1[(size_t)q * 32 + o];
+    if (i + di < 3 && j + dj < 3) s += (double)obs[(size_t)b * kObs + ((i + di) * 3 + j + dj) * 4 + c] * (double)dz1[(size_t)q * 32 + o];
   }
   part[ph][o] = s;
   __syncthreads();
   if (t < 32) {
-    float v = 0.0f;
+    double v = 0.0;
     for (int r = 0; r < 8; ++r) v += part[r][t];
-    g0[kr * 32 + t] = v;
+    g0[kr * 32 + t] = (float)v;
   }
 }
 
 // per-variable L2 norms (one block per variable, fixed-order tree) and legacy Adam with clip_by_norm
 __global__ __launch_bounds__(256) void k_norms(const float* g, float* norms) {
-  __shared__ float red[256];
+  __shared__ double red[256];
   const int v = blockIdx.x;
   const float* gv = g + var_off(v);
-  float s = 0.0f;
-  for (int i = threadIdx.x; i < kVarSize[v]; i += 256) s += gv[i] * gv[i];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < kVarSize[v]; i += 256) s += (double)gv[i] * (double)gv[i];
   red[threadIdx.x] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
     if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
     __syncthreads();
   }
-  if (threadIdx.x == 0) norms[v] = red[0] > 0.0f ? sqrtf(red[0]) : red[0];
+  if (threadIdx.x == 0) {
+    const float l2 = (float)red[0];
+    norms[v] = l2 > 0.0f ? sqrtf(l2) : l2;
+  }
 }
 
 __global__ __launch_bounds__(256) void k_adam(float* w, float* m, float* vv, const float* g, const float* norms, float alpha,

@@ -205,7 +205,12 @@ __global__ __launch_bounds__(256) void k_fc2(Fc2Args A) {
       mx = fmaxf(fmaxf(q0, q1), q2);
     }
     const float r = A.rewards[b];
-    A.y_out[b] = A.dones[b] ? r : __fadd_rn(r, __fmul_rn(mx, A.gamma));   // two roundings, as the reference (add_arrays after array_mul)
+    {   // two roundings, as the reference (add_arrays after array_mul).  __fadd_rn(r, __fmul_rn(mx, gamma)) was one v_fma_f32
+        // here: they are plain + and * in a header and this file is built with contraction on (see adam_elem)
+#pragma clang fp contract(off)
+      const float v = mx * A.gamma;
+      A.y_out[b] = A.dones[b] ? r : r + v;
+    }
   }
 }
 
