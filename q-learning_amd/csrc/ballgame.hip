@@ -370,12 +370,10 @@ struct qlx_bg_env {
   uint32_t id_offset = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  qlx_ballgame_state* d_state = nullptr;
-  uint32_t* d_ep_steps = nullptr;
-  uint32_t* d_bad = nullptr;
-  uint8_t* d_tmp_u8 = nullptr;
-  uint8_t* d_tmp_u8b = nullptr;
-  float* d_tmp_f32 = nullptr;
+  DeviceBuffer<qlx_ballgame_state> d_state;
+  DeviceBuffer<uint32_t> d_ep_steps, d_bad;
+  DeviceBuffer<uint8_t> d_tmp_u8, d_tmp_u8b;
+  DeviceBuffer<float> d_tmp_f32;
 };
 
 struct BgWs {
@@ -389,10 +387,10 @@ struct qlx_bg_model {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  float *d_params = nullptr, *d_m = nullptr, *d_v = nullptr, *d_grads = nullptr, *d_norms = nullptr;
+  DeviceBuffer<float> d_params, d_m, d_v, d_grads, d_norms;
   int64_t iterations = 0;
   float lr = 0.00025f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f, clipnorm = 1.0f;
-  void* ws = nullptr;
+  DeviceBuffer<uint8_t> ws;
   int ws_batch = 0;
   BgWs w;
 };
@@ -403,8 +401,8 @@ namespace bg {
 static void model_workspace(qlx_bg_model* m, int B) {
   if (B <= m->ws_batch) return;
   QLX_HIP(hipStreamSynchronize(m->stream));
-  if (m->ws) (void)hipFree(m->ws);
-  m->ws = nullptr;
+  m->ws.release();
+  m->ws_batch = 0;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; };
   const size_t o_obs = take((size_t)B * kObs), o_a1 = take((size_t)B * 288 * 4), o_a2 = take((size_t)B * 288 * 4);
@@ -412,8 +410,8 @@ static void model_workspace(qlx_bg_model* m, int B) {
   const size_t o_hs = take((size_t)B * 4), o_dz3 = take((size_t)B * 512 * 4), o_dz2 = take((size_t)B * 288 * 4);
   const size_t o_dz1 = take((size_t)B * 288 * 4), o_y = take((size_t)B * 4), o_rew = take((size_t)B * 4), o_loss = take(64);
   const size_t o_act = take((size_t)B), o_am = take((size_t)B), o_done = take((size_t)B);
-  QLX_HIP(hipMalloc(&m->ws, off));
-  char* base = (char*)m->ws;
+  m->ws.alloc(off);
+  char* base = (char*)m->ws.get();
   BgWs& w = m->w;
   w.obs = (uint8_t*)(base + o_obs);
   w.a1 = (float*)(base + o_a1); w.a2 = (float*)(base + o_a2); w.a3 = (float*)(base + o_a3);
@@ -520,20 +518,20 @@ struct qlx_bg_learner {
   uint32_t N = 0, B = 0, max_updates = 0;
   uint64_t cap = 0, total = 0;
   // replay columns (replay_buffer.rs: one FIFO position for all)
-  qlx_ballgame_state *d_rs = nullptr, *d_rsn = nullptr;
-  uint8_t *d_ra = nullptr, *d_rd = nullptr;
-  float* d_rr = nullptr;
+  DeviceBuffer<qlx_ballgame_state> d_rs, d_rsn;
+  DeviceBuffer<uint8_t> d_ra, d_rd;
+  DeviceBuffer<float> d_rr;
   // per vector step
-  uint8_t *d_obs = nullptr, *d_actions = nullptr, *d_dones = nullptr, *d_reset = nullptr;
-  float *d_rewards = nullptr, *d_q = nullptr;
-  double* d_eps = nullptr;
+  DeviceBuffer<uint8_t> d_obs, d_actions, d_dones, d_reset;
+  DeviceBuffer<float> d_rewards, d_q;
+  DeviceBuffer<double> d_eps;
   uint64_t eps_len = 0;
-  float *d_ep_reward = nullptr, *d_hist = nullptr;
-  Book* d_book = nullptr;
-  uint64_t* d_idx = nullptr;
-  uint8_t *d_xs = nullptr, *d_xn = nullptr, *d_bact = nullptr, *d_bdone = nullptr;
-  float *d_brew = nullptr, *d_targets = nullptr, *d_losses = nullptr;
-  float* d_qsel = nullptr;   // double DQN: online Q(s') of the step's batches [U*B][5]
+  DeviceBuffer<float> d_ep_reward, d_hist;
+  DeviceBuffer<Book> d_book;
+  DeviceBuffer<uint64_t> d_idx;
+  DeviceBuffer<uint8_t> d_xs, d_xn, d_bact, d_bdone;
+  DeviceBuffer<float> d_brew, d_targets, d_losses;
+  DeviceBuffer<float> d_qsel;   // double DQN: online Q(s') of the step's batches [U*B][5]
   bool ddqn = false, per = false;
   qlx::PerState prio;
   uint64_t step_count = 0, vec_steps = 0, update_count = 0;
@@ -671,12 +669,12 @@ int32_t qlx_bg_env_create(uint32_t n_envs, uint64_t seed, int32_t device, qlx_bg
       e->n = n_envs;
       e->seed = seed;
       QLX_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-      QLX_HIP(hipMalloc(&e->d_state, (size_t)n_envs * sizeof(qlx_ballgame_state)));
-      QLX_HIP(hipMalloc(&e->d_ep_steps, (size_t)n_envs * 4));
-      QLX_HIP(hipMalloc(&e->d_bad, 4));
-      QLX_HIP(hipMalloc(&e->d_tmp_u8, n_envs));
-      QLX_HIP(hipMalloc(&e->d_tmp_u8b, n_envs));
-      QLX_HIP(hipMalloc(&e->d_tmp_f32, (size_t)n_envs * 4));
+      e->d_state.alloc(n_envs);
+      e->d_ep_steps.alloc(n_envs);
+      e->d_bad.alloc(1);
+      e->d_tmp_u8.alloc(n_envs);
+      e->d_tmp_u8b.alloc(n_envs);
+      e->d_tmp_f32.alloc(n_envs);
       QLX_HIP(hipMemsetAsync(e->d_bad, 0, 4, e->stream));
       hipLaunchKernelGGL(k_env_init, dim3((n_envs + 255) / 256), dim3(256), 0, e->stream, e->d_state, e->d_ep_steps, n_envs, seed,
                          0u, (const uint8_t*)nullptr, 0);
@@ -695,8 +693,6 @@ int32_t qlx_bg_env_destroy(qlx_bg_env* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
-    void* ptrs[] = {e->d_state, e->d_ep_steps, e->d_bad, e->d_tmp_u8, e->d_tmp_u8b, e->d_tmp_f32};
-    for (void* p : ptrs) (void)hipFree(p);
     if (e->own_stream) (void)hipStreamDestroy(e->stream);
     delete e;
   });
@@ -743,12 +739,10 @@ int32_t qlx_bg_env_obs(qlx_bg_env* e, uint8_t* out) {
   return guard([&] {
     QLX_CHECK(e && out, QLX_E_INVALID, "null argument");
     QLX_HIP(hipSetDevice(e->device));
-    uint8_t* d = nullptr;
-    QLX_HIP(hipMalloc(&d, (size_t)e->n * kObs));
+    DeviceBuffer<uint8_t> d((size_t)e->n * kObs);
     hipLaunchKernelGGL(k_env_obs, dim3((e->n + 255) / 256), dim3(256), 0, e->stream, e->d_state, e->n, d);
     QLX_HIP(hipMemcpyAsync(out, d, (size_t)e->n * kObs, hipMemcpyDeviceToHost, e->stream));
     QLX_HIP(hipStreamSynchronize(e->stream));
-    QLX_HIP(hipFree(d));
   });
 }
 
@@ -790,11 +784,11 @@ int32_t qlx_bg_model_create(uint64_t seed, int32_t device, qlx_bg_model** out) {
       m->device = device;
       QLX_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
       const size_t pb = kParams * 4;
-      QLX_HIP(hipMalloc(&m->d_params, pb));
-      QLX_HIP(hipMalloc(&m->d_m, pb));
-      QLX_HIP(hipMalloc(&m->d_v, pb));
-      QLX_HIP(hipMalloc(&m->d_grads, pb));
-      QLX_HIP(hipMalloc(&m->d_norms, kVars * 4));
+      m->d_params.alloc(kParams);
+      m->d_m.alloc(kParams);
+      m->d_v.alloc(kParams);
+      m->d_grads.alloc(kParams);
+      m->d_norms.alloc(kVars);
       std::vector<float> params;
       glorot_host(params, seed);
       QLX_HIP(hipMemcpy(m->d_params, params.data(), pb, hipMemcpyHostToDevice));
@@ -814,8 +808,6 @@ int32_t qlx_bg_model_destroy(qlx_bg_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
-    void* ptrs[] = {m->d_params, m->d_m, m->d_v, m->d_grads, m->d_norms, m->ws};
-    for (void* p : ptrs) (void)hipFree(p);
     if (m->own_stream) (void)hipStreamDestroy(m->stream);
     delete m;
   });
@@ -943,9 +935,9 @@ int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learne
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
       st = qlx_bg_model_create(p->init_seed, device, &L->target);   // same initial weights (:107-108)
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
-      L->env->stream = L->stream; L->env->own_stream = false;
-      L->online->stream = L->stream; L->online->own_stream = false;
-      L->target->stream = L->stream; L->target->own_stream = false;
+      adopt_stream(L->env, L->stream);
+      adopt_stream(L->online, L->stream);
+      adopt_stream(L->target, L->stream);
       if (p->rank != 0) {   // data-parallel ranks own env ids rank * N + e
         L->env->id_offset = p->rank * L->N;
         hipLaunchKernelGGL(k_env_init, dim3((L->N + 255) / 256), dim3(256), 0, L->stream, L->env->d_state, L->env->d_ep_steps, L->N,
@@ -953,33 +945,33 @@ int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learne
       }
       const std::vector<double> eps = epsilon_table(*p);
       L->eps_len = eps.size();
-      QLX_HIP(hipMalloc(&L->d_eps, eps.size() * 8));
+      L->d_eps.alloc(eps.size());
       QLX_HIP(hipMemcpy(L->d_eps, eps.data(), eps.size() * 8, hipMemcpyHostToDevice));
       const uint32_t N = L->N, B = L->B;
       L->max_updates = (uint32_t)(N / p->update_after_actions + 2);
       const size_t UB = (size_t)L->max_updates * B;
-      QLX_HIP(hipMalloc(&L->d_rs, L->cap * sizeof(qlx_ballgame_state)));
-      QLX_HIP(hipMalloc(&L->d_rsn, L->cap * sizeof(qlx_ballgame_state)));
-      QLX_HIP(hipMalloc(&L->d_ra, L->cap));
-      QLX_HIP(hipMalloc(&L->d_rd, L->cap));
-      QLX_HIP(hipMalloc(&L->d_rr, L->cap * 4));
-      QLX_HIP(hipMalloc(&L->d_obs, (size_t)N * kObs));
-      QLX_HIP(hipMalloc(&L->d_actions, N));
-      QLX_HIP(hipMalloc(&L->d_dones, N));
-      QLX_HIP(hipMalloc(&L->d_reset, N));
-      QLX_HIP(hipMalloc(&L->d_rewards, (size_t)N * 4));
-      QLX_HIP(hipMalloc(&L->d_q, (size_t)N * kA * 4));
-      QLX_HIP(hipMalloc(&L->d_ep_reward, (size_t)N * 4));
-      QLX_HIP(hipMalloc(&L->d_hist, p->episode_reward_history_buffer_len * 4));
-      QLX_HIP(hipMalloc(&L->d_book, sizeof(Book)));
-      QLX_HIP(hipMalloc(&L->d_idx, UB * 8));
-      QLX_HIP(hipMalloc(&L->d_xs, UB * kObs));
-      QLX_HIP(hipMalloc(&L->d_xn, UB * kObs));
-      QLX_HIP(hipMalloc(&L->d_bact, UB));
-      QLX_HIP(hipMalloc(&L->d_bdone, UB));
-      QLX_HIP(hipMalloc(&L->d_brew, UB * 4));
-      QLX_HIP(hipMalloc(&L->d_targets, UB * 4));
-      QLX_HIP(hipMalloc(&L->d_losses, L->max_updates * 4));
+      L->d_rs.alloc(L->cap);
+      L->d_rsn.alloc(L->cap);
+      L->d_ra.alloc(L->cap);
+      L->d_rd.alloc(L->cap);
+      L->d_rr.alloc(L->cap);
+      L->d_obs.alloc((size_t)N * kObs);
+      L->d_actions.alloc(N);
+      L->d_dones.alloc(N);
+      L->d_reset.alloc(N);
+      L->d_rewards.alloc(N);
+      L->d_q.alloc((size_t)N * kA);
+      L->d_ep_reward.alloc(N);
+      L->d_hist.alloc(p->episode_reward_history_buffer_len);
+      L->d_book.alloc(1);
+      L->d_idx.alloc(UB);
+      L->d_xs.alloc(UB * kObs);
+      L->d_xn.alloc(UB * kObs);
+      L->d_bact.alloc(UB);
+      L->d_bdone.alloc(UB);
+      L->d_brew.alloc(UB);
+      L->d_targets.alloc(UB);
+      L->d_losses.alloc(L->max_updates);
       QLX_HIP(hipMemsetAsync(L->d_ep_reward, 0, (size_t)N * 4, L->stream));
       QLX_HIP(hipMemsetAsync(L->d_book, 0, sizeof(Book), L->stream));
       QLX_HIP(hipMemsetAsync(L->d_q, 0, (size_t)N * kA * 4, L->stream));
@@ -987,7 +979,7 @@ int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learne
       model_workspace(L->target, (int)UB);
       if (L->ddqn) {
         model_workspace(L->online, (int)UB);
-        QLX_HIP(hipMalloc(&L->d_qsel, UB * kA * 4));
+        L->d_qsel.alloc(UB * kA);
       }
       if (L->per) L->prio.init(L->cap, UB);
       QLX_HIP(hipStreamSynchronize(L->stream));
@@ -1007,11 +999,6 @@ int32_t qlx_bg_learner_destroy(qlx_bg_learner* L) {
     qlx_bg_env_destroy(L->env);
     qlx_bg_model_destroy(L->online);
     qlx_bg_model_destroy(L->target);
-    void* ptrs[] = {L->d_rs, L->d_rsn, L->d_ra, L->d_rd, L->d_rr, L->d_obs, L->d_actions, L->d_dones, L->d_reset, L->d_rewards,
-                    L->d_q, L->d_eps, L->d_ep_reward, L->d_hist, L->d_book, L->d_idx, L->d_xs, L->d_xn, L->d_bact, L->d_bdone,
-                    L->d_brew, L->d_targets, L->d_losses, L->d_qsel};
-    for (void* p : ptrs) (void)hipFree(p);
-    L->prio.release();
     (void)hipStreamDestroy(L->stream);
     delete L;
   });

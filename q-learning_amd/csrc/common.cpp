@@ -7,6 +7,7 @@
 #include <mutex>
 #include <set>
 #include <tuple>
+#include "device_memory.h"
 #include "qlx_internal.h"
 
 namespace qlx {
@@ -36,6 +37,30 @@ void debug_sync(hipStream_t s, const char* what) {
   const hipError_t e = hipStreamSynchronize(s);
   if (e != hipSuccess) throw Error{QLX_E_HIP, std::string("after ") + what + ": " + hipGetErrorString(e)};
 }
+
+// the only callers of the HIP allocator (device_memory.h).  A failed allocation leaves the runtime's last error set:
+// it is cleared here, so the launch check after the next kernel does not report it.
+[[noreturn]] static void alloc_failed(const char* what, hipError_t e, size_t bytes) {
+  (void)hipGetLastError();
+  const std::string msg = std::string(what) + " of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e);
+  throw Error{e == hipErrorOutOfMemory ? QLX_E_OOM : QLX_E_HIP, msg};
+}
+
+void* device_alloc(size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) alloc_failed("hipMalloc", e, bytes);
+  return p;
+}
+void device_free(void* p) noexcept { (void)hipFree(p); }
+
+void* pinned_alloc(size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) alloc_failed("hipHostMalloc", e, bytes);
+  return p;
+}
+void pinned_free(void* p) noexcept { (void)hipHostFree(p); }
 
 int current_device_checked(int device) {
   int count = 0;

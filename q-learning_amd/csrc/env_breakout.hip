@@ -508,14 +508,14 @@ int32_t qlx_env_create(int32_t kind, uint32_t n_envs, uint64_t seed, int32_t dev
       e->seed = seed;
       e->acos_thr = acos_threshold_host();
       QLX_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-      QLX_HIP(hipMalloc(&e->d_state, sizeof(State) * n_envs));
-      QLX_HIP(hipMalloc(&e->d_obs, (size_t)n_envs * kSlots * kFramePix));
-      QLX_HIP(hipMalloc(&e->d_hash, sizeof(uint64_t) * n_envs));
-      QLX_HIP(hipMalloc(&e->d_ep_steps, sizeof(uint32_t) * n_envs));
-      QLX_HIP(hipMalloc(&e->d_flags, 16));
-      QLX_HIP(hipMalloc(&e->d_tmp_u8, n_envs));
-      QLX_HIP(hipMalloc(&e->d_tmp_u8b, n_envs));
-      QLX_HIP(hipMalloc(&e->d_tmp_f32, sizeof(float) * n_envs));
+      e->d_state.alloc(n_envs);
+      e->d_obs.alloc((size_t)n_envs * kSlots * kFramePix);
+      e->d_hash.alloc(n_envs);
+      e->d_ep_steps.alloc(n_envs);
+      e->d_flags.alloc(4);
+      e->d_tmp_u8.alloc(n_envs);
+      e->d_tmp_u8b.alloc(n_envs);
+      e->d_tmp_f32.alloc(n_envs);
       QLX_HIP(hipMemsetAsync(e->d_hash, 0, sizeof(uint64_t) * n_envs, e->stream));
       QLX_HIP(hipMemsetAsync(e->d_flags, 0, 16, e->stream));
       int8_t col[kFrame], row[kFrame];
@@ -537,9 +537,6 @@ int32_t qlx_env_destroy(qlx_env* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(e->d_state); (void)hipFree(e->d_obs); (void)hipFree(e->d_hash); (void)hipFree(e->d_flags);
-    (void)hipFree(e->d_ep_steps);
-    (void)hipFree(e->d_tmp_u8); (void)hipFree(e->d_tmp_u8b); (void)hipFree(e->d_tmp_f32); (void)hipFree(e->d_obs_view);
     if (e->own_stream) (void)hipStreamDestroy(e->stream);
     delete e;
   });
@@ -585,7 +582,7 @@ int32_t qlx_env_obs(qlx_env* e, uint8_t* out) {
     QLX_HIP(hipSetDevice(e->device));
     const size_t bytes = (size_t)e->n * kFramePix * kSlots;
     // (a device buffer kept by the env: the Rust Environment::step of INTEGRATION.md reads the state every step)
-    if (!e->d_obs_view) QLX_HIP(hipMalloc(&e->d_obs_view, bytes));
+    e->d_obs_view.reserve(bytes);
     const size_t total = (size_t)e->n * kFramePix;
     hipLaunchKernelGGL(k_env_obs_view, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_obs, e->n, e->d_obs_view);
     QLX_HIP(hipGetLastError());

@@ -174,23 +174,20 @@ struct qlx_evaluator {
   uint32_t poll = 0;
   qlx_env* env = nullptr;
   hipStream_t env_stream = nullptr;   // the env's own stream (it adopts the model's for a run)
-  uint8_t* d_actions = nullptr;
-  float* d_rewards = nullptr;
-  uint8_t* d_dones = nullptr;
-  uint8_t* d_reset = nullptr;
-  uint32_t* d_list = nullptr;          // [n] envs still playing, env order
-  const uint8_t** d_table = nullptr;   // [n][4] frame pointers of the next forward
-  float* d_ret = nullptr;              // [n] running episode return
-  float* d_qsum = nullptr;             // [n] running sum of max_a q
-  float* d_qmax = nullptr;             // [n] max_a q of the step being taken
-  uint32_t* d_kdone = nullptr;         // [n] episodes recorded
-  float* d_rec_ret = nullptr;          // [n][K] records
-  uint32_t* d_rec_len = nullptr;
-  uint8_t* d_rec_term = nullptr;
-  float* d_rec_qsum = nullptr;
-  unsigned long long* d_counts = nullptr;   // [3] actions taken
-  uint32_t* d_count = nullptr;              // [2] (k_eval_init)
-  uint32_t* h_count = nullptr;              // pinned copy read at each poll
+  qlx::DeviceBuffer<uint8_t> d_actions, d_dones, d_reset;
+  qlx::DeviceBuffer<float> d_rewards;
+  qlx::DeviceBuffer<uint32_t> d_list;          // [n] envs still playing, env order
+  qlx::DeviceBuffer<const uint8_t*> d_table;   // [n][4] frame pointers of the next forward
+  qlx::DeviceBuffer<float> d_ret;              // [n] running episode return
+  qlx::DeviceBuffer<float> d_qsum;             // [n] running sum of max_a q
+  qlx::DeviceBuffer<float> d_qmax;             // [n] max_a q of the step being taken
+  qlx::DeviceBuffer<uint32_t> d_kdone;         // [n] episodes recorded
+  qlx::DeviceBuffer<float> d_rec_ret, d_rec_qsum;   // [n][K] records
+  qlx::DeviceBuffer<uint32_t> d_rec_len;
+  qlx::DeviceBuffer<uint8_t> d_rec_term;
+  qlx::DeviceBuffer<unsigned long long> d_counts;   // [3] actions taken
+  qlx::DeviceBuffer<uint32_t> d_count;              // [2] (k_eval_init)
+  qlx::PinnedBuffer<uint32_t> h_count;              // pinned copy read at each poll
   hipEvent_t polled = nullptr;
   // host copies of the last run's records
   bool has_run = false;
@@ -319,23 +316,23 @@ int32_t qlx_evaluator_create(const qlx_eval_config* cfg, int32_t device, qlx_eva
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
       ev->env_stream = ev->env->stream;
       ev->env->hashing = false;
-      QLX_HIP(hipMalloc(&ev->d_actions, n));
-      QLX_HIP(hipMalloc(&ev->d_rewards, n * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_dones, n));
-      QLX_HIP(hipMalloc(&ev->d_reset, n));
-      QLX_HIP(hipMalloc(&ev->d_list, n * sizeof(uint32_t)));
-      QLX_HIP(hipMalloc(&ev->d_table, (size_t)n * kSlots * sizeof(void*)));
-      QLX_HIP(hipMalloc(&ev->d_ret, n * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_qsum, n * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_qmax, n * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_kdone, n * sizeof(uint32_t)));
-      QLX_HIP(hipMalloc(&ev->d_rec_ret, R * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_rec_len, R * sizeof(uint32_t)));
-      QLX_HIP(hipMalloc(&ev->d_rec_term, R));
-      QLX_HIP(hipMalloc(&ev->d_rec_qsum, R * sizeof(float)));
-      QLX_HIP(hipMalloc(&ev->d_counts, kActions * sizeof(unsigned long long)));
-      QLX_HIP(hipMalloc(&ev->d_count, 2 * sizeof(uint32_t)));
-      QLX_HIP(hipHostMalloc((void**)&ev->h_count, 2 * sizeof(uint32_t), hipHostMallocDefault));
+      ev->d_actions.alloc(n);
+      ev->d_rewards.alloc(n);
+      ev->d_dones.alloc(n);
+      ev->d_reset.alloc(n);
+      ev->d_list.alloc(n);
+      ev->d_table.alloc((size_t)n * kSlots);
+      ev->d_ret.alloc(n);
+      ev->d_qsum.alloc(n);
+      ev->d_qmax.alloc(n);
+      ev->d_kdone.alloc(n);
+      ev->d_rec_ret.alloc(R);
+      ev->d_rec_len.alloc(R);
+      ev->d_rec_term.alloc(R);
+      ev->d_rec_qsum.alloc(R);
+      ev->d_counts.alloc(kActions);
+      ev->d_count.alloc(2);
+      ev->h_count.alloc(2);
       QLX_HIP(hipEventCreateWithFlags(&ev->polled, hipEventDisableTiming));
       ev->rec_ret.resize(R);
       ev->rec_qsum.resize(R);
@@ -354,10 +351,6 @@ int32_t qlx_evaluator_destroy(qlx_evaluator* ev) {
     if (!ev) return;
     (void)hipSetDevice(ev->device);
     qlx_env_destroy(ev->env);
-    void* ptrs[] = {ev->d_actions, ev->d_rewards, ev->d_dones, ev->d_reset, ev->d_list, (void*)ev->d_table, ev->d_ret, ev->d_qsum,
-                    ev->d_qmax, ev->d_kdone, ev->d_rec_ret, ev->d_rec_len, ev->d_rec_term, ev->d_rec_qsum, ev->d_counts, ev->d_count};
-    for (void* p : ptrs) (void)hipFree(p);
-    if (ev->h_count) (void)hipHostFree(ev->h_count);
     if (ev->polled) (void)hipEventDestroy(ev->polled);
     delete ev;
   });

@@ -264,24 +264,19 @@ struct qlx_learner {
   qlx_model* target = nullptr;
   uint32_t N = 0, B = 0;
   // device buffers
-  uint8_t* d_actions = nullptr;
-  float* d_rewards = nullptr;
-  uint8_t* d_dones = nullptr;
-  uint8_t* d_reset = nullptr;
-  const uint8_t** d_obs_table = nullptr;
-  double* d_eps = nullptr;
+  qlx::DeviceBuffer<uint8_t> d_actions, d_dones, d_reset;
+  qlx::DeviceBuffer<float> d_rewards;
+  qlx::DeviceBuffer<const uint8_t*> d_obs_table;
+  qlx::DeviceBuffer<double> d_eps;
   uint64_t eps_len = 0;
-  float* d_ep_reward = nullptr;
-  float* d_hist = nullptr;
-  qlx::Book* d_book = nullptr;
-  uint64_t* d_idx = nullptr;       // [max_updates][B]
-  const uint8_t** d_tab_s = nullptr;
-  const uint8_t** d_tab_sn = nullptr;
-  uint8_t* d_bact = nullptr;
-  float* d_brew = nullptr;
-  uint8_t* d_bdone = nullptr;
-  float* d_losses = nullptr;       // [max_updates]
-  float* d_targets = nullptr;      // [max_updates][B]
+  qlx::DeviceBuffer<float> d_ep_reward, d_hist;
+  qlx::DeviceBuffer<qlx::Book> d_book;
+  qlx::DeviceBuffer<uint64_t> d_idx;       // [max_updates][B]
+  qlx::DeviceBuffer<const uint8_t*> d_tab_s, d_tab_sn;
+  qlx::DeviceBuffer<uint8_t> d_bact, d_bdone;
+  qlx::DeviceBuffer<float> d_brew;
+  qlx::DeviceBuffer<float> d_losses;       // [max_updates]
+  qlx::DeviceBuffer<float> d_targets;      // [max_updates][B]
   uint32_t max_updates = 0;
   bool ddqn = false, per = false;  // qlx_params.flags
   qlx::PerState prio;              // prioritized replay (per.hip)
@@ -298,34 +293,31 @@ struct qlx_learner {
   int world = 1, rank = 0;
   // global solved() over ranks: per vector step, {sum running_reward, sum has_history, sum episodes} (f64) and {min
   // episode reward} all-reduced on the learner stream (d_gsum[3], d_gmin[1])
-  double* d_gsum = nullptr;
-  float* d_gmin = nullptr;
+  qlx::DeviceBuffer<double> d_gsum;
+  qlx::DeviceBuffer<float> d_gmin;
   // pinned host copies read after every vector step (the solved() check): Book + the global sums
-  qlx::Book* h_book = nullptr;
-  double* h_gsum = nullptr;
+  qlx::PinnedBuffer<qlx::Book> h_book;
+  qlx::PinnedBuffer<double> h_gsum;
   // frame_sparsity's counters: a device buffer and its pinned host copy (8 x u64: the train and the acting halves)
-  unsigned long long* d_sparsity = nullptr;
-  unsigned long long* h_sparsity = nullptr;
+  qlx::DeviceBuffer<unsigned long long> d_sparsity;
+  qlx::PinnedBuffer<unsigned long long> h_sparsity;
   // Bellman-target memo per replay slot (ycache_fill): on when the target net is frozen (target_sync_steps == 0,
   // the reference) and y does not depend on the online net (no double DQN); QLX_TARGET_CACHE=0 turns it off
   bool ycache = false;
-  float* d_ycache = nullptr;           // [capacity] y of the transition in each ring slot
-  const uint8_t** d_ytab = nullptr;    // [ychunk * 4]
-  float* d_yrew = nullptr;             // [ychunk]
-  uint8_t* d_ydone = nullptr;          // [ychunk]
-  float* d_ytmp = nullptr;             // [ychunk]
+  qlx::DeviceBuffer<float> d_ycache;           // [capacity] y of the transition in each ring slot
+  qlx::DeviceBuffer<const uint8_t*> d_ytab;    // [ychunk * 4]
+  qlx::DeviceBuffer<float> d_yrew, d_ytmp;     // [ychunk]
+  qlx::DeviceBuffer<uint8_t> d_ydone;          // [ychunk]
   uint32_t ychunk = 0;
   uint64_t ycache_version = 0;         // target->version the memo was computed with
-  uint32_t ycap = 0;                   // allocated chunk of d_ytab / d_yrew / d_ydone / d_ytmp (>= ychunk)
   // n-step returns (qlx_params.n_step > 1).  The memo then holds the bootstrap value v = max_a Q_target(s')
   // per slot instead of y, and every target pass runs the head with gamma = 1 over zero rewards / dones (d_zero: zero
   // bytes, read as both) so that it leaves v; R, g and terminal of the sampled windows are kept only without the memo.
   uint32_t n_step = 1;
-  void* d_zero = nullptr;              // [zcap * 4 bytes] of zeros
-  uint32_t zcap = 0;
-  float* d_nret = nullptr;             // [max_updates][B] R
-  float* d_ndisc = nullptr;            // [max_updates][B] g = gamma^m
-  uint8_t* d_nterm = nullptr;          // [max_updates][B] done of the window's last transition
+  qlx::DeviceBuffer<float> d_zero;             // zeros (zero_reserve)
+  qlx::DeviceBuffer<float> d_nret;             // [max_updates][B] R
+  qlx::DeviceBuffer<float> d_ndisc;            // [max_updates][B] g = gamma^m
+  qlx::DeviceBuffer<uint8_t> d_nterm;          // [max_updates][B] done of the window's last transition
   qlx::Profiler prof;
   // statistics events (write_checkpoint + learning_update_log, self_driving_tf_q_learner.rs:204-212,226-230)
   uint64_t stats_events = 0;
@@ -355,8 +347,8 @@ static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, cons
   ta.gamma = L->p.gamma;
   ta.y_out = L->d_targets + o;
   if (L->n_step > 1) {   // the head leaves the bootstrap value: y = 0 + v * 1 (d_tab_sn holds s' of each window's last transition)
-    ta.rewards = static_cast<const float*>(L->d_zero);
-    ta.dones = static_cast<const uint8_t*>(L->d_zero);
+    ta.rewards = L->d_zero;
+    ta.dones = reinterpret_cast<const uint8_t*>(L->d_zero.get());
     ta.gamma = 1.0f;
   }
   model_head(tg, 2, ta, (int)n, s);
@@ -367,16 +359,12 @@ static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, cons
   }
 }
 
-// at least n * 4 zero bytes in d_zero (n-step: the zero rewards / dones of the bootstrap passes)
+// at least n zero floats in d_zero (n-step: the zero rewards / dones of the bootstrap passes)
 static void zero_reserve(qlx_learner* L, uint32_t n) {
-  if (n <= L->zcap) return;
+  if (n <= L->d_zero.size()) return;
   QLX_HIP(hipStreamSynchronize(L->stream));
-  if (L->d_zero) QLX_HIP(hipFree(L->d_zero));
-  L->d_zero = nullptr;
-  L->zcap = 0;
-  QLX_HIP(hipMalloc(&L->d_zero, (size_t)n * 4));
-  QLX_HIP(hipMemsetAsync(L->d_zero, 0, (size_t)n * 4, L->stream));
-  L->zcap = n;
+  L->d_zero.reserve(n);
+  QLX_HIP(hipMemsetAsync(L->d_zero, 0, L->d_zero.bytes(), L->stream));
 }
 
 // Target memo.  With the target net frozen, y = r + gamma * max_a Q_target(s') (or r if done) of a transition is a
@@ -393,16 +381,13 @@ static void zero_reserve(qlx_learner* L, uint32_t n) {
 // (k_gather_nstep).  v is as fixed a function of the slot as y is, so the fill and the rebuild are the same.
 static void ycache_reserve(qlx_learner* L, uint32_t chunk) {
   if (L->n_step > 1) zero_reserve(L, chunk);
-  if (chunk <= L->ycap) return;
-  QLX_HIP(hipStreamSynchronize(L->stream));
-  for (void* p : {(void*)L->d_ytab, (void*)L->d_yrew, (void*)L->d_ydone, (void*)L->d_ytmp})
-    if (p) QLX_HIP(hipFree(p));
-  QLX_HIP(hipMalloc(&L->d_ytab, (size_t)chunk * 4 * sizeof(void*)));
-  QLX_HIP(hipMalloc(&L->d_yrew, chunk * sizeof(float)));
-  QLX_HIP(hipMalloc(&L->d_ydone, chunk));
-  QLX_HIP(hipMalloc(&L->d_ytmp, chunk * sizeof(float)));
+  // (d_ytmp grows last: after a regrow that failed part-way it is the one that still says so)
+  if (chunk > L->d_ytmp.size()) QLX_HIP(hipStreamSynchronize(L->stream));
+  L->d_ytab.reserve((size_t)chunk * 4);
+  L->d_yrew.reserve(chunk);
+  L->d_ydone.reserve(chunk);
+  L->d_ytmp.reserve(chunk);
   model_workspace(L->target, (int)chunk);
-  L->ycap = chunk;
 }
 
 static void ycache_fill(qlx_learner* L, uint64_t i0, uint64_t n, uint32_t chunk) {
@@ -422,8 +407,8 @@ static void ycache_fill(qlx_learner* L, uint64_t i0, uint64_t n, uint32_t chunk)
     ta.gamma = L->p.gamma;
     ta.y_out = L->d_ytmp;
     if (L->n_step > 1) {
-      ta.rewards = static_cast<const float*>(L->d_zero);
-      ta.dones = static_cast<const uint8_t*>(L->d_zero);
+      ta.rewards = L->d_zero;
+      ta.dones = reinterpret_cast<const uint8_t*>(L->d_zero.get());
       ta.gamma = 1.0f;
     }
     model_head(tg, 2, ta, (int)m, s);
@@ -704,10 +689,10 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
       // the memo (chunks of n_envs) and the per-batch target pass (U * B samples) must produce the same y bit for bit
       model_set_batch_invariant(L->target);
       // everything runs on the learner's stream
-      L->env->stream = L->stream; L->env->own_stream = false;
-      L->rb->stream = L->stream; L->rb->own_stream = false;
-      L->online->stream = L->stream; L->online->own_stream = false;
-      L->target->stream = L->stream; L->target->own_stream = false;
+      adopt_stream(L->env, L->stream);
+      adopt_stream(L->rb, L->stream);
+      adopt_stream(L->online, L->stream);
+      adopt_stream(L->target, L->stream);
       L->env->hashing = false;
       // re-seat env ids for data-parallel ranks (ball launch streams are per global env id)
       if (p->rank != 0) {
@@ -717,31 +702,31 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
       // epsilon table: eps_k after k decrements, k = 0.. until epsilon_min (repeated f64 subtraction)
       const std::vector<double> eps = epsilon_table(*p);
       L->eps_len = eps.size();
-      QLX_HIP(hipMalloc(&L->d_eps, eps.size() * sizeof(double)));
+      L->d_eps.alloc(eps.size());
       QLX_HIP(hipMemcpy(L->d_eps, eps.data(), eps.size() * sizeof(double), hipMemcpyHostToDevice));
       const uint32_t N = L->N, B = L->B;
       L->max_updates = (uint32_t)(N / p->update_after_actions + 2);
-      QLX_HIP(hipMalloc(&L->d_actions, N));
-      QLX_HIP(hipMalloc(&L->d_rewards, N * sizeof(float)));
-      QLX_HIP(hipMalloc(&L->d_dones, N));
-      QLX_HIP(hipMalloc(&L->d_reset, N));
-      QLX_HIP(hipMalloc(&L->d_obs_table, N * 4 * sizeof(void*)));
-      QLX_HIP(hipMalloc(&L->d_ep_reward, N * sizeof(float)));
-      QLX_HIP(hipMalloc(&L->d_hist, p->episode_reward_history_buffer_len * sizeof(float)));
-      QLX_HIP(hipMalloc(&L->d_book, sizeof(Book)));
-      QLX_HIP(hipHostMalloc((void**)&L->h_book, sizeof(Book), hipHostMallocDefault));
-      QLX_HIP(hipHostMalloc((void**)&L->h_gsum, 3 * sizeof(double), hipHostMallocDefault));
-      QLX_HIP(hipMalloc(&L->d_sparsity, 8 * sizeof(unsigned long long)));
-      QLX_HIP(hipHostMalloc((void**)&L->h_sparsity, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-      QLX_HIP(hipMalloc(&L->d_idx, (size_t)L->max_updates * B * sizeof(uint64_t)));
+      L->d_actions.alloc(N);
+      L->d_rewards.alloc(N);
+      L->d_dones.alloc(N);
+      L->d_reset.alloc(N);
+      L->d_obs_table.alloc((size_t)N * 4);
+      L->d_ep_reward.alloc(N);
+      L->d_hist.alloc(p->episode_reward_history_buffer_len);
+      L->d_book.alloc(1);
+      L->h_book.alloc(1);
+      L->h_gsum.alloc(3);
+      L->d_sparsity.alloc(8);
+      L->h_sparsity.alloc(8);
       const size_t UB = (size_t)L->max_updates * B;   // all batches of one vector step
-      QLX_HIP(hipMalloc(&L->d_tab_s, UB * 4 * sizeof(void*)));
-      QLX_HIP(hipMalloc(&L->d_tab_sn, UB * 4 * sizeof(void*)));
-      QLX_HIP(hipMalloc(&L->d_bact, UB));
-      QLX_HIP(hipMalloc(&L->d_brew, UB * sizeof(float)));
-      QLX_HIP(hipMalloc(&L->d_bdone, UB));
-      QLX_HIP(hipMalloc(&L->d_losses, L->max_updates * sizeof(float)));
-      QLX_HIP(hipMalloc(&L->d_targets, (size_t)L->max_updates * B * sizeof(float)));
+      L->d_idx.alloc(UB);
+      L->d_tab_s.alloc(UB * 4);
+      L->d_tab_sn.alloc(UB * 4);
+      L->d_bact.alloc(UB);
+      L->d_brew.alloc(UB);
+      L->d_bdone.alloc(UB);
+      L->d_losses.alloc(L->max_updates);
+      L->d_targets.alloc(UB);
       QLX_HIP(hipMemsetAsync(L->d_ep_reward, 0, N * sizeof(float), L->stream));
       QLX_HIP(hipMemsetAsync(L->d_book, 0, sizeof(Book), L->stream));
       QLX_HIP(hipMemsetAsync(L->d_actions, 0, N, L->stream));
@@ -754,16 +739,16 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
       L->ycache = p->target_sync_steps == 0 && !L->ddqn && !(tc && tc[0] == '0');
       if (L->ycache) {
         L->ychunk = std::min<uint32_t>(N, (uint32_t)kF32FwdChunk);
-        QLX_HIP(hipMalloc(&L->d_ycache, p->history_buffer_len * sizeof(float)));
+        L->d_ycache.alloc(p->history_buffer_len);
         ycache_reserve(L, L->ychunk);
         L->ycache_version = L->target->version;
       } else {
         model_workspace(L->target, (int)(L->max_updates * B));   // batched target pass (learner_targets)
         if (L->n_step > 1) {
           zero_reserve(L, (uint32_t)UB);
-          QLX_HIP(hipMalloc(&L->d_nret, UB * sizeof(float)));
-          QLX_HIP(hipMalloc(&L->d_ndisc, UB * sizeof(float)));
-          QLX_HIP(hipMalloc(&L->d_nterm, UB));
+          L->d_nret.alloc(UB);
+          L->d_ndisc.alloc(UB);
+          L->d_nterm.alloc(UB);
         }
       }
       if (L->ddqn) model_workspace(L->online, (int)(L->max_updates * B));   // + the online pass over s'
@@ -791,15 +776,6 @@ int32_t qlx_learner_destroy(qlx_learner* L) {
     qlx_replay_destroy(L->rb);
     qlx_model_destroy(L->online);
     qlx_model_destroy(L->target);
-    void* ptrs[] = {L->d_actions, L->d_rewards, L->d_dones, L->d_reset, (void*)L->d_obs_table, L->d_eps, L->d_ep_reward,
-                    L->d_hist, L->d_book, L->d_idx, (void*)L->d_tab_s, (void*)L->d_tab_sn, L->d_bact, L->d_brew,
-                    L->d_bdone, L->d_losses, L->d_targets, L->d_gsum, L->d_gmin, L->d_ycache, (void*)L->d_ytab,
-                    L->d_yrew, L->d_ydone, L->d_ytmp, L->d_sparsity, L->d_zero, L->d_nret,
-                    L->d_ndisc, L->d_nterm};
-    for (void* p : ptrs) (void)hipFree(p);
-    for (void* p : {(void*)L->h_book, (void*)L->h_gsum, (void*)L->h_sparsity})
-      if (p) (void)hipHostFree(p);
-    L->prio.release();
     (void)hipStreamDestroy(L->stream);
     delete L;
   });
@@ -1070,12 +1046,12 @@ static void learner_step_full(qlx_learner* L, bool train) {
   QLX_HIP(hipMemcpyAsync(L->h_book, L->d_book, sizeof(Book), hipMemcpyDeviceToHost, L->stream));
   if (dp) QLX_HIP(hipMemcpyAsync(L->h_gsum, L->d_gsum, 3 * sizeof(double), hipMemcpyDeviceToHost, L->stream));
   QLX_HIP(hipStreamSynchronize(L->stream));
-  const uint64_t episodes = dp ? (uint64_t)L->h_gsum[2] : L->h_book->episode_count;
+  const uint64_t episodes = dp ? (uint64_t)L->h_gsum[2] : L->h_book[0].episode_count;
   const bool ended = episodes != L->seen_episodes;
   L->seen_episodes = episodes;
   const float goal = learner_goal(L);
   const bool may_solve = dp ? (L->h_gsum[1] == (double)L->world && L->h_gsum[0] / (double)L->world >= (double)goal)
-                            : (L->h_book->hist_len > 0 && L->h_book->running_reward >= goal);
+                            : (L->h_book[0].hist_len > 0 && L->h_book[0].running_reward >= goal);
   if (ended && may_solve) {
     qlx_learner_stats st{};
     const int32_t rc = qlx_learner_stats_get(L, &st);
@@ -1138,16 +1114,15 @@ int32_t qlx_learner_dist_init(qlx_learner* L, int32_t world, int32_t rank, const
     for (hipEvent_t* e : {&L->ev_dense, &L->ev_reduced}) QLX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     L->world = world;
     L->rank = rank;
-    QLX_HIP(hipMalloc(&L->d_gsum, 3 * sizeof(double)));
-    QLX_HIP(hipMalloc(&L->d_gmin, sizeof(float)));
+    L->d_gsum.alloc(3);
+    L->d_gmin.alloc(1);
     // rank 0's online weights, Adam slots and step count on every rank (one broadcast of the initial
     // weights), and the target net = the online net as in SelfDrivingQLearner::new (self_driving_tf_q_learner.rs:94-116)
     qlx_model* on = L->online;
     QLX_HIP(hipStreamSynchronize(L->stream));
-    int64_t* d_iter = nullptr;
-    QLX_HIP(hipMalloc(&d_iter, sizeof(int64_t)));
+    DeviceBuffer<int64_t> d_iter(1);
     QLX_HIP(hipMemcpy(d_iter, &on->iterations, sizeof(int64_t), hipMemcpyHostToDevice));
-    for (float* buf : {on->d_params, on->d_m, on->d_v}) {
+    for (float* buf : {on->d_params.get(), on->d_m.get(), on->d_v.get()}) {
       const ncclResult_t rb = ncclBroadcast(buf, buf, (size_t)kNumParams, ncclFloat, 0, L->comm, L->stream);
       QLX_CHECK(rb == ncclSuccess, QLX_E_COMM, std::string("ncclBroadcast: ") + ncclGetErrorString(rb));
     }
@@ -1158,7 +1133,6 @@ int32_t qlx_learner_dist_init(qlx_learner* L, int32_t world, int32_t rank, const
     model_pack(L->target);
     QLX_HIP(hipStreamSynchronize(L->stream));
     QLX_HIP(hipMemcpy(&on->iterations, d_iter, sizeof(int64_t), hipMemcpyDeviceToHost));
-    QLX_HIP(hipFree(d_iter));
     // the global episode statistics as of now, so a stats query before the first vector step reads defined values
     if (world > 1) {
       learner_book_allreduce(L);

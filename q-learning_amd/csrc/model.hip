@@ -115,15 +115,13 @@ void model_adam(qlx_model* m, hipStream_t s, float scale) { m->f32 ? f32_adam(m,
 
 static void model_frame_table_from_host(qlx_model* m, const uint8_t* obs_host, int B) {
   model_workspace(m, B);
-  uint8_t* d_obs = nullptr;
   const size_t bytes = (size_t)B * kFramePix * 4;
-  QLX_HIP(hipMalloc(&d_obs, bytes));
+  DeviceBuffer<uint8_t> d_obs(bytes);
   QLX_HIP(hipMemcpyAsync(d_obs, obs_host, bytes, hipMemcpyHostToDevice, m->stream));
   hipLaunchKernelGGL(k_pack_obs, dim3((B * kFramePix + 255) / 256), dim3(256), 0, m->stream, d_obs, B, m->w.frames);
   hipLaunchKernelGGL(k_frame_table, dim3((B * 4 + 255) / 256), dim3(256), 0, m->stream, m->w.frames, B, m->w.table);
   QLX_HIP(hipGetLastError());
   QLX_HIP(hipStreamSynchronize(m->stream));
-  QLX_HIP(hipFree(d_obs));
 }
 
 static void glorot_host(std::vector<float>& params, uint64_t seed) {
@@ -169,11 +167,11 @@ int32_t qlx_model_create(int32_t arch, uint64_t seed, int32_t device, qlx_model*
       m->device = device;
       QLX_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
       const size_t pb = kNumParams * sizeof(float);
-      QLX_HIP(hipMalloc(&m->d_params, pb));
-      QLX_HIP(hipMalloc(&m->d_m, pb));
-      QLX_HIP(hipMalloc(&m->d_v, pb));
-      QLX_HIP(hipMalloc(&m->d_grads, pb));
-      QLX_HIP(hipMalloc(&m->d_norms, 64));
+      m->d_params.alloc(kNumParams);
+      m->d_m.alloc(kNumParams);
+      m->d_v.alloc(kNumParams);
+      m->d_grads.alloc(kNumParams);
+      m->d_norms.alloc(16);
       m->f32 ? f32_create(m) : bf16_create(m);
       std::vector<float> params;
       glorot_host(params, seed);
@@ -197,7 +195,6 @@ int32_t qlx_model_destroy(qlx_model* m) {
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
     m->f32 ? f32_destroy(m) : bf16_destroy(m);
-    for (void* p : {(void*)m->d_params, (void*)m->d_m, (void*)m->d_v, (void*)m->d_grads, (void*)m->d_norms, m->ws}) (void)hipFree(p);
     if (m->own_stream) (void)hipStreamDestroy(m->stream);
     delete m;
   });

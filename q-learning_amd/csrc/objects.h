@@ -14,15 +14,14 @@ struct qlx_env {
   uint32_t id_offset = 0;         // global id of env 0 (data-parallel ranks own disjoint ids)
   hipStream_t stream = nullptr;   // owned unless adopted by a learner
   bool own_stream = true;
-  qlx_breakout_state* d_state = nullptr;
-  uint32_t* d_ep_steps = nullptr;  // [n] steps taken in the current episode
-  uint8_t* d_obs = nullptr;        // [n][4][7056] ring frames, s2d layout
-  uint64_t* d_hash = nullptr;      // [n] running parity checksum
-  uint32_t* d_flags = nullptr;     // [4] bad-action flag
-  uint8_t* d_tmp_u8 = nullptr;     // [n] staging
-  uint8_t* d_tmp_u8b = nullptr;    // [n]
-  float* d_tmp_f32 = nullptr;      // [n]
-  uint8_t* d_obs_view = nullptr;   // [n][84][84][4] qlx_env_obs's tensor view (allocated on its first call, kept)
+  qlx::DeviceBuffer<qlx_breakout_state> d_state;
+  qlx::DeviceBuffer<uint32_t> d_ep_steps;  // [n] steps taken in the current episode
+  qlx::DeviceBuffer<uint8_t> d_obs;        // [n][4][7056] ring frames, s2d layout
+  qlx::DeviceBuffer<uint64_t> d_hash;      // [n] running parity checksum
+  qlx::DeviceBuffer<uint32_t> d_flags;     // [4] bad-action flag
+  qlx::DeviceBuffer<uint8_t> d_tmp_u8, d_tmp_u8b;   // [n] staging
+  qlx::DeviceBuffer<float> d_tmp_f32;      // [n]
+  qlx::DeviceBuffer<uint8_t> d_obs_view;   // [n][84][84][4] qlx_env_obs's tensor view (allocated on its first call, kept)
   float acos_thr = 0.0f;
   bool hashing = true;
 };
@@ -35,17 +34,22 @@ struct qlx_replay {
   uint64_t total = 0;    // transitions pushed so far
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  uint8_t* d_frames = nullptr;
-  uint8_t* d_action = nullptr;
-  float* d_reward = nullptr;
-  uint8_t* d_done = nullptr;
-  uint32_t* d_epstep = nullptr;
-  uint64_t* d_idx = nullptr;    // scratch for sampling [max_batch]
-  uint32_t idx_cap = 0;
+  qlx::DeviceBuffer<uint8_t> d_frames, d_action, d_done;
+  qlx::DeviceBuffer<float> d_reward;
+  qlx::DeviceBuffer<uint32_t> d_epstep;
+  qlx::DeviceBuffer<uint64_t> d_idx;    // scratch for sampling [max_batch]
   uint64_t len() const { return total < cap ? total : cap; }
 };
 
 namespace qlx {
+// A learner runs its env, replay and models on its own stream: the object's stream (idle: every create ends synchronised)
+// is destroyed, not dropped - a stream holds device memory of its own.
+template <class Obj>
+void adopt_stream(Obj* o, hipStream_t s) {
+  if (o->own_stream) (void)hipStreamDestroy(o->stream);
+  o->stream = s;
+  o->own_stream = false;
+}
 // episode bookkeeping state of a learner (learner.hip k_episode_book)
 struct Book {
   uint64_t episode_count;

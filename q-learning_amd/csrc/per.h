@@ -5,18 +5,19 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "device_memory.h"
+
 namespace qlx {
 
 struct PerState {
   uint64_t cap = 0;
   uint32_t L = 0;               // leaves (power of two >= cap); node i of the heap at d_tree[i], leaves at d_tree + L
-  float* d_tree = nullptr;      // [2L]
-  uint32_t* d_owner = nullptr;  // [L] last-writer claims of the priority write (zero between launches)
-  float* d_max = nullptr;       // largest priority so far (new transitions enter with it), starts at 1
-  float* d_w = nullptr;         // [max samples] IS weights of the sampled batches
-  float* d_td = nullptr;        // [max samples] |TD error| of the sampled transitions
+  DeviceBuffer<float> d_tree;      // [2L]
+  DeviceBuffer<uint32_t> d_owner;  // [L] last-writer claims of the priority write (zero between launches)
+  DeviceBuffer<float> d_max;       // largest priority so far (new transitions enter with it), starts at 1
+  DeviceBuffer<float> d_w;         // [max samples] IS weights of the sampled batches
+  DeviceBuffer<float> d_td;        // [max samples] |TD error| of the sampled transitions
   void init(uint64_t capacity, size_t max_samples);
-  void release();
   float* leaves() const { return d_tree + L; }
 };
 

@@ -194,23 +194,15 @@ void PerState::init(uint64_t capacity, size_t max_samples) {
   QLX_CHECK(capacity >= 1 && capacity <= (1ull << 30), QLX_E_INVALID, "prioritized replay: capacity out of range");
   cap = capacity;
   L = per_leaves(capacity);
-  QLX_HIP(hipMalloc(&d_tree, 2 * (size_t)L * sizeof(float)));
-  QLX_HIP(hipMemset(d_tree, 0, 2 * (size_t)L * sizeof(float)));
-  QLX_HIP(hipMalloc(&d_owner, (size_t)L * sizeof(uint32_t)));
-  QLX_HIP(hipMemset(d_owner, 0, (size_t)L * sizeof(uint32_t)));
-  QLX_HIP(hipMalloc(&d_max, sizeof(float)));
+  d_tree.alloc(2 * (size_t)L);
+  QLX_HIP(hipMemset(d_tree, 0, d_tree.bytes()));
+  d_owner.alloc(L);
+  QLX_HIP(hipMemset(d_owner, 0, d_owner.bytes()));
+  d_max.alloc(1);
   const float one = 1.0f;
   QLX_HIP(hipMemcpy(d_max, &one, sizeof(float), hipMemcpyHostToDevice));
-  if (max_samples) {
-    QLX_HIP(hipMalloc(&d_w, max_samples * sizeof(float)));
-    QLX_HIP(hipMalloc(&d_td, max_samples * sizeof(float)));
-  }
-}
-
-void PerState::release() {
-  for (void* p : {(void*)d_tree, (void*)d_owner, (void*)d_max, (void*)d_w, (void*)d_td})
-    if (p) (void)hipFree(p);
-  d_tree = nullptr; d_owner = nullptr; d_max = nullptr; d_w = nullptr; d_td = nullptr;
+  d_w.alloc(max_samples);
+  d_td.alloc(max_samples);
 }
 
 }  // namespace qlx
@@ -222,19 +214,9 @@ struct qlx_sumtree {
   int device = 0;
   hipStream_t stream = nullptr;
   PerState st;
-  uint64_t* d_idx = nullptr;
-  float* d_w = nullptr;
-  float* d_td = nullptr;
-  size_t scratch = 0;
-  void need(size_t n) {
-    if (n <= scratch) return;
-    for (void* p : {(void*)d_idx, (void*)d_w, (void*)d_td})
-      if (p) (void)hipFree(p);
-    QLX_HIP(hipMalloc(&d_idx, n * 8));
-    QLX_HIP(hipMalloc(&d_w, n * 4));
-    QLX_HIP(hipMalloc(&d_td, n * 4));
-    scratch = n;
-  }
+  DeviceBuffer<uint64_t> d_idx;
+  DeviceBuffer<float> d_w, d_td;
+  void need(size_t n) { d_idx.reserve(n); d_w.reserve(n); d_td.reserve(n); }
 };
 
 extern "C" {
@@ -248,7 +230,6 @@ int32_t qlx_sumtree_create(uint64_t capacity, int32_t device, qlx_sumtree** out)
       QLX_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
       t->st.init(capacity, 0);
     } catch (...) {
-      t->st.release();
       if (t->stream) (void)hipStreamDestroy(t->stream);
       delete t;
       throw;
@@ -261,9 +242,6 @@ int32_t qlx_sumtree_destroy(qlx_sumtree* t) {
   return guard([&] {
     if (!t) return;
     (void)hipStreamSynchronize(t->stream);
-    t->st.release();
-    for (void* p : {(void*)t->d_idx, (void*)t->d_w, (void*)t->d_td})
-      if (p) (void)hipFree(p);
     (void)hipStreamDestroy(t->stream);
     delete t;
   });

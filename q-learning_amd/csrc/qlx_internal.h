@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/qlx.h"
+#include "device_memory.h"
 
 namespace qlx {
 

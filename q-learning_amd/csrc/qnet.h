@@ -55,15 +55,12 @@ struct qlx_model {
   bool f32 = true;   // QLX_ARCH_NATURE_DQN: fp32 (the reference's arithmetic); QLX_ARCH_NATURE_DQN_BF16: bf16 MFMA operands
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  float* d_params = nullptr;   // fp32 master weights, Keras layouts, variables concatenated
-  float* d_m = nullptr;
-  float* d_v = nullptr;
-  float* d_grads = nullptr;
-  float* d_norms = nullptr;
+  qlx::DeviceBuffer<float> d_params;   // fp32 master weights, Keras layouts, variables concatenated
+  qlx::DeviceBuffer<float> d_m, d_v, d_grads, d_norms;
   int64_t iterations = 0;
   uint64_t version = 0;   // bumped by model_pack, i.e. on every write of the weights from outside the optimizer
   float lr = 0.00025f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f, clipnorm = 1.0f;
-  void* ws = nullptr;   // one allocation: the common buffers (w), then the backend's
+  qlx::DeviceBuffer<uint8_t> ws;   // one allocation: the common buffers (w), then the backend's
   int ws_batch = 0;
   int last_batch = 0;
   qlx::CommonWs w;
@@ -145,14 +142,13 @@ void ws_common(qlx_model* m, Arena& a, int B);
 template <class Layout>
 void ws_alloc(qlx_model* m, int B, Layout&& layout) {
   QLX_HIP(hipStreamSynchronize(m->stream));
-  if (m->ws) (void)hipFree(m->ws);
-  m->ws = nullptr;
+  m->ws.release();
   m->ws_batch = 0;
   Arena size;
   ws_common(m, size, B);
   layout(size);
-  QLX_HIP(hipMalloc(&m->ws, size.off));
-  Arena a{(uintptr_t)m->ws};
+  m->ws.alloc(size.off);
+  Arena a{(uintptr_t)m->ws.get()};
   ws_common(m, a, B);
   layout(a);
   m->ws_batch = B;

@@ -58,7 +58,7 @@ struct F32Net {
   int frl_cap = 0;   // samples the row lists hold
   int fchunk = 0;
   // the gradient buffers (dz, weight-gradient chunk slabs) in their own allocation `fgrad`, sized for fgrad_batch
-  void* fgrad = nullptr;
+  DeviceBuffer<uint8_t> fgrad;
   int fgrad_batch = 0;
   float *fdz1 = nullptr, *fdz2 = nullptr, *fdz3 = nullptr, *fdz4 = nullptr;
   float *fslab1 = nullptr, *fslab2 = nullptr, *fslab3 = nullptr;
@@ -634,8 +634,6 @@ void f32_create(qlx_model* m) {
 }
 
 void f32_destroy(qlx_model* m) {
-  if (!m->fp32) return;
-  (void)hipFree(m->fp32->fgrad);
   delete m->fp32;
   m->fp32 = nullptr;
 }
@@ -675,8 +673,7 @@ static void f32_grad_workspace(qlx_model* m, int B) {
   F32Net& w = *m->fp32;
   if (B <= w.fgrad_batch) return;
   QLX_HIP(hipStreamSynchronize(m->stream));
-  if (w.fgrad) (void)hipFree(w.fgrad);
-  w.fgrad = nullptr;
+  w.fgrad.release();
   w.fgrad_batch = 0;
   auto layout = [&](Arena& a) {
     w.fdz1 = a.take<float>((size_t)B * 12800); w.fdz2 = a.take<float>((size_t)B * 5184); w.fdz3 = a.take<float>((size_t)B * 3136);
@@ -690,8 +687,8 @@ static void f32_grad_workspace(qlx_model* m, int B) {
   };
   Arena size;
   layout(size);
-  QLX_HIP(hipMalloc(&w.fgrad, size.off));
-  Arena a{(uintptr_t)w.fgrad};
+  w.fgrad.alloc(size.off);
+  Arena a{(uintptr_t)w.fgrad.get()};
   layout(a);
   w.fgrad_batch = B;
 }

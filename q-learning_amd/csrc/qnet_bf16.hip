@@ -30,16 +30,16 @@ constexpr size_t kWgradSlabFloats = (size_t)9600 * 1024;
 
 struct Bf16Net {
   // bf16 MFMA operand copies of the master weights ([n][k], k contiguous)
-  bf16 *wf0 = nullptr, *wf1 = nullptr, *wb1 = nullptr, *wf2 = nullptr, *wb2 = nullptr, *wb3 = nullptr;
+  DeviceBuffer<bf16> wf0, wf1, wb1, wf2, wb2, wb3;
   // k_sumsq: gradient ranges and their partials
   int n_ranges = 0;
-  int64_t *d_rbeg = nullptr, *d_rend = nullptr;
-  float* d_partial = nullptr;
-  int* d_var_first = nullptr;
+  DeviceBuffer<int64_t> d_rbeg, d_rend;
+  DeviceBuffer<float> d_partial;
+  DeviceBuffer<int> d_var_first;
   // clip_by_norm partials written by the gradient producers themselves (fc1 wgrad tiles, conv slab reduction
   // blocks, fc2 wgrad blocks): while they belong to d_grads as it stands the k_sumsq pass is skipped
-  float* d_sqf = nullptr;
-  int* d_sqf_first = nullptr;
+  DeviceBuffer<float> d_sqf;
+  DeviceBuffer<int> d_sqf_first;
   // Update-tail protocol.  fused_valid: this model's backward was the last writer of d_grads, so d_sqf holds that
   // gradient's partials (set at the end of bf16_backward_conv, cleared by bf16_gradient_replaced alone: Adam reads
   // d_grads and leaves it and d_sqf as they are).  norms_fused: bf16_norms' decision for the bf16_adam that follows -
@@ -47,8 +47,8 @@ struct Bf16Net {
   bool fused_valid = false;
   bool norms_fused = false;
   // XCD-aware block -> tile table of the fc1 backward launch (built per batch size, fc1_bwd_map)
-  int* d_fc1bwd_map = nullptr;
-  int fc1bwd_map_B = -1, fc1bwd_grid = 0, fc1bwd_cap = 0;
+  DeviceBuffer<int> d_fc1bwd_map;
+  int fc1bwd_map_B = -1, fc1bwd_grid = 0;
   // conv1 weight gradient as channel-half blocks (k_conv1_wgrad_h); QLX_CONV1_HALVES=0 at create time selects the
   // one-block-per-chunk k_conv1_wgrad (bit-identical gradients)
   bool conv1_halves = true;
@@ -397,11 +397,9 @@ static void fc1_bwd_map(Bf16Net& n, const PW& Pw, const PD& Pd, int extra, hipSt
   std::vector<int> map(8 * per, -1);
   for (int x = 0; x < 8; ++x)
     for (size_t l = 0; l < lists[x].size(); ++l) map[l * 8 + x] = lists[x][l];
-  if ((int)map.size() > n.fc1bwd_cap) {
+  if (map.size() > n.d_fc1bwd_map.size()) {
     QLX_HIP(hipStreamSynchronize(s));
-    if (n.d_fc1bwd_map) (void)hipFree(n.d_fc1bwd_map);
-    QLX_HIP(hipMalloc(&n.d_fc1bwd_map, map.size() * sizeof(int)));
-    n.fc1bwd_cap = (int)map.size();
+    n.d_fc1bwd_map.reset(map.size());
   }
   QLX_HIP(hipMemcpy(n.d_fc1bwd_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
   n.fc1bwd_grid = (int)map.size();
@@ -558,12 +556,12 @@ void bf16_create(qlx_model* m) {
   Bf16Net& n = *(m->bf16 = new Bf16Net);
   const char* ch = std::getenv("QLX_CONV1_HALVES");
   n.conv1_halves = !(ch && ch[0] == '0');
-  QLX_HIP(hipMalloc(&n.wf0, 32 * 256 * 2));
-  QLX_HIP(hipMalloc(&n.wf1, 64 * 512 * 2));
-  QLX_HIP(hipMalloc(&n.wb1, 32 * 1024 * 2));
-  QLX_HIP(hipMalloc(&n.wf2, 64 * 576 * 2));
-  QLX_HIP(hipMalloc(&n.wb2, 64 * 576 * 2));
-  QLX_HIP(hipMalloc(&n.wb3, 3136 * 512 * 2));
+  n.wf0.alloc(32 * 256);
+  n.wf1.alloc(64 * 512);
+  n.wb1.alloc(32 * 1024);
+  n.wf2.alloc(64 * 576);
+  n.wb2.alloc(64 * 576);
+  n.wb3.alloc(3136 * 512);
   // norm ranges: chunks of <= 2048 elements (~830 blocks) that never cross a variable
   std::vector<int64_t> rb, re;
   std::vector<int> vf(kNumVars + 1, 0);
@@ -580,14 +578,14 @@ void bf16_create(qlx_model* m) {
   for (int v = 0; v < kNumVars; ++v)
     QLX_CHECK(vf[v + 1] - vf[v] <= kAdamMaxPartials && kSqSlots[v] <= kAdamMaxPartials, QLX_E_STATE, "k_adam partial bound");
   n.n_ranges = (int)rb.size();
-  QLX_HIP(hipMalloc(&n.d_rbeg, rb.size() * 8));
-  QLX_HIP(hipMalloc(&n.d_rend, re.size() * 8));
-  QLX_HIP(hipMalloc(&n.d_partial, rb.size() * 4));
-  QLX_HIP(hipMalloc(&n.d_var_first, vf.size() * 4));
+  n.d_rbeg.alloc(rb.size());
+  n.d_rend.alloc(re.size());
+  n.d_partial.alloc(rb.size());
+  n.d_var_first.alloc(vf.size());
   std::vector<int> sf(kNumVars + 1);
   for (int v = 0; v <= kNumVars; ++v) sf[v] = v < kNumVars ? sq_first(v) : sq_first(kNumVars - 1) + kSqSlots[kNumVars - 1];
-  QLX_HIP(hipMalloc(&n.d_sqf, sf[kNumVars] * 4));
-  QLX_HIP(hipMalloc(&n.d_sqf_first, sf.size() * 4));
+  n.d_sqf.alloc(sf[kNumVars]);
+  n.d_sqf_first.alloc(sf.size());
   QLX_HIP(hipMemcpy(n.d_sqf_first, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
   QLX_HIP(hipMemset(n.d_sqf, 0, sf[kNumVars] * 4));
   QLX_HIP(hipMemcpy(n.d_rbeg, rb.data(), rb.size() * 8, hipMemcpyHostToDevice));
@@ -596,13 +594,7 @@ void bf16_create(qlx_model* m) {
 }
 
 void bf16_destroy(qlx_model* m) {
-  Bf16Net* n = m->bf16;
-  if (!n) return;
-  for (void* p : {(void*)n->wf0, (void*)n->wf1, (void*)n->wb1, (void*)n->wf2, (void*)n->wb2, (void*)n->wb3, (void*)n->d_rbeg,
-                  (void*)n->d_rend, (void*)n->d_partial, (void*)n->d_var_first, (void*)n->d_sqf, (void*)n->d_sqf_first,
-                  (void*)n->d_fc1bwd_map})
-    (void)hipFree(p);
-  delete n;
+  delete m->bf16;
   m->bf16 = nullptr;
 }
 
@@ -668,8 +660,8 @@ void bf16_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t 
     set_lds_attr(k_trunk_fwd<true>, kTrunkFwdLds);
     set_lds_attr(k_trunk_fwd<false>, kTrunkFwdLds);
     auto kern = store_acts ? k_trunk_fwd<true> : k_trunk_fwd<false>;
-    hipExtLaunchKernelGGL(kern, dim3(trunk_grid(B)), dim3(kTrunkThreads), kTrunkFwdLds, s, ea, eb, 0u, table, B, w.wf0, w.wf1,
-                          w.wf2, p + var_offset(1), p + var_offset(3), p + var_offset(5), w.a1, w.a2, w.a3);
+    hipExtLaunchKernelGGL(kern, dim3(trunk_grid(B)), dim3(kTrunkThreads), kTrunkFwdLds, s, ea, eb, 0u, table, B, w.wf0.get(),
+                          w.wf1.get(), w.wf2.get(), p + var_offset(1), p + var_offset(3), p + var_offset(5), w.a1, w.a2, w.a3);
   }
   {  // fc1: M = B, N = 512, K = 3136.  Small batches split K into kFc1Split fp32 slabs (reduced with bias +
      // ReLU in fixed order) to fill the chip; from 64 M tiles on (B >= 8192) one pass with the epilogue fused

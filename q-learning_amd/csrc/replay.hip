@@ -195,12 +195,11 @@ int32_t qlx_replay_create(uint64_t capacity, uint32_t n_envs, int32_t device, ql
       r->n = n_envs;
       r->F = capacity + 4ull * n_envs;
       QLX_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-      const hipError_t e = hipMalloc(&r->d_frames, r->F * kFramePix);
-      if (e != hipSuccess) { delete r; throw Error{QLX_E_OOM, "replay frame store allocation failed"}; }
-      QLX_HIP(hipMalloc(&r->d_action, capacity));
-      QLX_HIP(hipMalloc(&r->d_reward, capacity * sizeof(float)));
-      QLX_HIP(hipMalloc(&r->d_done, capacity));
-      QLX_HIP(hipMalloc(&r->d_epstep, capacity * sizeof(uint32_t)));
+      r->d_frames.alloc(r->F * kFramePix);
+      r->d_action.alloc(capacity);
+      r->d_reward.alloc(capacity);
+      r->d_done.alloc(capacity);
+      r->d_epstep.alloc(capacity);
     } catch (...) {
       qlx_replay_destroy(r);
       throw;
@@ -214,8 +213,6 @@ int32_t qlx_replay_destroy(qlx_replay* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     (void)hipStreamSynchronize(r->stream);
-    (void)hipFree(r->d_frames); (void)hipFree(r->d_action); (void)hipFree(r->d_reward); (void)hipFree(r->d_done);
-    (void)hipFree(r->d_epstep); (void)hipFree(r->d_idx);
     if (r->own_stream) (void)hipStreamDestroy(r->stream);
     delete r;
   });
@@ -255,11 +252,7 @@ int32_t qlx_replay_sample_distinct(qlx_replay* r, uint64_t seed, uint32_t update
     QLX_CHECK(r->len() >= batch, QLX_E_INVALID, "replay holds fewer transitions than the batch");
     QLX_HIP(hipSetDevice(r->device));
     QLX_HIP(hipDeviceSynchronize());
-    if (r->idx_cap < batch) {
-      (void)hipFree(r->d_idx);
-      QLX_HIP(hipMalloc(&r->d_idx, batch * sizeof(uint64_t)));
-      r->idx_cap = batch;
-    }
+    r->d_idx.reserve(batch);
     replay_launch_sample(r, r->stream, seed, update_idx, 1, rank, batch, r->d_idx);
     QLX_HIP(hipMemcpyAsync(out, r->d_idx, batch * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
     QLX_HIP(hipStreamSynchronize(r->stream));
@@ -273,16 +266,10 @@ int32_t qlx_replay_get_many(qlx_replay* r, const uint64_t* indices, uint32_t B, 
     for (uint32_t b = 0; b < B; ++b) QLX_CHECK(indices[b] < r->len(), QLX_E_INVALID, "index out of range");
     QLX_HIP(hipSetDevice(r->device));
     QLX_HIP(hipDeviceSynchronize());
-    uint64_t* d_idx = nullptr;
-    uint8_t* d_out = nullptr;
-    float* d_r = nullptr;
-    uint8_t *d_a = nullptr, *d_d = nullptr;
     const size_t bytes = (size_t)B * kFramePix * kSlots;
-    QLX_HIP(hipMalloc(&d_idx, B * sizeof(uint64_t)));
-    QLX_HIP(hipMalloc(&d_out, bytes));
-    QLX_HIP(hipMalloc(&d_r, B * sizeof(float)));
-    QLX_HIP(hipMalloc(&d_a, B));
-    QLX_HIP(hipMalloc(&d_d, B));
+    DeviceBuffer<uint64_t> d_idx(B);
+    DeviceBuffer<uint8_t> d_out(bytes), d_a(B), d_d(B);
+    DeviceBuffer<float> d_r(B);
     QLX_HIP(hipMemcpyAsync(d_idx, indices, B * sizeof(uint64_t), hipMemcpyHostToDevice, r->stream));
     const ReplayView v = replay_view(r);
     const size_t total = (size_t)B * kFramePix;
@@ -300,7 +287,6 @@ int32_t qlx_replay_get_many(qlx_replay* r, const uint64_t* indices, uint32_t B, 
     if (rewards) QLX_HIP(hipMemcpyAsync(rewards, d_r, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
     if (dones) QLX_HIP(hipMemcpyAsync(dones, d_d, B, hipMemcpyDeviceToHost, r->stream));
     QLX_HIP(hipStreamSynchronize(r->stream));
-    (void)hipFree(d_idx); (void)hipFree(d_out); (void)hipFree(d_r); (void)hipFree(d_a); (void)hipFree(d_d);
   });
 }
 
@@ -312,31 +298,20 @@ int32_t qlx_replay_nstep(qlx_replay* r, const uint64_t* indices, uint32_t B, uin
     for (uint32_t b = 0; b < B; ++b) QLX_CHECK(indices[b] < r->len(), QLX_E_INVALID, "index out of range");
     QLX_HIP(hipSetDevice(r->device));
     QLX_HIP(hipDeviceSynchronize());
-    // one allocation: idx u64 [B] | last u64 [B] | ret f32 [B] | disc f32 [B] | steps u32 [B] | term u8 [B]
-    uint8_t* d = nullptr;
-    QLX_HIP(hipMalloc(&d, (size_t)B * 29));
-    uint64_t* d_idx = reinterpret_cast<uint64_t*>(d);
-    uint64_t* d_last = d_idx + B;
-    float* d_ret = reinterpret_cast<float*>(d_last + B);
-    float* d_disc = d_ret + B;
-    uint32_t* d_steps = reinterpret_cast<uint32_t*>(d_disc + B);
-    uint8_t* d_term = reinterpret_cast<uint8_t*>(d_steps + B);
-    try {
-      QLX_HIP(hipMemcpyAsync(d_idx, indices, B * sizeof(uint64_t), hipMemcpyHostToDevice, r->stream));
-      hipLaunchKernelGGL(k_replay_nstep, dim3((B + 255) / 256), dim3(256), 0, r->stream, replay_view(r), d_idx, B, n_step, gamma,
-                         d_ret, d_disc, d_last, d_term, d_steps);
-      QLX_HIP(hipGetLastError());
-      if (returns) QLX_HIP(hipMemcpyAsync(returns, d_ret, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-      if (discounts) QLX_HIP(hipMemcpyAsync(discounts, d_disc, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-      if (last_indices) QLX_HIP(hipMemcpyAsync(last_indices, d_last, B * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
-      if (terminals) QLX_HIP(hipMemcpyAsync(terminals, d_term, B, hipMemcpyDeviceToHost, r->stream));
-      if (steps) QLX_HIP(hipMemcpyAsync(steps, d_steps, B * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-      QLX_HIP(hipStreamSynchronize(r->stream));
-    } catch (...) {
-      (void)hipFree(d);
-      throw;
-    }
-    (void)hipFree(d);
+    DeviceBuffer<uint64_t> d_idx(B), d_last(B);
+    DeviceBuffer<float> d_ret(B), d_disc(B);
+    DeviceBuffer<uint32_t> d_steps(B);
+    DeviceBuffer<uint8_t> d_term(B);
+    QLX_HIP(hipMemcpyAsync(d_idx, indices, B * sizeof(uint64_t), hipMemcpyHostToDevice, r->stream));
+    hipLaunchKernelGGL(k_replay_nstep, dim3((B + 255) / 256), dim3(256), 0, r->stream, replay_view(r), d_idx, B, n_step, gamma,
+                       d_ret, d_disc, d_last, d_term, d_steps);
+    QLX_HIP(hipGetLastError());
+    if (returns) QLX_HIP(hipMemcpyAsync(returns, d_ret, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    if (discounts) QLX_HIP(hipMemcpyAsync(discounts, d_disc, B * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    if (last_indices) QLX_HIP(hipMemcpyAsync(last_indices, d_last, B * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+    if (terminals) QLX_HIP(hipMemcpyAsync(terminals, d_term, B, hipMemcpyDeviceToHost, r->stream));
+    if (steps) QLX_HIP(hipMemcpyAsync(steps, d_steps, B * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    QLX_HIP(hipStreamSynchronize(r->stream));
   });
 }
 

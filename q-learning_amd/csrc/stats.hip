@@ -59,9 +59,8 @@ __global__ __launch_bounds__(256) void k_action_counts(const uint8_t* actions, u
 
 void action_counts(hipStream_t s, const uint8_t* d_actions, uint64_t len, uint32_t n_actions, std::vector<uint64_t>& out) {
   QLX_CHECK(n_actions >= 1 && n_actions < 256, QLX_E_INVALID, "bad action space");
-  unsigned long long* d = nullptr;
-  QLX_HIP(hipMalloc(reinterpret_cast<void**>(&d), (n_actions + 1) * sizeof(unsigned long long)));
-  QLX_HIP(hipMemsetAsync(d, 0, (n_actions + 1) * sizeof(unsigned long long), s));
+  DeviceBuffer<unsigned long long> d(n_actions + 1);
+  QLX_HIP(hipMemsetAsync(d, 0, d.bytes(), s));
   if (len) {
     const uint64_t blocks = std::min<uint64_t>(1024, std::max<uint64_t>(1, (len / 16 + 255) / 256));
     hipLaunchKernelGGL(k_action_counts, dim3((uint32_t)blocks), dim3(256), 0, s, d_actions, len, n_actions, d);
@@ -70,7 +69,6 @@ void action_counts(hipStream_t s, const uint8_t* d_actions, uint64_t len, uint32
   std::vector<unsigned long long> h(n_actions + 1);
   QLX_HIP(hipMemcpyAsync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   QLX_HIP(hipStreamSynchronize(s));
-  QLX_HIP(hipFree(d));
   QLX_CHECK(h[n_actions] == 0, QLX_E_STATE, "replay holds an action outside the action space");
   out.assign(h.begin(), h.begin() + n_actions);
 }

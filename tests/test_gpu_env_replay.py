@@ -121,3 +121,27 @@ def test_sample_distinct_matches_oracle(length, B):
         ref = O.sample_distinct(77, u, 0, length, B)
         assert np.array_equal(got, ref)
         assert len(set(got.tolist())) == B
+
+
+def test_replay_allocation_failure_is_clean():
+    """A frame store no device has is refused as out of memory (status -3) and leaves nothing behind: no device memory,
+    and no stale runtime error for the launch checks of the next object."""
+    import torch
+    qlx = _qlx()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(5):
+        with pytest.raises(qlx.QlError, match="status -3"):
+            qlx.ReplayBuffer(capacity=1 << 44, n_envs=1)
+    n = 4
+    env = qlx.BreakoutEnvironment(n_envs=n, seed=ENV_SEED)
+    rb = qlx.ReplayBuffer(capacity=64, n_envs=n)
+    zeros = np.zeros(n, np.uint8)
+    for _ in range(8):
+        _, r, d = env.step(zeros)
+        rb.add(env, zeros, r, d)
+    assert len(rb) == 32
+    got = rb.sample_distinct(seed=77, update_idx=0, batch=8)
+    assert len(set(got.tolist())) == 8 and (got < 32).all()
+    rb.close()
+    env.close()
+    assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)

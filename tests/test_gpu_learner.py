@@ -502,3 +502,20 @@ def test_invalid_parameters_fail_loudly():
             qlx.SelfDrivingQLearner(qlx.Parameter(n_envs=16, batch_size=32, history_buffer_len=1000, flags=qlx.PER,
                                                   per_eps=-1.0))
     assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)
+
+
+def test_create_destroy_returns_memory():
+    """Every learner gives back the device memory it took (allocator slack as in test_invalid_parameters_fail_loudly): a
+    buffer that no owner releases shows up as free memory going down with every create / close."""
+    import torch
+    qlx = _qlx()
+    base = dict(n_envs=4, batch_size=8, history_buffer_len=64)
+    cases = [(qlx.SelfDrivingQLearner, dict(n_step=3)), (qlx.SelfDrivingQLearner, dict(flags=qlx.PER)),
+             (qlx.BallGameLearner, dict()), (qlx.BallGameLearner, dict(flags=qlx.PER))]   # (n_step is Breakout's alone)
+    free0 = torch.cuda.mem_get_info()[0]
+    for cls, kw in cases:
+        for _ in range(10):
+            L = cls(qlx.Parameter(**base, **kw))
+            L.vector_step()
+            L.close()
+    assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)

@@ -50,6 +50,18 @@ def test_sumtree_sample_matches_oracle(cap, length):
         t.sample(1, 0, 1, 0, cap + 1, 0.4, 8)
 
 
+def test_sumtree_scratch_regrow():
+    """The sample scratch grows on demand (qlx_sumtree::need): a draw after a larger one equals the same draw before it."""
+    qlx = _qlx()
+    t = qlx.SumTree(64)
+    t.set_leaves(np.arange(1, 65, dtype=np.float32))
+    first = t.sample(5, 0, 1, 0, 64, 0.4, 8)
+    big = t.sample(5, 0, 8, 0, 64, 0.4, 8)
+    third = t.sample(5, 0, 1, 0, 64, 0.4, 8)
+    assert same(first[0], third[0]) and same(first[1], third[1])
+    assert big[0].shape == (8, 8) and big[0].max() < 64
+
+
 def test_sumtree_update_last_writer_wins():
     qlx = _qlx()
     cap = 1000
