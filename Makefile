@@ -15,7 +15,8 @@ STRICT := -ffp-contract=off
 LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
 OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
-        $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o
+        $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o \
+        $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
 
@@ -75,6 +76,13 @@ $(OUT)/obj/per.o: $(SRC)/per.hip $(HDRS) | $(OUT)/obj
 
 $(OUT)/obj/stats.o: $(SRC)/stats.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+
+# snapshots: the container and the host reference of the frame codec (host only, no HIP call), and the codec's kernels
+$(OUT)/obj/snapshot_format.o: $(SRC)/snapshot_format.cpp $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OUT)/obj/frame_codec.o: $(SRC)/frame_codec.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OUT)/libqlx.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) $(OBJS) $(LDFLAGS) -o $@

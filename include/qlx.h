@@ -348,6 +348,43 @@ qlx_env* qlx_evaluator_env(qlx_evaluator* ev);
  * env, replay, counters, RNG positions, memo and profiler scopes are untouched.  Local to the rank (no collective). */
 int32_t qlx_learner_evaluate(qlx_learner* l, const qlx_eval_config* cfg, qlx_eval_summary* out);
 
+/* ---------------- Snapshots (beyond the reference) ----------------
+ * A learner (or a replay alone) saved to one file and created again from it, so that a run continues bit for bit like one
+ * that never stopped: every random draw here is a function of counters, and the file holds those counters with the env,
+ * replay, both models, the episode books, the prioritized-replay leaves and the target memo (DESIGN.md "Snapshots").
+ * Frames cross PCIe and reach the file packed on the GPU (QLX_FRAME_CODEC_BITMAP: a bitmap of the non-zero bytes and
+ * those bytes, lossless); QLX_SNAPSHOT_PACK=0, read at save, stores them raw; a load accepts both.
+ * Errors: arguments QLX_E_INVALID; anything wrong with a file (missing, short, bad magic, version, kind, a section past
+ * the end, a checksum or the codec's own consistency) QLX_E_IO with a message naming it; a failed load creates nothing.
+ * A save writes path + ".tmp" and renames it over path; two saves of equal state are byte-identical.  Not saved: the
+ * profiler, the log callback, the RCCL communicator (a snapshot is local to its rank; qlx_learner_dist_init may follow
+ * a load) and the last step's outputs (qlx_learner_last reports 0 updates until the next vector step). */
+#define QLX_SNAPSHOT_VERSION 1
+#define QLX_SNAPSHOT_LEARNER 1
+#define QLX_SNAPSHOT_REPLAY  2
+#define QLX_FRAME_CODEC_RAW    0
+#define QLX_FRAME_CODEC_BITMAP 1
+
+typedef struct qlx_snapshot_info {
+  uint32_t format_version, kind, frame_codec, reserved;
+  uint64_t step_count, vec_steps, update_count, episode_count, replay_len, replay_total;
+  uint64_t frames, frame_bytes_raw, frame_bytes_stored, file_bytes;
+  qlx_params params;            /* kind LEARNER; zero for REPLAY except n_envs, history_buffer_len */
+} qlx_snapshot_info;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_snapshot_info) == 504, "qlx_snapshot_info ABI size");
+#endif
+
+int32_t qlx_snapshot_info_read(const char* path, qlx_snapshot_info* out);        /* host only, no device */
+int32_t qlx_learner_save(qlx_learner* l, const char* path);                      /* synchronises; local to the rank */
+int32_t qlx_learner_load(const char* path, int32_t device, qlx_learner** out);   /* creates the learner from the file */
+int32_t qlx_replay_save(qlx_replay* rb, const char* path);
+int32_t qlx_replay_load(const char* path, int32_t device, qlx_replay** out);
+/* test hook of the frame codec: host frames [n][7056] -> device -> pack -> packed_out (host, cap bytes) -> device ->
+ * unpack -> frames_out; *packed_bytes = the packed size (QLX_E_INVALID when cap is smaller).  codec as above. */
+int32_t qlx_frame_codec_roundtrip(const uint8_t* frames, uint32_t n, int32_t codec, int32_t device,
+                                  uint8_t* packed_out, uint64_t cap, uint64_t* packed_bytes, uint8_t* frames_out);
+
 /* ---------------- DBSCAN over f32 (src/ql/src/util/dbscan.rs:209-341) ----------------
  * cluster_analysis(values, max_neighbor_distance, core_point_min_neighbors) with Distance = |a - b|, exact, in
  * O(n log n): labels[i] = cluster position (clusters ordered by lowest member index, as the reference returns

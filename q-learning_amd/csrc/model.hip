@@ -338,6 +338,26 @@ int32_t qlx_model_write_checkpoint(qlx_model* m, const char* path) {
 }
 
 // weights, Adam slots and the iteration count as read from a file, onto the device
+static void model_restore(qlx_model* m, const float* w, const float* mm, const float* vv, int64_t iterations);
+
+}  // extern "C"
+
+namespace qlx {
+void model_state_get(qlx_model* m, float* out3, int64_t* iterations) {
+  QLX_HIP(hipSetDevice(m->device));
+  QLX_HIP(hipStreamSynchronize(m->stream));
+  QLX_HIP(hipMemcpy(out3, m->d_params, kNumParams * 4, hipMemcpyDeviceToHost));
+  QLX_HIP(hipMemcpy(out3 + kNumParams, m->d_m, kNumParams * 4, hipMemcpyDeviceToHost));
+  QLX_HIP(hipMemcpy(out3 + 2 * kNumParams, m->d_v, kNumParams * 4, hipMemcpyDeviceToHost));
+  *iterations = m->iterations;
+}
+void model_state_put(qlx_model* m, const float* in3, int64_t iterations) {
+  model_restore(m, in3, in3 + kNumParams, in3 + 2 * kNumParams, iterations);
+}
+}  // namespace qlx
+
+extern "C" {
+
 static void model_restore(qlx_model* m, const float* w, const float* mm, const float* vv, int64_t iterations) {
   QLX_HIP(hipSetDevice(m->device));
   QLX_HIP(hipStreamSynchronize(m->stream));

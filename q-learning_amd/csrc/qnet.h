@@ -137,6 +137,11 @@ void model_norms_dense(qlx_model* m, hipStream_t s, float scale);
 void model_norms(qlx_model* m, hipStream_t s, float scale);
 void model_adam(qlx_model* m, hipStream_t s, float scale);
 
+// weights, Adam m and v ([3][kNumParams]) and the iteration count to / from host arrays (snapshots); put restores like a
+// checkpoint read: the operand copies are rebuilt from the masters (model_pack) and the stream is synchronised
+void model_state_get(qlx_model* m, float* out3, int64_t* iterations);
+void model_state_put(qlx_model* m, const float* in3, int64_t iterations);
+
 // (Re)allocates m->ws for B samples: the common buffers, then whatever `layout` takes from the arena for the backend
 void ws_common(qlx_model* m, Arena& a, int B);
 template <class Layout>

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "crc32c.h"
 #include "objects.h"
 #include "qlx_internal.h"
 
@@ -28,22 +29,7 @@ namespace qlx {
 
 namespace {
 
-uint32_t crc32c_table[256];
-bool crc_init = false;
-
-uint32_t crc32c(const uint8_t* p, size_t n) {   // Castagnoli, reflected 0x82F63B78
-  if (!crc_init) {
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-      crc32c_table[i] = c;
-    }
-    crc_init = true;
-  }
-  uint32_t c = 0xFFFFFFFFu;
-  for (size_t i = 0; i < n; ++i) c = crc32c_table[(c ^ p[i]) & 0xFF] ^ (c >> 8);
-  return c ^ 0xFFFFFFFFu;
-}
+// (crc32c itself: crc32c.h, shared with the snapshot container)
 uint32_t crc_mask(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }   // leveldb / tf crc32c::Mask
 
 struct Reader {

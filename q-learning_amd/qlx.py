@@ -105,6 +105,21 @@ class EvalSummary(C.Structure):
 
 EVAL_MAX_ENVS = 8192   # QLX_EVAL_MAX_ENVS
 
+SNAPSHOT_VERSION = 1      # QLX_SNAPSHOT_VERSION
+SNAPSHOT_LEARNER = 1      # QLX_SNAPSHOT_LEARNER
+SNAPSHOT_REPLAY = 2       # QLX_SNAPSHOT_REPLAY
+FRAME_CODEC_RAW = 0       # QLX_FRAME_CODEC_RAW
+FRAME_CODEC_BITMAP = 1    # QLX_FRAME_CODEC_BITMAP: a bitmap of each frame's non-zero bytes + those bytes
+FRAME_BYTES = FRAME * FRAME
+
+
+class SnapshotInfo(C.Structure):
+    """qlx_snapshot_info (snapshots, beyond the reference)"""
+    _fields_ = [(k, C.c_uint32) for k in ("format_version", "kind", "frame_codec", "reserved")] + [
+        (k, C.c_uint64) for k in ("step_count", "vec_steps", "update_count", "episode_count", "replay_len",
+                                  "replay_total", "frames", "frame_bytes_raw", "frame_bytes_stored", "file_bytes")] + [
+        ("params", Params)]
+
 
 def _eval_config(n_envs, episodes_per_env=1, max_steps_per_episode=10_000, epsilon=0.0, env_seed=0x51A5EED,
                  policy_seed=1, poll_steps=0, flags=0):
@@ -190,6 +205,10 @@ def lib():
         "qlx_evaluator_run": ([vp, vp, C.POINTER(EvalSummary)], i32),
         "qlx_evaluator_episodes": ([vp, vp, vp, vp, vp], i32), "qlx_evaluator_env": ([vp], vp),
         "qlx_learner_evaluate": ([vp, C.POINTER(EvalConfig), C.POINTER(EvalSummary)], i32),
+        "qlx_snapshot_info_read": ([C.c_char_p, C.POINTER(SnapshotInfo)], i32),
+        "qlx_learner_save": ([vp, C.c_char_p], i32), "qlx_learner_load": ([C.c_char_p, i32, C.POINTER(vp)], i32),
+        "qlx_replay_save": ([vp, C.c_char_p], i32), "qlx_replay_load": ([C.c_char_p, i32, C.POINTER(vp)], i32),
+        "qlx_frame_codec_roundtrip": ([vp, u32, i32, i32, vp, u64, C.POINTER(u64), vp], i32),
         "qlx_dbscan_f32": ([vp, u64, C.c_float, u64, vp, C.POINTER(u64)], i32),
         "qlx_dbscan_f32_format": ([vp, u64, C.c_float, u64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)], i32),
         "qlx_sumtree_create": ([u64, i32, C.POINTER(vp)], i32), "qlx_sumtree_destroy": ([vp], i32),
@@ -285,6 +304,28 @@ def model_hparams(ballgame=False):
     out = np.zeros(5, np.float32)
     _check((lib().qlx_bg_model_hparams if ballgame else lib().qlx_model_hparams)(_p(out)))
     return out
+
+
+def snapshot_info(path):
+    """qlx_snapshot_info of a snapshot file as a dict (`params` is a Params); reads the file on the host, no device"""
+    info = SnapshotInfo()
+    _check(lib().qlx_snapshot_info_read(os.fspath(path).encode(), C.byref(info)))
+    d = {k: getattr(info, k) for k, _ in SnapshotInfo._fields_ if k != "params"}
+    d["params"] = Params.from_buffer_copy(info.params)
+    return d
+
+
+def frame_codec_roundtrip(frames, codec=FRAME_CODEC_BITMAP, device=0):
+    """Test hook of the snapshot frame codec: frames [n][7056] u8 are packed on the GPU, brought to the host, sent back
+    and unpacked; (packed bytes as a u8 array, the unpacked frames)"""
+    x = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, FRAME_BYTES)
+    n = x.shape[0]
+    cap = n * (FRAME_BYTES + FRAME_BYTES // 8) + 16 * (n // 512 + 1) + 2 * n + 64   # the worst case: every byte non-zero
+    packed = np.zeros(cap, np.uint8)
+    out = np.zeros_like(x)
+    nb = C.c_uint64()
+    _check(lib().qlx_frame_codec_roundtrip(_p(x), n, codec, device, _p(packed), cap, C.byref(nb), _p(out)))
+    return packed[:nb.value].copy(), out
 
 
 def exported_symbols():
@@ -395,6 +436,19 @@ class ReplayBuffer:
         d = np.zeros(B, np.uint8)
         _check(lib().qlx_replay_get_many(self.h, _p(idx), B, _p(s), _p(sn), _p(a), _p(r), _p(d)))
         return dict(state=s, state_next=sn, action=a, reward=r, done=d.astype(bool))
+
+    def save(self, path):
+        """the replay alone to a snapshot file (qlx_replay_save)"""
+        _check(lib().qlx_replay_save(self.h, os.fspath(path).encode()))
+
+    @classmethod
+    def load(cls, path, device=0):
+        """a replay created from a file ReplayBuffer.save wrote"""
+        h = C.c_void_p()
+        _check(lib().qlx_replay_load(os.fspath(path).encode(), device, C.byref(h)))
+        rb = cls(0, 0, handle=h.value)
+        rb._owned = True
+        return rb
 
     def nstep(self, indices, n_step, gamma):
         """n-step return windows of the transitions at `indices` (qlx_replay_nstep): returns = sum_{j<m} gamma^j r_j,
@@ -552,11 +606,13 @@ class SelfDrivingQLearner(_LearningStats):
     """SelfDrivingQLearner with n parallel envs on one GPU (vector-step generalisation)."""
     _n_actions = 3
 
-    def __init__(self, param, device=0):
+    def __init__(self, param, device=0, handle=None):
         self.param = param
-        h = C.c_void_p()
-        _check(lib().qlx_learner_create(C.byref(param), device, C.byref(h)))
-        self.h = h.value
+        if handle is None:
+            h = C.c_void_p()
+            _check(lib().qlx_learner_create(C.byref(param), device, C.byref(h)))
+            handle = h.value
+        self.h = handle
         self.environment = BreakoutEnvironment(handle=lib().qlx_learner_env(self.h))
         self.replay_buffer = ReplayBuffer(0, 0, handle=lib().qlx_learner_replay(self.h))
         self.model = DeepQLearningModel(handle=lib().qlx_learner_model(self.h, 0))
@@ -568,6 +624,19 @@ class SelfDrivingQLearner(_LearningStats):
         self.h = None
 
     __del__ = close
+
+    def save(self, path):
+        """Snapshot of the whole learner between vector steps (qlx_learner_save): a learner loaded from it continues
+        bit for bit like this one.  Written to path + ".tmp" and renamed; QLX_SNAPSHOT_PACK=0 stores the frames raw."""
+        _check(lib().qlx_learner_save(self.h, os.fspath(path).encode()))
+
+    @classmethod
+    def load(cls, path, device=0):
+        """the learner a snapshot file holds (qlx_learner_load); its Parameter comes from the file"""
+        param = snapshot_info(path)["params"]
+        h = C.c_void_p()
+        _check(lib().qlx_learner_load(os.fspath(path).encode(), device, C.byref(h)))
+        return cls(param, handle=h.value)
 
     def vector_step(self):
         _check(lib().qlx_learner_vector_step(self.h))
