@@ -16,7 +16,7 @@ LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
 OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
         $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o \
-        $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o
+        $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o $(OUT)/obj/learner_core.o $(OUT)/obj/learner_snapshot.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
 
@@ -57,6 +57,14 @@ $(OUT)/obj/qnet32.o: $(SRC)/qnet32.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(Q32SCHED) $(Q32VFORM) -c $< -o $@
 
 $(OUT)/obj/learner.o: $(SRC)/learner.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+
+# the environment-independent learner core (its two kernels came out of learner.hip: the same flags; the f32 running-reward
+# sum is compared bit for bit with the oracle) and the learner's save / load
+$(OUT)/obj/learner_core.o: $(SRC)/learner_core.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+
+$(OUT)/obj/learner_snapshot.o: $(SRC)/learner_snapshot.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 
 # policy evaluation: fp32 sums compared bit for bit with the oracle restatement, like the learner's books

@@ -23,8 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "learner_core.h"
 #include "objects.h"
-#include "per.h"
 #include "stats.h"
 
 namespace qlx {
@@ -33,6 +33,7 @@ namespace bg {
 constexpr int kObs = 36;        // [3][3][4] u8 one-hot
 constexpr int kA = 5;
 constexpr int kMaxSteps = 16;   // MAX_STEPS (:12)
+constexpr float kGoalMean = 9.5f;   // episode_reward_goal_mean (:88)
 enum : uint8_t { EMPTY = 0, GOAL = 1, BALL = 2, OBST = 3 };
 constexpr int kVars = 8;
 constexpr int kVarSize[kVars] = {2 * 2 * 4 * 32, 32, 32 * 32, 32, 288 * 512, 512, 512 * 5, 5};
@@ -508,34 +509,20 @@ static const uint8_t* stage_obs(qlx_bg_model* m, const uint8_t* obs_host, int n)
 
 // ---------------- learner ----------------
 
-struct qlx_bg_learner {
-  qlx_params p{};
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct qlx_bg_learner : qlx::LearnerCore {
   qlx_bg_env* env = nullptr;
   qlx_bg_model* online = nullptr;
   qlx_bg_model* target = nullptr;
-  uint32_t N = 0, B = 0, max_updates = 0;
   uint64_t cap = 0, total = 0;
+  uint64_t len() const { return std::min(total, cap); }
   // replay columns (replay_buffer.rs: one FIFO position for all)
   DeviceBuffer<qlx_ballgame_state> d_rs, d_rsn;
   DeviceBuffer<uint8_t> d_ra, d_rd;
   DeviceBuffer<float> d_rr;
-  // per vector step
-  DeviceBuffer<uint8_t> d_obs, d_actions, d_dones, d_reset;
-  DeviceBuffer<float> d_rewards, d_q;
-  DeviceBuffer<double> d_eps;
-  uint64_t eps_len = 0;
-  DeviceBuffer<float> d_ep_reward, d_hist;
-  DeviceBuffer<Book> d_book;
-  DeviceBuffer<uint64_t> d_idx;
-  DeviceBuffer<uint8_t> d_xs, d_xn, d_bact, d_bdone;
-  DeviceBuffer<float> d_brew, d_targets, d_losses;
-  DeviceBuffer<float> d_qsel;   // double DQN: online Q(s') of the step's batches [U*B][5]
-  bool ddqn = false, per = false;
-  qlx::PerState prio;
-  uint64_t step_count = 0, vec_steps = 0, update_count = 0;
-  uint32_t last_updates = 0;
+  DeviceBuffer<uint8_t> d_obs;      // [N][36] one-hot observations the step acts on
+  DeviceBuffer<float> d_q;          // [N][5] Q(s) of the acting forward
+  DeviceBuffer<uint8_t> d_xs, d_xn; // [U*B][36] one-hot s / s' of the step's batches
+  DeviceBuffer<float> d_qsel;       // double DQN: online Q(s') of the step's batches [U*B][5]
 };
 
 namespace qlx {
@@ -580,40 +567,31 @@ static void learner_vector_step(qlx_bg_learner* L) {
   qlx_bg_env* env = L->env;
   if (step_before + N >= L->p.epsilon_pure_random_steps) {   // acting forward with the weights at the step start
     hipLaunchKernelGGL(k_env_obs, dim3((N + 255) / 256), dim3(256), 0, s, env->d_state, N, L->d_obs);
+    QLX_HIP(hipGetLastError());
     forward(L->online, L->d_obs, (int)N, s);
     HeadArgs h = head_args(L->online, (int)N);
     h.q = L->d_q;
     head<0>(h, s);
   }
-  launch_select_actions(s, N, kA, step_before, L->p.epsilon_pure_random_steps, L->d_eps, L->eps_len, L->p.epsilon_min,
-                        L->p.learner_seed, env->id_offset, (uint32_t)L->vec_steps, L->d_q, L->d_actions);
-  L->step_count += N;
+  L->select_actions(L->d_q, kA, env->id_offset);
   hipLaunchKernelGGL(k_step_push, dim3((N + 255) / 256), dim3(256), 0, s, env->d_state, env->d_ep_steps, N, L->d_actions,
                      L->d_rewards, L->d_dones, L->d_rs, L->d_rsn, L->d_ra, L->d_rr, L->d_rd, L->total, L->cap);
-  if (L->per) per_launch_push(s, L->prio.leaves(), L->cap, L->total, N, L->prio.d_max);
+  QLX_HIP(hipGetLastError());
+  L->per_push(L->cap, L->total);
   L->total += N;
-  launch_episode_book(s, N, L->d_rewards, L->d_dones, env->d_ep_steps, L->p.max_steps_per_episode, L->d_ep_reward, L->d_hist,
-                      (uint32_t)L->p.episode_reward_history_buffer_len, L->d_book, L->d_reset);
+  L->episode_book(env->d_ep_steps);
   hipLaunchKernelGGL(k_env_init, dim3((N + 255) / 256), dim3(256), 0, s, env->d_state, env->d_ep_steps, N, env->seed,
                      env->id_offset, L->d_reset, 1);
-  const uint64_t ua = L->p.update_after_actions;
-  const uint64_t triggers = L->step_count / ua - step_before / ua;
-  const uint64_t len = std::min(L->total, L->cap);
+  QLX_HIP(hipGetLastError());
+  const uint64_t len = L->len();
   L->last_updates = 0;
-  if (len > B && triggers > 0) {
-    const uint32_t U = (uint32_t)triggers;
-    QLX_CHECK(U <= L->max_updates, QLX_E_STATE, "too many updates per vector step");
+  if (const uint32_t U = L->updates_due(step_before, len)) {
     const uint64_t start = (L->total - len) % L->cap;
-    if (L->per) {
-      per_launch_build(s, L->prio.d_tree, L->prio.L);
-      per_launch_sample(s, L->prio.d_tree, L->prio.L, L->p.learner_seed, (uint32_t)L->update_count, U, L->p.rank, len,
-                        L->p.per_beta, B, L->cap, start, L->d_idx, L->prio.d_w);
-    } else {
-      launch_sample_distinct(s, L->p.learner_seed, (uint32_t)L->update_count, U, L->p.rank, len, B, L->d_idx);
-    }
+    L->sample(U, len, L->cap, start);
     const uint32_t n = U * B;
     hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), dim3(256), 0, s, L->d_rs, L->d_rsn, L->d_ra, L->d_rr, L->d_rd, L->total, len,
                        L->cap, L->d_idx, n, L->d_xs, L->d_xn, L->d_bact, L->d_brew, L->d_bdone);
+    QLX_HIP(hipGetLastError());
     // targets of all U updates from the fixed target weights (a sync happens only between vector steps); double
     // DQN picks a* with the online weights as they stand before this step's updates
     if (L->ddqn) {
@@ -638,13 +616,10 @@ static void learner_vector_step(qlx_bg_learner* L) {
       apply_adam(L->online, s);
       L->update_count += 1;
     }
-    if (L->per)
-      per_launch_update(s, L->d_idx, L->prio.d_td, n, L->cap, start, L->p.per_alpha, L->p.per_eps, L->prio.d_owner,
-                        L->prio.leaves(), L->prio.d_max);
+    L->write_priorities(U, L->cap, start);
     L->last_updates = U;
   }
-  const uint64_t ts = L->p.target_sync_steps;
-  if (ts > 0 && L->step_count / ts != step_before / ts)
+  if (L->target_sync_due(step_before))
     QLX_HIP(hipMemcpyAsync(L->target->d_params, L->online->d_params, kParams * 4, hipMemcpyDeviceToDevice, s));
   L->vec_steps += 1;
   QLX_HIP(hipGetLastError());
@@ -911,24 +886,13 @@ int32_t qlx_bg_model_train(qlx_bg_model* m, const uint8_t* obs, const uint8_t* a
 int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learner** out) {
   return guard([&] {
     QLX_CHECK(p && out, QLX_E_INVALID, "null argument");
-    QLX_CHECK(p->n_envs > 0 && p->batch_size > 0 && p->batch_size <= 4096, QLX_E_INVALID, "bad n_envs / batch_size");
-    QLX_CHECK(p->update_after_actions > 0 && p->history_buffer_len >= p->batch_size, QLX_E_INVALID, "bad parameters");
-    QLX_CHECK(p->episode_reward_history_buffer_len > 0, QLX_E_INVALID, "episode_reward_history_buffer_len must be > 0");
-    QLX_CHECK((p->flags & ~(QLX_LEARNER_DOUBLE_DQN | QLX_LEARNER_PER)) == 0, QLX_E_INVALID, "unknown learner flags");
+    LearnerCore::validate(*p);
     QLX_CHECK(p->n_step <= 1, QLX_E_INVALID, "n_step: Breakout learner only");
-    QLX_CHECK(!(p->flags & QLX_LEARNER_PER) || (p->per_alpha >= 0.0f && p->per_beta >= 0.0f && p->per_eps > 0.0f),
-              QLX_E_INVALID, "prioritized replay needs alpha >= 0, beta >= 0, eps > 0");
     current_device_checked(device);
     auto* L = new qlx_bg_learner;
     try {   // a failure part-way releases what was built
-      L->ddqn = (p->flags & QLX_LEARNER_DOUBLE_DQN) != 0;
-      L->per = (p->flags & QLX_LEARNER_PER) != 0;
-      L->p = *p;
-      L->device = device;
-      L->N = p->n_envs;
-      L->B = p->batch_size;
+      L->init(*p, device);
       L->cap = p->history_buffer_len;
-      QLX_HIP(hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
       int32_t st = qlx_bg_env_create(L->N, p->env_seed, device, &L->env);
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
       st = qlx_bg_model_create(p->init_seed, device, &L->online);
@@ -942,38 +906,19 @@ int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learne
         L->env->id_offset = p->rank * L->N;
         hipLaunchKernelGGL(k_env_init, dim3((L->N + 255) / 256), dim3(256), 0, L->stream, L->env->d_state, L->env->d_ep_steps, L->N,
                            L->env->seed, L->env->id_offset, (const uint8_t*)nullptr, 0);
+        QLX_HIP(hipGetLastError());
       }
-      const std::vector<double> eps = epsilon_table(*p);
-      L->eps_len = eps.size();
-      L->d_eps.alloc(eps.size());
-      QLX_HIP(hipMemcpy(L->d_eps, eps.data(), eps.size() * 8, hipMemcpyHostToDevice));
       const uint32_t N = L->N, B = L->B;
-      L->max_updates = (uint32_t)(N / p->update_after_actions + 2);
-      const size_t UB = (size_t)L->max_updates * B;
+      const size_t UB = L->max_samples();
       L->d_rs.alloc(L->cap);
       L->d_rsn.alloc(L->cap);
       L->d_ra.alloc(L->cap);
       L->d_rd.alloc(L->cap);
       L->d_rr.alloc(L->cap);
       L->d_obs.alloc((size_t)N * kObs);
-      L->d_actions.alloc(N);
-      L->d_dones.alloc(N);
-      L->d_reset.alloc(N);
-      L->d_rewards.alloc(N);
       L->d_q.alloc((size_t)N * kA);
-      L->d_ep_reward.alloc(N);
-      L->d_hist.alloc(p->episode_reward_history_buffer_len);
-      L->d_book.alloc(1);
-      L->d_idx.alloc(UB);
       L->d_xs.alloc(UB * kObs);
       L->d_xn.alloc(UB * kObs);
-      L->d_bact.alloc(UB);
-      L->d_bdone.alloc(UB);
-      L->d_brew.alloc(UB);
-      L->d_targets.alloc(UB);
-      L->d_losses.alloc(L->max_updates);
-      QLX_HIP(hipMemsetAsync(L->d_ep_reward, 0, (size_t)N * 4, L->stream));
-      QLX_HIP(hipMemsetAsync(L->d_book, 0, sizeof(Book), L->stream));
       QLX_HIP(hipMemsetAsync(L->d_q, 0, (size_t)N * kA * 4, L->stream));
       model_workspace(L->online, (int)std::max(N, B));
       model_workspace(L->target, (int)UB);
@@ -981,7 +926,6 @@ int32_t qlx_bg_learner_create(const qlx_params* p, int32_t device, qlx_bg_learne
         model_workspace(L->online, (int)UB);
         L->d_qsel.alloc(UB * kA);
       }
-      if (L->per) L->prio.init(L->cap, UB);
       QLX_HIP(hipStreamSynchronize(L->stream));
     } catch (...) {
       qlx_bg_learner_destroy(L);
@@ -1022,55 +966,21 @@ int32_t qlx_bg_learner_sync(qlx_bg_learner* L) {
 int32_t qlx_bg_learner_stats_get(qlx_bg_learner* L, qlx_learner_stats* out) {
   return guard([&] {
     QLX_CHECK(L && out, QLX_E_INVALID, "null argument");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    Book b;
-    QLX_HIP(hipMemcpy(&b, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-    std::vector<float> ring(L->p.episode_reward_history_buffer_len);
-    QLX_HIP(hipMemcpy(ring.data(), L->d_hist, ring.size() * 4, hipMemcpyDeviceToHost));
-    out->step_count = L->step_count;
-    out->vec_steps = L->vec_steps;
-    out->update_count = L->update_count;
-    out->episode_count = b.episode_count;
-    out->replay_len = std::min(L->total, L->cap);
-    double e = L->p.epsilon_min;
-    if (L->step_count < L->eps_len) QLX_HIP(hipMemcpy(&e, L->d_eps + L->step_count, 8, hipMemcpyDeviceToHost));
-    out->epsilon = e;
-    float running = 0.0f;
-    uint64_t solved = 0;
-    learner_book_stats(b, ring.data(), (uint32_t)ring.size(), 9.5f, L->p.lowest_episode_reward_goal_threshold_pct, &running, &solved);
-    out->running_reward = running;
-    out->solved = solved;
-    float loss = 0.0f;
-    if (L->last_updates) QLX_HIP(hipMemcpy(&loss, L->d_losses + L->last_updates - 1, 4, hipMemcpyDeviceToHost));
-    out->last_loss = loss;
+    L->stats(kGoalMean, L->len(), out);
   });
-}
-
-static std::vector<float> bg_episode_rewards(qlx_bg_learner* L) {
-  QLX_HIP(hipStreamSynchronize(L->stream));
-  Book b;
-  QLX_HIP(hipMemcpy(&b, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-  std::vector<float> ring(L->p.episode_reward_history_buffer_len), out(b.hist_len);
-  QLX_HIP(hipMemcpy(ring.data(), L->d_hist, ring.size() * 4, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < b.hist_len; ++i) out[i] = ring[(b.hist_head + i) % ring.size()];
-  return out;
 }
 
 int32_t qlx_bg_learner_action_counts(qlx_bg_learner* L, uint64_t* counts) {
   return guard([&] {
     QLX_CHECK(L && counts, QLX_E_INVALID, "null argument");
-    std::vector<uint64_t> c;
-    action_counts(L->stream, L->d_ra, std::min(L->total, L->cap), bg::kA, c);
-    std::copy(c.begin(), c.end(), counts);
+    L->action_counts(L->d_ra, L->len(), bg::kA, counts);
   });
 }
 
 int32_t qlx_bg_learner_episode_rewards(qlx_bg_learner* L, float* out, uint64_t cap, uint64_t* n) {
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
-    const std::vector<float> r = bg_episode_rewards(L);
-    if (n) *n = r.size();
-    if (out) std::copy(r.begin(), r.begin() + std::min<uint64_t>(cap, r.size()), out);
+    L->episode_rewards(out, cap, n);
   });
 }
 
@@ -1079,24 +989,14 @@ int32_t qlx_bg_learner_update_log(qlx_bg_learner* L, char* buf, size_t cap, size
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
     // BallGameAction Display (ballgame_test_environment.rs:222-234) by numeric value West 0 .. Nothing 4
     static const char* const kNames[bg::kA] = {"\xE2\x86\x90", "\xE2\x86\x91", "\xE2\x86\x92", "\xE2\x86\x93", "o"};
-    qlx_learner_stats st;
-    int32_t rc = qlx_bg_learner_stats_get(L, &st);
-    QLX_CHECK(rc == QLX_OK, rc, qlx_last_error());
-    LogInputs in{st.episode_count, st.step_count, L->p.gamma, st.epsilon, 9.5f, L->p.lowest_episode_reward_goal_threshold_pct,
-                 bg_episode_rewards(L), {}, kNames};
-    action_counts(L->stream, L->d_ra, std::min(L->total, L->cap), bg::kA, in.counts);
-    copy_text(learning_log(in), buf, cap, len);
+    copy_text(L->update_log(kGoalMean, kNames, bg::kA, L->d_ra, L->len()), buf, cap, len);
   });
 }
 
 int32_t qlx_bg_learner_priorities(qlx_bg_learner* L, float* is_weights, float* leaves, float* per_max) {
   return guard([&] {
     QLX_CHECK(L && L->per, QLX_E_STATE, "learner was created without QLX_LEARNER_PER");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    const uint32_t U = L->last_updates;
-    if (U && is_weights) QLX_HIP(hipMemcpy(is_weights, L->prio.d_w, (size_t)U * L->B * 4, hipMemcpyDeviceToHost));
-    if (leaves) QLX_HIP(hipMemcpy(leaves, L->prio.leaves(), L->prio.cap * 4, hipMemcpyDeviceToHost));
-    if (per_max) QLX_HIP(hipMemcpy(per_max, L->prio.d_max, 4, hipMemcpyDeviceToHost));
+    L->priorities(is_weights, leaves, per_max);
   });
 }
 
@@ -1104,15 +1004,7 @@ int32_t qlx_bg_learner_last(qlx_bg_learner* L, uint8_t* actions, float* rewards,
                             uint64_t* indices, float* targets, uint32_t* n_updates) {
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    const uint32_t U = L->last_updates;
-    if (actions) QLX_HIP(hipMemcpy(actions, L->d_actions, L->N, hipMemcpyDeviceToHost));
-    if (rewards) QLX_HIP(hipMemcpy(rewards, L->d_rewards, (size_t)L->N * 4, hipMemcpyDeviceToHost));
-    if (dones) QLX_HIP(hipMemcpy(dones, L->d_dones, L->N, hipMemcpyDeviceToHost));
-    if (U && losses) QLX_HIP(hipMemcpy(losses, L->d_losses, (size_t)U * 4, hipMemcpyDeviceToHost));
-    if (U && indices) QLX_HIP(hipMemcpy(indices, L->d_idx, (size_t)U * L->B * 8, hipMemcpyDeviceToHost));
-    if (U && targets) QLX_HIP(hipMemcpy(targets, L->d_targets, (size_t)U * L->B * 4, hipMemcpyDeviceToHost));
-    if (n_updates) *n_updates = U;
+    L->last(actions, rewards, dones, losses, indices, targets, n_updates);
   });
 }
 

@@ -6,12 +6,13 @@
 // train every update_after_actions steps once len > B, Bellman target r + gamma * max Q_target(s') or r
 // if done, episode bookkeeping + running_reward), :134-139 (solved), :276-296 (distinct ids).
 // Vector-step generalisation (N = 1 is the reference loop): DESIGN.md "Learner semantics".
+// What does not depend on the environment (acting, episode books, sampling, read-outs) is learner_core.hip; this file is
+// the Breakout vector step, the data-parallel update and the C API.  Snapshots: learner_snapshot.hip.
 #include <hip/hip_runtime.h>
 
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cmath>
 #include <limits>
@@ -19,148 +20,21 @@
 #include <string>
 #include <vector>
 
-#include "frame_codec.h"
-#include "objects.h"
-#include "per.h"
-#include "profiler.h"
+#include "learner.h"
 #include "qnet.h"
 #include "replay_dev.h"
 #include "stats.h"
 
+// an RCCL call that must succeed; the message is "<function name>: <RCCL's error text>"
+#define QLX_NCCL(call)                                                                                                  \
+  do {                                                                                                                  \
+    const ncclResult_t r__ = (call);                                                                                    \
+    QLX_CHECK(r__ == ncclSuccess, QLX_E_COMM, std::string(#call, std::strchr(#call, '(')) + ": " + ncclGetErrorString(r__)); \
+  } while (0)
+
 namespace qlx {
 
 ReplayView replay_view(const qlx_replay* rb);
-
-// ---- acting: epsilon-greedy (self_driving_tf_q_learner.rs:153-167) --------------------------
-// step_count of env e in this vector step = step_before + e + 1; epsilon used = eps_table[step_count - 1]
-// (value after step_count - 1 decrements). Draws: f64 from words 0-1, the random action from word 2 on.
-__global__ void k_select_actions(uint32_t n, uint32_t n_actions, uint64_t step_before, uint64_t pure_random,
-                                 const double* eps_table, uint64_t eps_len, double eps_min, uint64_t seed, uint32_t id_offset,
-                                 uint32_t vec_step, const float* q, uint8_t* actions) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const uint64_t sc = step_before + e + 1;
-  bool random = sc < pure_random;
-  if (!random) {
-    RngStream su(seed, id_offset + e, vec_step, P_ACT, 0);
-    const double eps = (sc - 1) < eps_len ? eps_table[sc - 1] : eps_min;
-    random = eps > uniform_f64_01(su);
-  }
-  uint8_t a;
-  if (random) {
-    RngStream sa(seed, id_offset + e, vec_step, P_ACT, 2);
-    a = (uint8_t)uniform_u8(sa, n_actions);
-  } else {   // tf.argmax over Q(s): first maximal index
-    int best = 0;
-    float bv = q[e * n_actions];
-    for (uint32_t j = 1; j < n_actions; ++j)
-      if (q[e * n_actions + j] > bv) { best = (int)j; bv = q[e * n_actions + j]; }
-    a = (uint8_t)best;
-  }
-  actions[e] = a;
-}
-
-void launch_select_actions(hipStream_t s, uint32_t n, uint32_t n_actions, uint64_t step_before, uint64_t pure_random,
-                           const double* eps_table, uint64_t eps_len, double eps_min, uint64_t seed, uint32_t id_offset,
-                           uint32_t vec_step, const float* q, uint8_t* actions) {
-  hipLaunchKernelGGL(k_select_actions, dim3((n + 255) / 256), dim3(256), 0, s, n, n_actions, step_before, pure_random, eps_table,
-                     eps_len, eps_min, seed, id_offset, vec_step, q, actions);
-  QLX_HIP(hipGetLastError());
-}
-
-// ---- episode bookkeeping (learn_episode :172-174, :214-224) -----------------------------------
-
-// Envs in order: ep_reward += r; an env whose episode ended (done, or max_steps_per_episode steps) pushes its
-// reward into the FIFO of episode rewards, counts the episode and is marked for reset.  The per-env part runs
-// one thread per env (1024 per round); wave 0 then walks the round's endings in env order (ballot per 64 envs)
-// and keeps the Book.  running_reward is refreshed (sequential f32 sum, oldest first) by every ending with
-// episode_count >= hist cap; only the last such refresh of the step survives and it sums the final FIFO, so it
-// runs once: the FIFO is loaded 64 entries per lane-parallel load and summed in order with uniform lane reads.
-__global__ __launch_bounds__(1024) void k_episode_book(uint32_t n, const float* rewards, const uint8_t* dones,
-                                                       const uint32_t* ep_steps, uint64_t max_steps, float* ep_reward,
-                                                       float* hist, uint32_t hist_cap, Book* book, uint8_t* reset_mask) {
-  __shared__ float s_er[1024];
-  __shared__ uint8_t s_end[1024];
-  const int tid = threadIdx.x, lane = tid & 63;
-  Book b = *book;
-  bool refresh = false;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t e = base + tid;
-    bool end = false;
-    float er = 0.0f;
-    if (e < n) {
-      er = ep_reward[e] + rewards[e];
-      end = dones[e] || ep_steps[e] >= max_steps;
-      ep_reward[e] = end ? 0.0f : er;
-      reset_mask[e] = end ? 1 : 0;
-    }
-    s_er[tid] = er;
-    s_end[tid] = end ? 1 : 0;
-    __syncthreads();
-    if (tid < 64) {
-      for (int c = 0; c < 1024 && base + c < n; c += 64) {
-        const float v0 = s_er[c + lane];
-        unsigned long long bal = __ballot(s_end[c + lane] != 0);
-        while (bal) {   // uniform loop: every lane tracks the same Book
-          const int l = __builtin_ctzll(bal);
-          bal &= bal - 1;
-          const float v = __shfl(v0, l);
-          if (b.hist_len < hist_cap) {
-            if (lane == 0) hist[(b.hist_head + b.hist_len) % hist_cap] = v;
-            b.hist_len += 1;
-          } else {
-            if (lane == 0) hist[b.hist_head] = v;
-            b.hist_head = (b.hist_head + 1) % hist_cap;
-          }
-          refresh = refresh || b.episode_count >= hist_cap;
-          b.episode_count += 1;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (tid < 64) {
-    if (refresh) {
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // lane 0's FIFO stores, before the other lanes read
-      float s = 0.0f;
-      for (uint32_t c = 0; c < b.hist_len; c += 64) {
-        const float v = c + lane < b.hist_len ? hist[(b.hist_head + c + lane) % hist_cap] : 0.0f;
-        const uint32_t m = b.hist_len - c < 64 ? b.hist_len - c : 64;
-        for (uint32_t j = 0; j < m; ++j) s += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), (int)j));
-      }
-      b.running_reward = s / (float)b.hist_len;
-    }
-    if (lane == 0) *book = b;
-  }
-}
-
-void launch_episode_book(hipStream_t s, uint32_t n, const float* rewards, const uint8_t* dones, const uint32_t* ep_steps,
-                         uint64_t max_steps, float* ep_reward, float* hist, uint32_t hist_cap, Book* book, uint8_t* reset_mask) {
-  hipLaunchKernelGGL(k_episode_book, dim3(1), dim3(1024), 0, s, n, rewards, dones, ep_steps, max_steps, ep_reward, hist, hist_cap,
-                     book, reset_mask);
-  QLX_HIP(hipGetLastError());
-}
-
-std::vector<double> epsilon_table(const qlx_params& p) {
-  std::vector<double> eps;
-  double e = p.epsilon_max;
-  const double delta = (p.epsilon_max - p.epsilon_min) / p.epsilon_greedy_steps;
-  const size_t cap = 1u << 26;
-  while (eps.size() < cap) {
-    eps.push_back(e);
-    if (e <= p.epsilon_min) break;
-    e = std::max(e - delta, p.epsilon_min);
-  }
-  return eps;
-}
-
-void learner_book_stats(const Book& b, const float* ring, uint32_t ring_cap, float goal, float pct, float* running, uint64_t* solved) {
-  *running = b.running_reward;
-  if (b.hist_len == 0) { *solved = 0; return; }
-  float mn = ring[b.hist_head % ring_cap];
-  for (uint32_t i = 0; i < b.hist_len; ++i) mn = std::min(mn, ring[(b.hist_head + i) % ring_cap]);
-  *solved = (b.running_reward >= goal && mn >= goal * pct) ? 1 : 0;
-}
 
 // ---- replay sample gather: frame pointer tables + metadata of one update ------------------------
 // (ycache != null: the Bellman target of each sampled slot is read from the per-slot memo instead, see ycache_fill)
@@ -254,119 +128,30 @@ __global__ void k_obs_table(const uint8_t* obs, uint32_t n, const uint8_t** tabl
   if (i < n * 4) table[i] = obs + (size_t)i * kFramePix;
 }
 
-}  // namespace qlx
-
-struct qlx_learner {
-  qlx_params p{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  qlx_env* env = nullptr;
-  qlx_replay* rb = nullptr;
-  qlx_model* online = nullptr;
-  qlx_model* target = nullptr;
-  uint32_t N = 0, B = 0;
-  // device buffers
-  qlx::DeviceBuffer<uint8_t> d_actions, d_dones, d_reset;
-  qlx::DeviceBuffer<float> d_rewards;
-  qlx::DeviceBuffer<const uint8_t*> d_obs_table;
-  qlx::DeviceBuffer<double> d_eps;
-  uint64_t eps_len = 0;
-  qlx::DeviceBuffer<float> d_ep_reward, d_hist;
-  qlx::DeviceBuffer<qlx::Book> d_book;
-  qlx::DeviceBuffer<uint64_t> d_idx;       // [max_updates][B]
-  qlx::DeviceBuffer<const uint8_t*> d_tab_s, d_tab_sn;
-  qlx::DeviceBuffer<uint8_t> d_bact, d_bdone;
-  qlx::DeviceBuffer<float> d_brew;
-  qlx::DeviceBuffer<float> d_losses;       // [max_updates]
-  qlx::DeviceBuffer<float> d_targets;      // [max_updates][B]
-  uint32_t max_updates = 0;
-  bool ddqn = false, per = false;  // qlx_params.flags
-  qlx::PerState prio;              // prioritized replay (per.hip)
-  // host counters
-  uint64_t step_count = 0, vec_steps = 0, update_count = 0;
-  uint32_t last_updates = 0;
-  // data parallel
-  ncclComm_t comm = nullptr;
-  hipStream_t comm_stream = nullptr;   // the communicator's collectives (bucketed gradient all-reduce)
-  bool dp_overlap = true;              // QLX_DP_OVERLAP=0: one whole-gradient all-reduce after the backward
-  bool dp_fold = true;                 // fp32 dense norm partials in the conv backward's reduction launch (QLX_DP_FOLD=0:
-                                       // a launch of their own on the communicator stream)
-  hipEvent_t ev_dense = nullptr, ev_reduced = nullptr;
-  int world = 1, rank = 0;
-  // global solved() over ranks: per vector step, {sum running_reward, sum has_history, sum episodes} (f64) and {min
-  // episode reward} all-reduced on the learner stream (d_gsum[3], d_gmin[1])
-  qlx::DeviceBuffer<double> d_gsum;
-  qlx::DeviceBuffer<float> d_gmin;
-  // pinned host copies read after every vector step (the solved() check): Book + the global sums
-  qlx::PinnedBuffer<qlx::Book> h_book;
-  qlx::PinnedBuffer<double> h_gsum;
-  // frame_sparsity's counters: a device buffer and its pinned host copy (8 x u64: the train and the acting halves)
-  qlx::DeviceBuffer<unsigned long long> d_sparsity;
-  qlx::PinnedBuffer<unsigned long long> h_sparsity;
-  // Bellman-target memo per replay slot (ycache_fill): on when the target net is frozen (target_sync_steps == 0,
-  // the reference) and y does not depend on the online net (no double DQN); QLX_TARGET_CACHE=0 turns it off
-  bool ycache = false;
-  qlx::DeviceBuffer<float> d_ycache;           // [capacity] y of the transition in each ring slot
-  qlx::DeviceBuffer<const uint8_t*> d_ytab;    // [ychunk * 4]
-  qlx::DeviceBuffer<float> d_yrew, d_ytmp;     // [ychunk]
-  qlx::DeviceBuffer<uint8_t> d_ydone;          // [ychunk]
-  uint32_t ychunk = 0;
-  uint64_t ycache_version = 0;         // target->version the memo was computed with
-  // n-step returns (qlx_params.n_step > 1).  The memo then holds the bootstrap value v = max_a Q_target(s')
-  // per slot instead of y, and every target pass runs the head with gamma = 1 over zero rewards / dones (d_zero: zero
-  // bytes, read as both) so that it leaves v; R, g and terminal of the sampled windows are kept only without the memo.
-  uint32_t n_step = 1;
-  qlx::DeviceBuffer<float> d_zero;             // zeros (zero_reserve)
-  qlx::DeviceBuffer<float> d_nret;             // [max_updates][B] R
-  qlx::DeviceBuffer<float> d_ndisc;            // [max_updates][B] g = gamma^m
-  qlx::DeviceBuffer<uint8_t> d_nterm;          // [max_updates][B] done of the window's last transition
-  qlx::Profiler prof;
-  // statistics events (write_checkpoint + learning_update_log, self_driving_tf_q_learner.rs:204-212,226-230)
-  uint64_t stats_events = 0;
-  uint64_t seen_episodes = 0;
-  std::string last_log;
-  void (*log_cb)(const char*, void*) = nullptr;
-  void* log_user = nullptr;
-};
-
-namespace qlx {
-
-// Targets of all U updates of one vector step in one pass: the target weights are fixed while the step's
-// updates run (a target sync happens only between vector steps) and all U batches were sampled up front
-// from the same replay state, so y = r + gamma * max_a Q_target(s') (or r if done) for the U*B sampled
-// transitions is one batched forward - the same values as U separate passes.
-// y for the updates [u0, u0 + nu) from the target net on stream s (after the gather)
-static void learner_targets_range(qlx_learner* L, uint32_t u0, uint32_t nu, const float* q_select, hipStream_t s) {
-  const uint32_t n = nu * L->B;
-  const size_t o = (size_t)u0 * L->B;
-  qlx_model* tg = L->target;
-  model_workspace(tg, (int)n);
-  model_forward_trunk(tg, L->d_tab_sn + o * 4, (int)n, s, false);
-  Fc2Args ta = fc2_args(tg, (int)n);
-  ta.q_select = q_select ? q_select + o * kActions : nullptr;
-  ta.rewards = L->d_brew + o;
-  ta.dones = L->d_bdone + o;
-  ta.gamma = L->p.gamma;
-  ta.y_out = L->d_targets + o;
-  if (L->n_step > 1) {   // the head leaves the bootstrap value: y = 0 + v * 1 (d_tab_sn holds s' of each window's last transition)
-    ta.rewards = L->d_zero;
-    ta.dones = reinterpret_cast<const uint8_t*>(L->d_zero.get());
-    ta.gamma = 1.0f;
-  }
-  model_head(tg, 2, ta, (int)n, s);
-  if (L->n_step > 1) {
-    hipLaunchKernelGGL(k_nstep_combine, dim3((n + 255) / 256), dim3(256), 0, s, n, L->d_nret + o, L->d_ndisc + o, L->d_nterm + o,
-                       L->d_targets + o);
-    QLX_HIP(hipGetLastError());
-  }
-}
-
 // at least n zero floats in d_zero (n-step: the zero rewards / dones of the bootstrap passes)
 static void zero_reserve(qlx_learner* L, uint32_t n) {
   if (n <= L->d_zero.size()) return;
   QLX_HIP(hipStreamSynchronize(L->stream));
   L->d_zero.reserve(n);
   QLX_HIP(hipMemsetAsync(L->d_zero, 0, L->d_zero.bytes(), L->stream));
+}
+
+// Head arguments of a target pass over n transitions: y = r + gamma * max_a Q_target(s') (or r if done), a* from q_select
+// if given.  n-step returns: the head leaves the bootstrap value instead, y = 0 + v * 1 (s' is then each window's last one).
+static Fc2Args target_head_args(qlx_learner* L, uint32_t n, const float* q_select, const float* rewards, const uint8_t* dones,
+                                float* y_out) {
+  Fc2Args ta = fc2_args(L->target, (int)n);
+  ta.q_select = q_select;
+  ta.rewards = rewards;
+  ta.dones = dones;
+  ta.gamma = L->p.gamma;
+  ta.y_out = y_out;
+  if (L->n_step > 1) {
+    ta.rewards = L->d_zero;
+    ta.dones = reinterpret_cast<const uint8_t*>(L->d_zero.get());
+    ta.gamma = 1.0f;
+  }
+  return ta;
 }
 
 // Target memo.  With the target net frozen, y = r + gamma * max_a Q_target(s') (or r if done) of a transition is a
@@ -402,24 +187,17 @@ static void ycache_fill(qlx_learner* L, uint64_t i0, uint64_t n, uint32_t chunk)
     hipLaunchKernelGGL(k_slot_tables, dim3((m + 255) / 256), dim3(256), 0, s, rv, i0 + c0, m, L->d_ytab, L->d_yrew, L->d_ydone);
     QLX_HIP(hipGetLastError());
     model_forward_trunk(tg, L->d_ytab, (int)m, s, false);
-    Fc2Args ta = fc2_args(tg, (int)m);
-    ta.q_select = nullptr;
-    ta.rewards = L->d_yrew;
-    ta.dones = L->d_ydone;
-    ta.gamma = L->p.gamma;
-    ta.y_out = L->d_ytmp;
-    if (L->n_step > 1) {
-      ta.rewards = L->d_zero;
-      ta.dones = reinterpret_cast<const uint8_t*>(L->d_zero.get());
-      ta.gamma = 1.0f;
-    }
-    model_head(tg, 2, ta, (int)m, s);
+    model_head(tg, 2, target_head_args(L, m, nullptr, L->d_yrew, L->d_ydone, L->d_ytmp), (int)m, s);
     hipLaunchKernelGGL(k_slot_put, dim3((m + 255) / 256), dim3(256), 0, s, rv, i0 + c0, m, L->d_ytmp, L->d_ycache);
     QLX_HIP(hipGetLastError());
   }
   debug_sync(s, "ycache_fill");
 }
 
+// Targets of all U updates of one vector step in one pass: the target weights are fixed while the step's
+// updates run (a target sync happens only between vector steps) and all U batches were sampled up front
+// from the same replay state, so y = r + gamma * max_a Q_target(s') (or r if done) for the U*B sampled
+// transitions is one batched forward - the same values as U separate passes.
 static void learner_targets(qlx_learner* L, uint32_t U) {
   hipStream_t s = L->stream;
   const uint32_t n = U * L->B;
@@ -433,6 +211,7 @@ static void learner_targets(qlx_learner* L, uint32_t U) {
     } else {
       hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), dim3(256), 0, s, rv, L->d_idx, n, L->d_tab_s, L->d_tab_sn, L->d_bact,
                          L->d_brew, L->d_bdone, L->ycache ? L->d_ycache : nullptr, L->d_targets);
+      QLX_HIP(hipGetLastError());
     }
   }
   debug_sync(s, "gather");
@@ -447,7 +226,14 @@ static void learner_targets(qlx_learner* L, uint32_t U) {
   }
   // (measured and not kept, round 3: the pass after its first chunk on a second stream beside the update chain - the chain
   // is latency-bound and every CU the pass holds delays it by more than the pass costs on the learner stream)
-  learner_targets_range(L, 0, U, q_select, s);
+  qlx_model* tg = L->target;
+  model_workspace(tg, (int)n);
+  model_forward_trunk(tg, L->d_tab_sn, (int)n, s, false);
+  model_head(tg, 2, target_head_args(L, n, q_select, L->d_brew, L->d_bdone, L->d_targets), (int)n, s);
+  if (L->n_step > 1) {
+    hipLaunchKernelGGL(k_nstep_combine, dim3((n + 255) / 256), dim3(256), 0, s, n, L->d_nret, L->d_ndisc, L->d_nterm, L->d_targets);
+    QLX_HIP(hipGetLastError());
+  }
 }
 
 static void learner_update(qlx_learner* L, uint32_t u_local) {
@@ -466,8 +252,7 @@ static void learner_update(qlx_learner* L, uint32_t u_local) {
   } else if (!L->dp_overlap) {   // one all-reduce of the whole gradient on the learner stream
     model_backward(on, tab_s, (int)B, bact, L->d_targets + (size_t)u_local * B, L->d_losses + u_local, s, isw, td);
     ProfScope ps(&L->prof, "allreduce", s);
-    const ncclResult_t r = ncclAllReduce(on->d_grads, on->d_grads, (size_t)kNumParams, ncclFloat, ncclSum, L->comm, s);
-    QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+    QLX_NCCL(ncclAllReduce(on->d_grads, on->d_grads, (size_t)kNumParams, ncclFloat, ncclSum, L->comm, s));
     scale = 1.0f / (float)L->world;
   } else {
     // Data parallel, two gradient buckets: the dense one (W3, b3, W4, b4: 6.42 of 6.74 MB) is all-reduced on the
@@ -481,9 +266,8 @@ static void learner_update(qlx_learner* L, uint32_t u_local) {
     const int64_t off_dense = kVarOffsetDense;
     {
       ProfScope ps(&L->prof, "allreduce_dense", L->comm_stream);
-      const ncclResult_t r = ncclAllReduce(on->d_grads + off_dense, on->d_grads + off_dense, (size_t)(kNumParams - off_dense),
-                                           ncclFloat, ncclSum, L->comm, L->comm_stream);
-      QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+      QLX_NCCL(ncclAllReduce(on->d_grads + off_dense, on->d_grads + off_dense, (size_t)(kNumParams - off_dense), ncclFloat, ncclSum,
+                             L->comm, L->comm_stream));
     }
     // the dense variables' clip-norm partials of the reduced bucket (a model that keeps them apart: the fp32 net) ride in
     // the conv backward's reduction launch, which waits for this all-reduce (round 6: dp_single_rank 0.963 -> 0.967 of the
@@ -494,8 +278,7 @@ static void learner_update(qlx_learner* L, uint32_t u_local) {
     QLX_HIP(hipStreamWaitEvent(s, L->ev_reduced, 0));
     {
       ProfScope ps(&L->prof, "allreduce_conv", s);
-      const ncclResult_t r = ncclAllReduce(on->d_grads, on->d_grads, (size_t)off_dense, ncclFloat, ncclSum, L->comm, s);
-      QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+      QLX_NCCL(ncclAllReduce(on->d_grads, on->d_grads, (size_t)off_dense, ncclFloat, ncclSum, L->comm, s));
     }
   }
   model_norms(on, s, scale);
@@ -510,15 +293,19 @@ static void learner_book_allreduce(qlx_learner* L) {
   hipLaunchKernelGGL(k_book_local, dim3(1), dim3(64), 0, s, L->d_book, L->d_hist, (uint32_t)L->p.episode_reward_history_buffer_len,
                      L->d_gsum, L->d_gmin);
   QLX_HIP(hipGetLastError());
-  ncclResult_t r = ncclAllReduce(L->d_gsum, L->d_gsum, 3, ncclFloat64, ncclSum, L->comm, s);
-  QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-  r = ncclAllReduce(L->d_gmin, L->d_gmin, 1, ncclFloat, ncclMin, L->comm, s);
-  QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+  QLX_NCCL(ncclAllReduce(L->d_gsum, L->d_gsum, 3, ncclFloat64, ncclSum, L->comm, s));
+  QLX_NCCL(ncclAllReduce(L->d_gmin, L->d_gmin, 1, ncclFloat, ncclMin, L->comm, s));
 }
 
 // the goal solved() tests: Environment::episode_reward_goal_mean (breakout_environment.rs:203-206) unless mocked
 static float learner_goal(const qlx_learner* L) {
   return std::isnan(L->p.episode_reward_goal) ? (float)(kNumBricks - 1) : L->p.episode_reward_goal;
+}
+
+// learning_update_log (self_driving_tf_q_learner.rs:235-273) as of now
+static std::string learner_log(qlx_learner* L) {
+  static const char* const kNames[kActions] = {"None", "Left", "Right"};   // BreakoutAction Debug
+  return L->update_log(learner_goal(L), kNames, kActions, L->rb->d_action, L->rb->len());
 }
 
 static void learner_vector_step(qlx_learner* L, bool train = true) {
@@ -533,13 +320,8 @@ static void learner_vector_step(qlx_learner* L, bool train = true) {
     Fc2Args a = fc2_args(L->online, (int)N);
     model_head(L->online, 0, a, (int)N, s);
   }
-  {
-    ProfScope ps(&L->prof, "select", s);
-    launch_select_actions(s, N, kActions, step_before, L->p.epsilon_pure_random_steps, L->d_eps, L->eps_len, L->p.epsilon_min,
-                          L->p.learner_seed, (uint32_t)L->rank * N, (uint32_t)L->vec_steps, L->online->w.q, L->d_actions);
-  }
+  L->select_actions(L->online->w.q, kActions, (uint32_t)L->rank * N, &L->prof);
   debug_sync(s, "act + select");
-  L->step_count += N;
   // ---- env step (physics + frame) and replay push
   {
     ProfScope ps(&L->prof, "env_step", s, 7190.0 * N);   // state r/w + new frame + action/reward/done
@@ -549,10 +331,7 @@ static void learner_vector_step(qlx_learner* L, bool train = true) {
   {
     ProfScope ps(&L->prof, "replay_push", s, 2.0 * 7056.0 * N + 10.0 * N);   // frame read + write + metadata
     replay_launch_push(L->rb, L->env, s, L->d_actions, L->d_rewards, L->d_dones);
-    if (L->per) {
-      ProfScope pp(&L->prof, "per_push", s);
-      per_launch_push(s, L->prio.leaves(), L->rb->cap, L->rb->total - N, N, L->prio.d_max);
-    }
+    L->per_push(L->rb->cap, L->rb->total - N, &L->prof);
   }
   debug_sync(s, "replay_push");
   if (L->ycache) {   // y of the N new transitions (all live slots after a write of the target weights)
@@ -568,46 +347,23 @@ static void learner_vector_step(qlx_learner* L, bool train = true) {
   }
   {
     ProfScope ps(&L->prof, "episode_reset", s);
-    launch_episode_book(s, N, L->d_rewards, L->d_dones, L->env->d_ep_steps, L->p.max_steps_per_episode, L->d_ep_reward, L->d_hist,
-                        (uint32_t)L->p.episode_reward_history_buffer_len, L->d_book, L->d_reset);
+    L->episode_book(L->env->d_ep_steps);
     env_launch_reset(L->env, L->d_reset, 1);
   }
   debug_sync(s, "episode book + reset");
   if (L->comm && L->world > 1) learner_book_allreduce(L);   // global solved(): every vector step
   // ---- training updates
-  const uint64_t ua = L->p.update_after_actions;
-  const uint64_t triggers = L->step_count / ua - step_before / ua;
   L->last_updates = 0;
-  if (train && L->rb->len() > L->B && triggers > 0) {
-    const uint32_t U = (uint32_t)triggers;
-    QLX_CHECK(U <= L->max_updates, QLX_E_STATE, "too many updates per vector step");
-    const uint64_t cap = L->rb->cap, start = (L->rb->total - L->rb->len()) % cap;
-    {
-      ProfScope ps(&L->prof, "sample", s);
-      if (L->per) {
-        {
-          ProfScope pb(&L->prof, "per_tree_build", s);
-          per_launch_build(s, L->prio.d_tree, L->prio.L);
-        }
-        ProfScope pd(&L->prof, "per_draw", s);
-        per_launch_sample(s, L->prio.d_tree, L->prio.L, L->p.learner_seed, (uint32_t)L->update_count, U, (uint32_t)L->rank,
-                          L->rb->len(), L->p.per_beta, L->B, cap, start, L->d_idx, L->prio.d_w);
-      } else {
-        replay_launch_sample(L->rb, s, L->p.learner_seed, (uint32_t)L->update_count, U, (uint32_t)L->rank, L->B, L->d_idx);
-      }
-    }
+  if (const uint32_t U = train ? L->updates_due(step_before, L->rb->len()) : 0) {
+    const uint64_t len = L->rb->len(), cap = L->rb->cap, start = (L->rb->total - len) % cap;
+    L->sample(U, len, cap, start, &L->prof);
     debug_sync(s, "sample");
     learner_targets(L, U);
     for (uint32_t u = 0; u < U; ++u) learner_update(L, u);
-    if (L->per) {
-      ProfScope ps(&L->prof, "priorities", s);
-      per_launch_update(s, L->d_idx, L->prio.d_td, U * L->B, cap, start, L->p.per_alpha, L->p.per_eps, L->prio.d_owner,
-                        L->prio.leaves(), L->prio.d_max);
-    }
+    L->write_priorities(U, cap, start, &L->prof);
     L->last_updates = U;
   }
-  const uint64_t ts = L->p.target_sync_steps;
-  if (ts > 0 && L->step_count / ts != step_before / ts) {
+  if (L->target_sync_due(step_before)) {
     QLX_HIP(hipMemcpyAsync(L->target->d_params, L->online->d_params, kNumParams * sizeof(float), hipMemcpyDeviceToDevice, s));
     model_pack(L->target);
   }
@@ -650,17 +406,11 @@ void qlx_params_default(qlx_params* p) {
 int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** out) {
   return guard([&] {
     QLX_CHECK(p && out, QLX_E_INVALID, "null argument");
-    QLX_CHECK(p->n_envs > 0 && p->batch_size > 0 && p->batch_size <= 4096, QLX_E_INVALID, "bad n_envs / batch_size");
-    QLX_CHECK(p->update_after_actions > 0 && p->history_buffer_len >= p->batch_size, QLX_E_INVALID, "bad parameters");
-    QLX_CHECK(p->episode_reward_history_buffer_len > 0, QLX_E_INVALID, "episode_reward_history_buffer_len must be > 0");
-    QLX_CHECK((p->flags & ~(QLX_LEARNER_DOUBLE_DQN | QLX_LEARNER_PER)) == 0, QLX_E_INVALID, "unknown learner flags");
+    LearnerCore::validate(*p);
     QLX_CHECK(p->qnet_precision == QLX_PREC_F32 || p->qnet_precision == QLX_PREC_BF16, QLX_E_INVALID, "unknown qnet_precision");
     QLX_CHECK(p->qnet_precision == QLX_PREC_BF16 || p->batch_size <= (uint32_t)kF32FwdChunk, QLX_E_INVALID,
               "fp32 batch_size above the forward chunk");
     QLX_CHECK(p->n_step <= QLX_NSTEP_MAX, QLX_E_INVALID, "n_step above QLX_NSTEP_MAX");
-    QLX_CHECK(!(p->flags & QLX_LEARNER_PER) || (std::isfinite(p->per_alpha) && std::isfinite(p->per_beta) && std::isfinite(p->per_eps) &&
-                                                 p->per_alpha >= 0.0f && p->per_beta >= 0.0f && p->per_eps > 0.0f),
-              QLX_E_INVALID, "prioritized replay needs finite alpha >= 0, beta >= 0, eps > 0");
     // ABI note (round 4): NaN, not 0, selects the env's own goal.  A caller that zero-fills the struct instead of starting
     // from qlx_params_default would mock a goal of 0, which any Breakout episode reaches: say so once.
     if (p->episode_reward_goal == 0.0f)
@@ -669,15 +419,9 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
     current_device_checked(device);
     auto* L = new qlx_learner;
     try {   // a failure part-way releases what was built
-      L->ddqn = (p->flags & QLX_LEARNER_DOUBLE_DQN) != 0;
-      L->per = (p->flags & QLX_LEARNER_PER) != 0;
-      L->p = *p;
-      L->device = device;
-      L->N = p->n_envs;
-      L->B = p->batch_size;
+      L->init(*p, device);
       L->rank = (int)p->rank;
       L->n_step = std::max<uint32_t>(p->n_step, 1);
-      QLX_HIP(hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
       int32_t st;
       st = qlx_env_create(QLX_ENV_BREAKOUT, L->N, p->env_seed, device, &L->env);
       QLX_CHECK(st == QLX_OK, st, qlx_last_error());
@@ -701,39 +445,15 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
         L->env->id_offset = p->rank * L->N;
         env_launch_reset(L->env, nullptr, 0);
       }
-      // epsilon table: eps_k after k decrements, k = 0.. until epsilon_min (repeated f64 subtraction)
-      const std::vector<double> eps = epsilon_table(*p);
-      L->eps_len = eps.size();
-      L->d_eps.alloc(eps.size());
-      QLX_HIP(hipMemcpy(L->d_eps, eps.data(), eps.size() * sizeof(double), hipMemcpyHostToDevice));
       const uint32_t N = L->N, B = L->B;
-      L->max_updates = (uint32_t)(N / p->update_after_actions + 2);
-      L->d_actions.alloc(N);
-      L->d_rewards.alloc(N);
-      L->d_dones.alloc(N);
-      L->d_reset.alloc(N);
       L->d_obs_table.alloc((size_t)N * 4);
-      L->d_ep_reward.alloc(N);
-      L->d_hist.alloc(p->episode_reward_history_buffer_len);
-      L->d_book.alloc(1);
       L->h_book.alloc(1);
       L->h_gsum.alloc(3);
       L->d_sparsity.alloc(8);
       L->h_sparsity.alloc(8);
-      const size_t UB = (size_t)L->max_updates * B;   // all batches of one vector step
-      L->d_idx.alloc(UB);
+      const size_t UB = L->max_samples();
       L->d_tab_s.alloc(UB * 4);
       L->d_tab_sn.alloc(UB * 4);
-      L->d_bact.alloc(UB);
-      L->d_brew.alloc(UB);
-      L->d_bdone.alloc(UB);
-      L->d_losses.alloc(L->max_updates);
-      L->d_targets.alloc(UB);
-      QLX_HIP(hipMemsetAsync(L->d_ep_reward, 0, N * sizeof(float), L->stream));
-      QLX_HIP(hipMemsetAsync(L->d_book, 0, sizeof(Book), L->stream));
-      QLX_HIP(hipMemsetAsync(L->d_actions, 0, N, L->stream));
-      QLX_HIP(hipMemsetAsync(L->d_rewards, 0, N * sizeof(float), L->stream));
-      QLX_HIP(hipMemsetAsync(L->d_dones, 0, N, L->stream));
       hipLaunchKernelGGL(k_obs_table, dim3((N * 4 + 255) / 256), dim3(256), 0, L->stream, L->env->d_obs, N, L->d_obs_table);
       QLX_HIP(hipGetLastError());
       model_workspace(L->online, (int)std::max(N, B));
@@ -754,7 +474,6 @@ int32_t qlx_learner_create(const qlx_params* p, int32_t device, qlx_learner** ou
         }
       }
       if (L->ddqn) model_workspace(L->online, (int)(L->max_updates * B));   // + the online pass over s'
-      if (L->per) L->prio.init(p->history_buffer_len, UB);
       QLX_HIP(hipStreamSynchronize(L->stream));
     } catch (...) {
       qlx_learner_destroy(L);
@@ -817,8 +536,7 @@ int32_t qlx_learner_end_episodes(qlx_learner* L, const uint8_t* mask) {
     // the episode bookkeeping of one vector step with zero rewards and the mask as the end condition
     QLX_HIP(hipMemcpyAsync(L->d_reset, mask, L->N, hipMemcpyHostToDevice, s));
     QLX_HIP(hipMemsetAsync(L->d_rewards, 0, L->N * sizeof(float), s));
-    launch_episode_book(s, L->N, L->d_rewards, L->d_reset, L->env->d_ep_steps, L->p.max_steps_per_episode, L->d_ep_reward, L->d_hist,
-                        (uint32_t)L->p.episode_reward_history_buffer_len, L->d_book, L->d_dones);
+    L->episode_book(L->env->d_ep_steps, L->d_reset, L->d_dones);
     env_launch_reset(L->env, L->d_dones, 1);
     QLX_HIP(hipMemsetAsync(L->d_dones, 0, L->N, s));
     // data parallel: the global solved() inputs include these episodes at once (a collective: every rank calls this,
@@ -873,34 +591,8 @@ int32_t qlx_learner_sync(qlx_learner* L) {
 int32_t qlx_learner_stats_get(qlx_learner* L, qlx_learner_stats* out) {
   return guard([&] {
     QLX_CHECK(L && out, QLX_E_INVALID, "null argument");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    Book b;
-    QLX_HIP(hipMemcpy(&b, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-    std::vector<float> hist(b.hist_len);
-    if (b.hist_len) {
-      std::vector<float> ring(L->p.episode_reward_history_buffer_len);
-      QLX_HIP(hipMemcpy(ring.data(), L->d_hist, ring.size() * sizeof(float), hipMemcpyDeviceToHost));
-      for (uint32_t i = 0; i < b.hist_len; ++i) hist[i] = ring[(b.hist_head + i) % ring.size()];
-    }
-    out->step_count = L->step_count;
-    out->vec_steps = L->vec_steps;
-    out->update_count = L->update_count;
-    out->episode_count = b.episode_count;
-    out->replay_len = L->rb->len();
-    // epsilon after step_count decrements
-    double e = L->p.epsilon_max;
-    if (L->step_count < L->eps_len) {
-      QLX_HIP(hipMemcpy(&e, L->d_eps + L->step_count, sizeof(double), hipMemcpyDeviceToHost));
-    } else {
-      e = L->p.epsilon_min;
-    }
-    out->epsilon = e;
-    out->running_reward = b.running_reward;
-    // solved (:134-139): running_reward >= goal && min episode reward >= goal * pct
     const float goal = learner_goal(L);
-    float mn = hist.empty() ? 0.0f : hist[0];
-    for (float v : hist) mn = std::min(mn, v);
-    out->solved = (!hist.empty() && b.running_reward >= goal && mn >= goal * L->p.lowest_episode_reward_goal_threshold_pct) ? 1 : 0;
+    L->stats(goal, L->rb->len(), out);
     if (L->comm && L->world > 1) {
       // data parallel: solved over all ranks' episodes (as of the last vector step) = mean of the ranks' running rewards
       // >= goal and the smallest episode reward of any rank's history >= goal * pct, every rank with a history
@@ -911,9 +603,6 @@ int32_t qlx_learner_stats_get(qlx_learner* L, qlx_learner_stats* out) {
       out->solved = (gs[1] == (double)L->world && gs[0] / (double)L->world >= (double)goal &&
                      gm >= goal * L->p.lowest_episode_reward_goal_threshold_pct) ? 1 : 0;
     }
-    float loss = 0.0f;
-    if (L->last_updates) QLX_HIP(hipMemcpy(&loss, L->d_losses + L->last_updates - 1, 4, hipMemcpyDeviceToHost));
-    out->last_loss = loss;
   });
 }
 
@@ -921,26 +610,14 @@ int32_t qlx_learner_last(qlx_learner* L, uint8_t* actions, float* rewards, uint8
                          uint64_t* indices, float* targets, uint32_t* n_updates) {
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    const uint32_t U = L->last_updates;
-    if (actions) QLX_HIP(hipMemcpy(actions, L->d_actions, L->N, hipMemcpyDeviceToHost));
-    if (rewards) QLX_HIP(hipMemcpy(rewards, L->d_rewards, L->N * sizeof(float), hipMemcpyDeviceToHost));
-    if (dones) QLX_HIP(hipMemcpy(dones, L->d_dones, L->N, hipMemcpyDeviceToHost));
-    if (U && losses) QLX_HIP(hipMemcpy(losses, L->d_losses, U * sizeof(float), hipMemcpyDeviceToHost));
-    if (U && indices) QLX_HIP(hipMemcpy(indices, L->d_idx, (size_t)U * L->B * 8, hipMemcpyDeviceToHost));
-    if (U && targets) QLX_HIP(hipMemcpy(targets, L->d_targets, (size_t)U * L->B * 4, hipMemcpyDeviceToHost));
-    if (n_updates) *n_updates = U;
+    L->last(actions, rewards, dones, losses, indices, targets, n_updates);
   });
 }
 
 int32_t qlx_learner_priorities(qlx_learner* L, float* is_weights, float* leaves, float* per_max) {
   return guard([&] {
     QLX_CHECK(L && L->per, QLX_E_STATE, "learner was created without QLX_LEARNER_PER");
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    const uint32_t U = L->last_updates;
-    if (U && is_weights) QLX_HIP(hipMemcpy(is_weights, L->prio.d_w, (size_t)U * L->B * 4, hipMemcpyDeviceToHost));
-    if (leaves) QLX_HIP(hipMemcpy(leaves, L->prio.leaves(), L->prio.cap * 4, hipMemcpyDeviceToHost));
-    if (per_max) QLX_HIP(hipMemcpy(per_max, L->prio.d_max, 4, hipMemcpyDeviceToHost));
+    L->priorities(is_weights, leaves, per_max);
   });
 }
 
@@ -957,46 +634,24 @@ int32_t qlx_learner_frame_sparsity(qlx_learner* L, double* out) {
   });
 }
 
-// ---- learning statistics (learning_update_log, self_driving_tf_q_learner.rs:235-273; stats.hip) ----
-static std::vector<float> learner_episode_rewards(qlx_learner* L) {
-  QLX_HIP(hipStreamSynchronize(L->stream));
-  Book b;
-  QLX_HIP(hipMemcpy(&b, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-  std::vector<float> ring(L->p.episode_reward_history_buffer_len), out(b.hist_len);
-  QLX_HIP(hipMemcpy(ring.data(), L->d_hist, ring.size() * sizeof(float), hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < b.hist_len; ++i) out[i] = ring[(b.hist_head + i) % ring.size()];
-  return out;
-}
-
 int32_t qlx_learner_action_counts(qlx_learner* L, uint64_t* counts) {
   return guard([&] {
     QLX_CHECK(L && counts, QLX_E_INVALID, "null argument");
-    std::vector<uint64_t> c;
-    action_counts(L->stream, L->rb->d_action, L->rb->len(), kActions, c);
-    std::copy(c.begin(), c.end(), counts);
+    L->action_counts(L->rb->d_action, L->rb->len(), kActions, counts);
   });
 }
 
 int32_t qlx_learner_episode_rewards(qlx_learner* L, float* out, uint64_t cap, uint64_t* n) {
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
-    const std::vector<float> r = learner_episode_rewards(L);
-    if (n) *n = r.size();
-    if (out) std::copy(r.begin(), r.begin() + std::min<uint64_t>(cap, r.size()), out);
+    L->episode_rewards(out, cap, n);
   });
 }
 
 int32_t qlx_learner_update_log(qlx_learner* L, char* buf, size_t cap, size_t* len) {
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
-    static const char* const kNames[kActions] = {"None", "Left", "Right"};   // BreakoutAction Debug
-    qlx_learner_stats st;
-    int32_t rc = qlx_learner_stats_get(L, &st);
-    QLX_CHECK(rc == QLX_OK, rc, qlx_last_error());
-    LogInputs in{st.episode_count, st.step_count, L->p.gamma, st.epsilon, learner_goal(L),
-                 L->p.lowest_episode_reward_goal_threshold_pct, learner_episode_rewards(L), {}, kNames};
-    action_counts(L->stream, L->rb->d_action, L->rb->len(), kActions, in.counts);
-    copy_text(learning_log(in), buf, cap, len);
+    copy_text(learner_log(L), buf, cap, len);
   });
 }
 
@@ -1015,22 +670,12 @@ static void learner_stats_event(qlx_learner* L) {
     const int32_t rc = qlx_model_write_checkpoint(L->online, path);
     QLX_CHECK(rc == QLX_OK, rc, qlx_last_error());
   }
-  Book b;
-  QLX_HIP(hipStreamSynchronize(L->stream));
-  QLX_HIP(hipMemcpy(&b, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-  if (b.hist_len == 0) {
+  if (L->books().book.hist_len == 0) {
     // the reference's log asserts a finished episode (replay_buffer.rs:105-118 avg/min_episode_reward) and would panic;
     // the library logs the counters instead and keeps running
     L->last_log = "episode: 0, steps: " + std::to_string(L->step_count) + " (no finished episode yet)";
   } else {
-    size_t n = 0;
-    int32_t rc = qlx_learner_update_log(L, nullptr, 0, &n);
-    QLX_CHECK(rc == QLX_OK, rc, qlx_last_error());
-    std::string text(n + 1, '\0');
-    rc = qlx_learner_update_log(L, &text[0], text.size(), &n);
-    QLX_CHECK(rc == QLX_OK, rc, qlx_last_error());
-    text.resize(n);
-    L->last_log = text;
+    L->last_log = learner_log(L);
   }
   L->stats_events += 1;
   if (L->log_cb) L->log_cb(L->last_log.c_str(), L->log_user);
@@ -1088,8 +733,7 @@ int32_t qlx_dist_unique_id(uint8_t out[128]) {
   return guard([&] {
     static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId size");
     ncclUniqueId id;
-    const ncclResult_t r = ncclGetUniqueId(&id);
-    QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclGetUniqueId: ") + ncclGetErrorString(r));
+    QLX_NCCL(ncclGetUniqueId(&id));
     std::memcpy(out, &id, 128);
   });
 }
@@ -1104,8 +748,7 @@ int32_t qlx_learner_dist_init(qlx_learner* L, int32_t world, int32_t rank, const
     QLX_HIP(hipSetDevice(L->device));
     ncclUniqueId id;
     std::memcpy(&id, uid, 128);
-    const ncclResult_t r = ncclCommInitRank(&L->comm, world, id, rank);
-    QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
+    QLX_NCCL(ncclCommInitRank(&L->comm, world, id, rank));
     // (measured and not kept, round 6: the communicator stream at the device's highest priority - dp_single_rank 0.96 ->
     // 0.41 of the plain path)
     QLX_HIP(hipStreamCreateWithFlags(&L->comm_stream, hipStreamNonBlocking));
@@ -1124,12 +767,9 @@ int32_t qlx_learner_dist_init(qlx_learner* L, int32_t world, int32_t rank, const
     QLX_HIP(hipStreamSynchronize(L->stream));
     DeviceBuffer<int64_t> d_iter(1);
     QLX_HIP(hipMemcpy(d_iter, &on->iterations, sizeof(int64_t), hipMemcpyHostToDevice));
-    for (float* buf : {on->d_params.get(), on->d_m.get(), on->d_v.get()}) {
-      const ncclResult_t rb = ncclBroadcast(buf, buf, (size_t)kNumParams, ncclFloat, 0, L->comm, L->stream);
-      QLX_CHECK(rb == ncclSuccess, QLX_E_COMM, std::string("ncclBroadcast: ") + ncclGetErrorString(rb));
-    }
-    const ncclResult_t ri = ncclBroadcast(d_iter, d_iter, 1, ncclInt64, 0, L->comm, L->stream);
-    QLX_CHECK(ri == ncclSuccess, QLX_E_COMM, std::string("ncclBroadcast: ") + ncclGetErrorString(ri));
+    for (float* buf : {on->d_params.get(), on->d_m.get(), on->d_v.get()})
+      QLX_NCCL(ncclBroadcast(buf, buf, (size_t)kNumParams, ncclFloat, 0, L->comm, L->stream));
+    QLX_NCCL(ncclBroadcast(d_iter, d_iter, 1, ncclInt64, 0, L->comm, L->stream));
     QLX_HIP(hipMemcpyAsync(L->target->d_params, on->d_params, kNumParams * sizeof(float), hipMemcpyDeviceToDevice, L->stream));
     model_pack(on);
     model_pack(L->target);
@@ -1151,8 +791,7 @@ int32_t qlx_learner_comm_size(qlx_learner* L, int32_t* world) {
     *world = 1;
     if (!L->comm) return;
     int n = 0;
-    const ncclResult_t r = ncclCommCount(L->comm, &n);
-    QLX_CHECK(r == ncclSuccess, QLX_E_COMM, std::string("ncclCommCount: ") + ncclGetErrorString(r));
+    QLX_NCCL(ncclCommCount(L->comm, &n));
     *world = n;
   });
 }
@@ -1204,253 +843,6 @@ int32_t qlx_learner_profile_names(qlx_learner* L, char* buf, size_t cap) {
     for (auto& kv : L->prof.acc) { if (!s.empty()) s += ","; s += kv.first; }
     QLX_CHECK(s.size() < cap, QLX_E_INVALID, "buffer too small");
     std::memcpy(buf, s.c_str(), s.size() + 1);
-  });
-}
-
-}  // extern "C"
-
-// ---------------- snapshots (DESIGN.md "Snapshots") ----------------
-// Everything the next vector step reads: params and host counters, the env (mechanics, episode steps, checksums, ring
-// frames), the replay (replay_write), both models, the episode books, the prioritized-replay leaves and the target memo.
-// Every draw is a function of those counters, so a loaded learner continues bit for bit.  Small sections are built on
-// the host and carry a crc32c; frames go through the frame codec (frame_codec.hip).
-namespace {
-
-constexpr uint64_t kModelSectionBytes = 8 + 3 * (uint64_t)kNumParams * sizeof(float);
-
-void model_section_write(snap::Writer& w, uint32_t id, qlx_model* m) {
-  snap::Blob b;
-  uint8_t* p = b.grow(kModelSectionBytes);
-  int64_t it = 0;
-  model_state_get(m, reinterpret_cast<float*>(p + 8), &it);
-  std::memcpy(p, &it, 8);
-  w.small(id, b.bytes.data(), b.bytes.size());
-}
-
-void model_section_read(snap::Reader& r, uint32_t id, qlx_model* m) {
-  const std::vector<uint8_t> buf = r.small(id, kModelSectionBytes);
-  if (buf.size() != kModelSectionBytes) throw snap::FormatError{"snapshot: model section " + std::to_string(id) + " has the wrong size"};
-  int64_t it = 0;
-  std::memcpy(&it, buf.data(), 8);
-  model_state_put(m, reinterpret_cast<const float*>(buf.data() + 8), it);
-}
-
-template <class T>
-void put_device(snap::Blob& b, const T* dev, uint64_t count) {
-  if (count) QLX_HIP(hipMemcpy(b.grow(count * sizeof(T)), dev, count * sizeof(T), hipMemcpyDeviceToHost));
-}
-template <class T>
-void get_device(snap::BlobReader& br, T* dev, uint64_t count) {
-  if (count) QLX_HIP(hipMemcpy(dev, br.take(count * sizeof(T)), count * sizeof(T), hipMemcpyHostToDevice));
-}
-
-void learner_restore(snap::Reader& r, qlx_learner* L, snap::BlobReader& head, FrameIo* io) {
-  hipStream_t s = L->stream;
-  const uint32_t N = L->N;
-  L->step_count = head.u64();
-  L->vec_steps = head.u64();
-  L->update_count = head.u64();
-  L->stats_events = head.u64();
-  L->seen_episodes = head.u64();
-  const uint64_t log_len = head.u64();
-  const uint8_t* log = head.take(log_len);
-  L->last_log.assign(reinterpret_cast<const char*>(log), log_len);
-  head.done();
-  {   // env
-    const std::vector<uint8_t> buf = r.small(snap::SEC_ENV);
-    snap::BlobReader br(buf, snap::SEC_ENV);
-    qlx_env* e = L->env;
-    if (br.u32() != N) throw snap::FormatError{"snapshot: env section n_envs disagrees with the parameters"};
-    e->id_offset = br.u32();
-    e->seed = br.u64();
-    e->hashing = br.u32() != 0;
-    (void)br.u32();
-    get_device(br, e->d_state.get(), N);
-    get_device(br, e->d_ep_steps.get(), N);
-    get_device(br, e->d_hash.get(), N);
-    get_device(br, e->d_flags.get(), 4);
-    br.done();
-    frames_read(r, snap::SEC_ENV_FRAMES, FrameRing{e->d_obs, (uint64_t)N * kSlots, 0, (uint64_t)N * kSlots}, s, io);
-  }
-  replay_restore(r, L->rb, s, io);
-  model_section_read(r, snap::SEC_MODEL_ONLINE, L->online);
-  model_section_read(r, snap::SEC_MODEL_TARGET, L->target);
-  {   // episode books
-    const std::vector<uint8_t> buf = r.small(snap::SEC_BOOKS);
-    snap::BlobReader br(buf, snap::SEC_BOOKS);
-    const uint32_t hist_cap = (uint32_t)L->p.episode_reward_history_buffer_len;
-    Book b{};
-    b.episode_count = br.u64();
-    b.running_reward = br.f32();
-    b.hist_len = br.u32();
-    b.hist_head = br.u32();
-    if (br.u32() != hist_cap || b.hist_len > hist_cap || (b.hist_head >= hist_cap))
-      throw snap::FormatError{"snapshot: episode reward history disagrees with the parameters"};
-    QLX_HIP(hipMemcpy(L->d_book, &b, sizeof(Book), hipMemcpyHostToDevice));
-    get_device(br, L->d_ep_reward.get(), N);
-    const float* hist = reinterpret_cast<const float*>(br.take((uint64_t)b.hist_len * sizeof(float)));
-    br.done();
-    ring_from_host(L->d_hist.get(), hist, hist_cap, b.hist_head, b.hist_len);
-  }
-  if (L->per) {
-    const std::vector<uint8_t> buf = r.small(snap::SEC_PER);
-    snap::BlobReader br(buf, snap::SEC_PER);
-    if (br.u64() != L->prio.cap) throw snap::FormatError{"snapshot: prioritized-replay capacity disagrees with the parameters"};
-    get_device(br, L->prio.d_max.get(), 1);
-    get_device(br, L->prio.leaves(), L->prio.cap);   // the inner nodes are rebuilt before every draw (per_launch_build)
-    br.done();
-  }
-  if (L->ycache) {
-    if (r.find(snap::SEC_MEMO)) {
-      const std::vector<uint8_t> buf = r.small(snap::SEC_MEMO);
-      snap::BlobReader br(buf, snap::SEC_MEMO);
-      const uint64_t len = L->rb->len();
-      if (br.u64() != len) throw snap::FormatError{"snapshot: target memo length disagrees with the replay"};
-      const float* y = reinterpret_cast<const float*>(br.take(len * sizeof(float)));
-      br.done();
-      ring_from_host(L->d_ycache.get(), y, L->rb->cap, (L->rb->total - len) % L->rb->cap, len);
-      L->ycache_version = L->target->version;
-    } else {
-      L->ycache_version = L->target->version - 1;   // no memo in the file: the next push rebuilds every live slot
-    }
-  }
-  L->last_updates = 0;
-  QLX_HIP(hipStreamSynchronize(s));
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t qlx_learner_save(qlx_learner* L, const char* path) {
-  return guard([&] {
-    QLX_CHECK(L && path, QLX_E_INVALID, "null argument");
-    QLX_HIP(hipSetDevice(L->device));
-    QLX_HIP(hipStreamSynchronize(L->stream));
-    if (L->comm_stream) QLX_HIP(hipStreamSynchronize(L->comm_stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t s = L->stream;
-    const uint32_t N = L->N;
-    FrameIo io;
-    io.codec = snapshot_codec_from_env();
-    snapshot_timing_begin(&io);
-    uint64_t file_bytes = 0;
-    io_guard([&] {
-      snap::Writer w(path, QLX_SNAPSHOT_LEARNER);
-      Book book;
-      QLX_HIP(hipMemcpy(&book, L->d_book, sizeof(Book), hipMemcpyDeviceToHost));
-      {
-        snap::Blob b;
-        b.put(&L->p, sizeof(qlx_params));
-        b.u32(L->p.qnet_precision);
-        b.u32((uint32_t)L->rank);
-        b.u64(L->step_count);
-        b.u64(L->vec_steps);
-        b.u64(L->update_count);
-        b.u64(L->stats_events);
-        b.u64(L->seen_episodes);
-        b.u64(L->last_log.size());
-        b.put(L->last_log.data(), L->last_log.size());
-        w.small(snap::SEC_LEARNER, b.bytes.data(), b.bytes.size());
-      }
-      {
-        const qlx_env* e = L->env;
-        snap::Blob b;
-        b.u32(N);
-        b.u32(e->id_offset);
-        b.u64(e->seed);
-        b.u32(e->hashing ? 1 : 0);
-        b.u32(0);
-        put_device(b, e->d_state.get(), N);
-        put_device(b, e->d_ep_steps.get(), N);
-        put_device(b, e->d_hash.get(), N);
-        put_device(b, e->d_flags.get(), 4);
-        w.small(snap::SEC_ENV, b.bytes.data(), b.bytes.size());
-        frames_write(w, snap::SEC_ENV_FRAMES, FrameRing{e->d_obs, (uint64_t)N * kSlots, 0, (uint64_t)N * kSlots}, s, &io);
-      }
-      replay_write(w, L->rb, s, &io);
-      model_section_write(w, snap::SEC_MODEL_ONLINE, L->online);
-      model_section_write(w, snap::SEC_MODEL_TARGET, L->target);
-      {
-        const uint32_t hist_cap = (uint32_t)L->p.episode_reward_history_buffer_len;
-        snap::Blob b;
-        b.u64(book.episode_count);
-        b.f32(book.running_reward);
-        b.u32(book.hist_len);
-        b.u32(book.hist_head);
-        b.u32(hist_cap);
-        put_device(b, L->d_ep_reward.get(), N);
-        // the entries in use, oldest first (the rest of the ring was never written)
-        if (book.hist_len)
-          ring_to_host(reinterpret_cast<float*>(b.grow((uint64_t)book.hist_len * sizeof(float))), L->d_hist.get(), hist_cap,
-                       book.hist_head, book.hist_len);
-        w.small(snap::SEC_BOOKS, b.bytes.data(), b.bytes.size());
-      }
-      if (L->per) {
-        snap::Blob b;
-        b.u64(L->prio.cap);
-        put_device(b, L->prio.d_max.get(), 1);
-        put_device(b, L->prio.leaves(), L->prio.cap);
-        w.small(snap::SEC_PER, b.bytes.data(), b.bytes.size());
-      }
-      if (L->ycache && L->ycache_version == L->target->version) {   // y (or v) of the live slots, oldest first
-        const uint64_t len = L->rb->len();
-        snap::Blob b;
-        b.u64(len);
-        if (len)
-          ring_to_host(reinterpret_cast<float*>(b.grow(len * sizeof(float))), L->d_ycache.get(), L->rb->cap,
-                       (L->rb->total - len) % L->rb->cap, len);
-        w.small(snap::SEC_MEMO, b.bytes.data(), b.bytes.size());
-      }
-      qlx_snapshot_info info{};
-      info.format_version = QLX_SNAPSHOT_VERSION;
-      info.kind = QLX_SNAPSHOT_LEARNER;
-      info.frame_codec = (uint32_t)io.codec;
-      info.step_count = L->step_count;
-      info.vec_steps = L->vec_steps;
-      info.update_count = L->update_count;
-      info.episode_count = book.episode_count;
-      info.replay_len = L->rb->len();
-      info.replay_total = L->rb->total;
-      info.frames = io.frames;
-      info.frame_bytes_raw = io.raw_bytes;
-      info.frame_bytes_stored = io.stored_bytes;
-      info.file_bytes = w.position() + sizeof(info);
-      info.params = L->p;
-      w.small(snap::SEC_INFO, &info, sizeof(info));
-      file_bytes = w.finish();
-    });
-    snapshot_timing_report("learner_save", io, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), file_bytes);
-  });
-}
-
-int32_t qlx_learner_load(const char* path, int32_t device, qlx_learner** out) {
-  return guard([&] {
-    QLX_CHECK(path && out, QLX_E_INVALID, "null argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    FrameIo io;
-    snapshot_timing_begin(&io);
-    io_guard([&] {
-      snap::Reader r(path, QLX_SNAPSHOT_LEARNER);
-      const std::vector<uint8_t> buf = r.small(snap::SEC_LEARNER, 1u << 24);
-      snap::BlobReader head(buf, snap::SEC_LEARNER);
-      qlx_params p;
-      head.get(&p, sizeof(p));
-      if (head.u32() != p.qnet_precision || head.u32() != p.rank)
-        throw snap::FormatError{"snapshot: learner section disagrees with its parameters"};
-      qlx_learner* L = nullptr;
-      const int32_t st = qlx_learner_create(&p, device, &L);
-      QLX_CHECK(st == QLX_OK, st, qlx_last_error());
-      try {
-        learner_restore(r, L, head, &io);
-      } catch (...) {
-        qlx_learner_destroy(L);
-        throw;
-      }
-      *out = L;
-      snapshot_timing_report("learner_load", io, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
-                             r.header().file_bytes);
-    });
   });
 }
 

@@ -173,11 +173,6 @@ void launch_sample_distinct(hipStream_t s, uint64_t seed, uint32_t first_update,
   QLX_HIP(hipGetLastError());
 }
 
-void replay_launch_sample(qlx_replay* rb, hipStream_t s, uint64_t seed, uint32_t first_update, uint32_t n_updates,
-                          uint32_t rank, uint32_t batch, uint64_t* d_out) {
-  launch_sample_distinct(s, seed, first_update, n_updates, rank, (uint64_t)rb->len(), batch, d_out);
-}
-
 }  // namespace qlx
 
 using namespace qlx;
@@ -253,7 +248,7 @@ int32_t qlx_replay_sample_distinct(qlx_replay* r, uint64_t seed, uint32_t update
     QLX_HIP(hipSetDevice(r->device));
     QLX_HIP(hipDeviceSynchronize());
     r->d_idx.reserve(batch);
-    replay_launch_sample(r, r->stream, seed, update_idx, 1, rank, batch, r->d_idx);
+    launch_sample_distinct(r->stream, seed, update_idx, 1, rank, r->len(), batch, r->d_idx);
     QLX_HIP(hipMemcpyAsync(out, r->d_idx, batch * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
     QLX_HIP(hipStreamSynchronize(r->stream));
   });
