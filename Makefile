@@ -16,7 +16,8 @@ LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
 OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
         $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o \
-        $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o $(OUT)/obj/learner_core.o $(OUT)/obj/learner_snapshot.o
+        $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o $(OUT)/obj/learner_core.o $(OUT)/obj/learner_snapshot.o \
+        $(OUT)/obj/metrics.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
 
@@ -65,6 +66,11 @@ $(OUT)/obj/learner_core.o: $(SRC)/learner_core.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 
 $(OUT)/obj/learner_snapshot.o: $(SRC)/learner_snapshot.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+
+# per-update training metrics: its td = |q_a - y| and action gaps are single fp32 roundings the tests restate bit for bit
+# (learner.o's flags)
+$(OUT)/obj/metrics.o: $(SRC)/metrics.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 
 # policy evaluation: fp32 sums compared bit for bit with the oracle restatement, like the learner's books

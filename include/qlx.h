@@ -473,6 +473,55 @@ int32_t qlx_bg_learner_update_log(qlx_bg_learner* l, char* buf, size_t cap, size
 qlx_bg_env* qlx_bg_learner_env(qlx_bg_learner* l);
 qlx_bg_model* qlx_bg_learner_model(qlx_bg_learner* l, int32_t which /* 0 online, 1 target */);
 
+/* ---------------- Training metrics (beyond the reference; its nearest interface is learning_update_log) ----------------
+ * Opt-in, per learner: once enabled, every training update appends one 256-byte row to a ring in device memory (one small
+ * kernel after the update's Adam, nothing copied, no synchronisation), and the host drains the ring whenever it likes.
+ * With metrics off (the default, and after a load: not part of a snapshot) no launch, allocation or result changes.
+ * All statistics are over the update's batch; means are accumulated in double in a fixed order and rounded to float once,
+ * and every field is bit-reproducible from run to run.  Rows are local to the rank (no collective). */
+typedef struct qlx_update_metrics {
+  uint64_t update;        /* update_count before this update (0-based, consecutive) */
+  uint64_t step_count;    /* learner step_count when the update was enqueued */
+  uint32_t batch, n_actions, n_vars;   /* B; 3 (Breakout) / 5 (BallGame); 10 / 8 */
+  uint32_t n_clipped;     /* variables v < n_vars with grad_norm[v] > clipnorm */
+  uint32_t n_linear;      /* samples with |td| > 1 (Huber's linear branch; counted for BallGame's MSE too) */
+  uint32_t n_nonfinite;   /* samples whose q_a or y is not finite (the float statistics are then only reproducible) */
+  float loss;             /* the update's loss, the same bits qlx_learner_last reports */
+  float q_taken_mean, q_taken_min, q_taken_max;   /* q_a = Q(s)[action] as the training head wrote it */
+  float q_max_mean;       /* mean of max_a Q(s) */
+  float action_gap_mean;  /* mean of (largest - second largest of Q(s)); 0 for exact ties */
+  float y_mean, y_min, y_max;          /* the targets */
+  float td_abs_mean, td_abs_max;       /* td = |q_a - y|, one fp32 subtraction */
+  float weight_mean;      /* mean importance-sampling weight (prioritized replay), else 1.0f */
+  float grad_norm_global; /* (float)sqrt(sum_{v<n_vars} (double)grad_norm[v]^2), v ascending */
+  uint32_t reserved;      /* 0 */
+  uint32_t argmax_counts[8];   /* samples per first-argmax action of Q(s); entries >= n_actions are 0 */
+  float grad_norm[16];         /* pre-clip L2 norm per variable of the gradient Adam used (data parallel: of the reduced,
+                                  scaled one); entries >= n_vars are 0 */
+  uint32_t td_hist[16];        /* |td| by binary exponent, see qlx_metrics_td_bin */
+} qlx_update_metrics;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_update_metrics) == 256, "qlx_update_metrics ABI size");
+#endif
+
+/* Host only: the td_hist bin of |td| as the kernel computes it (from the exponent bits): bin 0 holds |td| < 2^-11
+ * (0 and denormals included), bin k = 1..14 holds 2^(k-12) <= |td| < 2^(k-11), bin 15 holds |td| >= 8, +inf and NaN. */
+int32_t qlx_metrics_td_bin(float td_abs);
+/* A ring of `capacity` rows (and its pinned staging buffer), replacing any earlier one; recorded and unread restart at 0
+ * while `update` carries on from update_count.  0 = metrics off and the ring freed; above 1 << 20: QLX_E_INVALID.
+ * Synchronises.  The row of the r-th recorded update lands in slot r % capacity. */
+int32_t qlx_learner_metrics_enable(qlx_learner* l, uint32_t capacity);
+/* Host counters, no synchronisation: the capacity, the updates recorded since enable, and the rows a read would return
+ * now (unread ones not yet overwritten).  QLX_E_STATE with metrics off. */
+int32_t qlx_learner_metrics_info(qlx_learner* l, uint32_t* capacity, uint64_t* recorded, uint64_t* unread);
+/* Synchronises the learner stream; up to `cap` of the oldest unread rows that still exist into out, oldest first (the
+ * rest stay unread); *n = rows written, *dropped = unread rows that were overwritten since the previous read.
+ * QLX_E_STATE with metrics off. */
+int32_t qlx_learner_metrics_read(qlx_learner* l, qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped);
+int32_t qlx_bg_learner_metrics_enable(qlx_bg_learner* l, uint32_t capacity);
+int32_t qlx_bg_learner_metrics_info(qlx_bg_learner* l, uint32_t* capacity, uint64_t* recorded, uint64_t* unread);
+int32_t qlx_bg_learner_metrics_read(qlx_bg_learner* l, qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped);
+
 /* ---------------- TF tensor bundles (the reference's model / checkpoint storage) ----------------
  * Host-only reader of variables.index (SSTable of BundleEntryProto) + variables.data-*; block and tensor
  * crc32c are verified.  Replaces SavedModelBundle::load's variable restore (q_learning_model.rs:47-52). */

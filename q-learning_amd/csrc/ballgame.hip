@@ -614,6 +614,8 @@ static void learner_vector_step(qlx_bg_learner* L) {
       backward(L->online, xs, (int)B, L->d_bact + (size_t)u * B, L->d_targets + (size_t)u * B, L->d_losses + u, s,
                L->per ? L->prio.d_w + (size_t)u * B : nullptr, L->per ? L->prio.d_td + (size_t)u * B : nullptr);
       apply_adam(L->online, s);
+      L->record_metrics(L->online->w.q, kA, L->online->d_norms, kVars, L->online->clipnorm, L->d_bact + (size_t)u * B,
+                        L->d_targets + (size_t)u * B, L->per ? L->prio.d_w + (size_t)u * B : nullptr, L->d_losses + u);
       L->update_count += 1;
     }
     L->write_priorities(U, L->cap, start);
@@ -1005,6 +1007,27 @@ int32_t qlx_bg_learner_last(qlx_bg_learner* L, uint8_t* actions, float* rewards,
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
     L->last(actions, rewards, dones, losses, indices, targets, n_updates);
+  });
+}
+
+int32_t qlx_bg_learner_metrics_enable(qlx_bg_learner* L, uint32_t capacity) {
+  return guard([&] {
+    QLX_CHECK(L, QLX_E_INVALID, "null learner");
+    L->metrics_enable(capacity);
+  });
+}
+
+int32_t qlx_bg_learner_metrics_info(qlx_bg_learner* L, uint32_t* capacity, uint64_t* recorded, uint64_t* unread) {
+  return guard([&] {
+    QLX_CHECK(L && capacity && recorded && unread, QLX_E_INVALID, "null argument");
+    L->metrics_info(capacity, recorded, unread);
+  });
+}
+
+int32_t qlx_bg_learner_metrics_read(qlx_bg_learner* L, qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped) {
+  return guard([&] {
+    QLX_CHECK(L && out && n && dropped, QLX_E_INVALID, "null argument");
+    L->metrics_read(out, cap, n, dropped);
   });
 }
 

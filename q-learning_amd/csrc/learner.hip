@@ -283,6 +283,9 @@ static void learner_update(qlx_learner* L, uint32_t u_local) {
   }
   model_norms(on, s, scale);
   model_adam(on, s, scale);
+  // (after Adam: d_norms is final; before the next update's forward overwrites w.q)
+  L->record_metrics(on->w.q, kActions, on->d_norms, kNumVars, on->clipnorm, bact, L->d_targets + (size_t)u_local * B, isw,
+                    L->d_losses + u_local, &L->prof);
   L->update_count += 1;
 }
 
@@ -652,6 +655,27 @@ int32_t qlx_learner_update_log(qlx_learner* L, char* buf, size_t cap, size_t* le
   return guard([&] {
     QLX_CHECK(L, QLX_E_INVALID, "null learner");
     copy_text(learner_log(L), buf, cap, len);
+  });
+}
+
+int32_t qlx_learner_metrics_enable(qlx_learner* L, uint32_t capacity) {
+  return guard([&] {
+    QLX_CHECK(L, QLX_E_INVALID, "null learner");
+    L->metrics_enable(capacity);
+  });
+}
+
+int32_t qlx_learner_metrics_info(qlx_learner* L, uint32_t* capacity, uint64_t* recorded, uint64_t* unread) {
+  return guard([&] {
+    QLX_CHECK(L && capacity && recorded && unread, QLX_E_INVALID, "null argument");
+    L->metrics_info(capacity, recorded, unread);
+  });
+}
+
+int32_t qlx_learner_metrics_read(qlx_learner* L, qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped) {
+  return guard([&] {
+    QLX_CHECK(L && out && n && dropped, QLX_E_INVALID, "null argument");
+    L->metrics_read(out, cap, n, dropped);
   });
 }
 

@@ -58,6 +58,11 @@ struct LearnerCore {
   DeviceBuffer<float> d_brew;
   DeviceBuffer<float> d_targets;      // [max_updates][B]
   DeviceBuffer<float> d_losses;       // [max_updates]
+  // training metrics (metrics.hip; off unless metrics_enable allocated the ring): the row of the r-th recorded update is
+  // in slot r % capacity; the host has consumed (read or counted as dropped) the first metrics_next of them
+  DeviceBuffer<qlx_update_metrics> d_metrics;   // [capacity]
+  PinnedBuffer<qlx_update_metrics> h_metrics;   // [capacity] staging of metrics_read
+  uint64_t metrics_recorded = 0, metrics_next = 0;
 
   // ---- setup
   // the parameter checks both learners share (p non-null); each learner adds its own
@@ -88,6 +93,11 @@ struct LearnerCore {
     const uint64_t ts = p.target_sync_steps;
     return ts > 0 && step_count / ts != step_before / ts;
   }
+  // training metrics of the update being enqueued, into the ring's next slot: called after the update's Adam (d_norms is
+  // final) and before update_count advances; q [B][n_actions] is what the training head wrote, actions / y / weights
+  // (null without prioritized replay) / loss are the update's.  With metrics off it returns before touching the device.
+  void record_metrics(const float* q, uint32_t n_actions, const float* d_norms, uint32_t n_vars, float clipnorm,
+                      const uint8_t* actions, const float* y, const float* weights, const float* loss, Profiler* prof = nullptr);
 
   // ---- read-outs (each synchronises the stream); the arguments are what the two environments differ in
   EpisodeBooks books();
@@ -98,6 +108,10 @@ struct LearnerCore {
   void action_counts(const uint8_t* d_replay_actions, uint64_t replay_len, uint32_t n_actions, uint64_t* counts);
   std::string update_log(float goal, const char* const* action_names, uint32_t n_actions, const uint8_t* d_replay_actions,
                          uint64_t replay_len);
+  // the metrics ring (qlx_learner_metrics_enable / _info / _read); enable and read synchronise the stream
+  void metrics_enable(uint32_t capacity);
+  void metrics_info(uint32_t* capacity, uint64_t* recorded, uint64_t* unread) const;
+  void metrics_read(qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped);
 };
 
 }  // namespace qlx

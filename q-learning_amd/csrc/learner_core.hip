@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "metrics.h"
 #include "objects.h"
 #include "profiler.h"
 #include "stats.h"
@@ -228,6 +229,72 @@ void LearnerCore::write_priorities(uint32_t U, uint64_t cap, uint64_t start, Pro
   if (!per) return;
   ProfScope ps(prof, "priorities", stream);
   per_launch_update(stream, d_idx, prio.d_td, U * B, cap, start, p.per_alpha, p.per_eps, prio.d_owner, prio.leaves(), prio.d_max);
+}
+
+void LearnerCore::record_metrics(const float* q, uint32_t n_actions, const float* d_norms, uint32_t n_vars, float clipnorm,
+                                 const uint8_t* actions, const float* y, const float* weights, const float* loss, Profiler* prof) {
+  if (!d_metrics) return;
+  ProfScope ps(prof, "metrics", stream);
+  MetricsArgs a{};
+  a.q = q;
+  a.actions = actions;
+  a.y = y;
+  a.weights = weights;
+  a.loss = loss;
+  a.norms = d_norms;
+  a.B = B;
+  a.n_actions = n_actions;
+  a.n_vars = n_vars;
+  a.clipnorm = clipnorm;
+  a.update = update_count;
+  a.step_count = step_count;
+  a.row = d_metrics + metrics_recorded % d_metrics.size();
+  launch_update_metrics(stream, a);
+  metrics_recorded += 1;
+}
+
+// ---- the metrics ring -----------------------------------------------------------------------------
+
+void LearnerCore::metrics_enable(uint32_t capacity) {
+  QLX_CHECK(capacity <= kMetricsMaxRows, QLX_E_INVALID, "metrics capacity above 1 << 20 rows");
+  QLX_HIP(hipSetDevice(device));
+  QLX_HIP(hipStreamSynchronize(stream));   // an enqueued update may still write the old ring
+  d_metrics.release();
+  h_metrics.release();
+  metrics_recorded = metrics_next = 0;
+  if (!capacity) return;
+  h_metrics.alloc(capacity);
+  d_metrics.alloc(capacity);
+}
+
+// the oldest recorded update whose row a read can still return
+static uint64_t metrics_first(const LearnerCore& c) {
+  const uint64_t cap = c.d_metrics.size();
+  return std::max(c.metrics_next, c.metrics_recorded - std::min(c.metrics_recorded, cap));
+}
+
+void LearnerCore::metrics_info(uint32_t* capacity, uint64_t* recorded, uint64_t* unread) const {
+  QLX_CHECK(d_metrics, QLX_E_STATE, "metrics are off (qlx_learner_metrics_enable)");
+  if (capacity) *capacity = (uint32_t)d_metrics.size();
+  if (recorded) *recorded = metrics_recorded;
+  if (unread) *unread = metrics_recorded - metrics_first(*this);
+}
+
+void LearnerCore::metrics_read(qlx_update_metrics* out, uint64_t cap, uint64_t* n, uint64_t* dropped) {
+  QLX_CHECK(d_metrics, QLX_E_STATE, "metrics are off (qlx_learner_metrics_enable)");
+  QLX_HIP(hipSetDevice(device));
+  const uint64_t ring = d_metrics.size(), first = metrics_first(*this);
+  const uint64_t m = std::min(cap, metrics_recorded - first);
+  // slots first % ring .. in ring order: one copy, or two where the rows wrap
+  const uint64_t s0 = first % ring, m0 = std::min(m, ring - s0);
+  if (m0) QLX_HIP(hipMemcpyAsync(h_metrics, d_metrics + s0, m0 * sizeof(qlx_update_metrics), hipMemcpyDeviceToHost, stream));
+  if (m > m0)
+    QLX_HIP(hipMemcpyAsync(h_metrics + m0, d_metrics, (m - m0) * sizeof(qlx_update_metrics), hipMemcpyDeviceToHost, stream));
+  QLX_HIP(hipStreamSynchronize(stream));
+  std::copy(h_metrics.get(), h_metrics.get() + m, out);
+  *n = m;
+  *dropped = first - metrics_next;
+  metrics_next = first + m;
 }
 
 // ---- read-outs ------------------------------------------------------------------------------------

@@ -121,6 +121,51 @@ class SnapshotInfo(C.Structure):
         ("params", Params)]
 
 
+class UpdateMetrics(C.Structure):
+    """qlx_update_metrics: one row per training update (training metrics, beyond the reference)"""
+    _fields_ = [("update", C.c_uint64), ("step_count", C.c_uint64)] + [
+        (k, C.c_uint32) for k in ("batch", "n_actions", "n_vars", "n_clipped", "n_linear", "n_nonfinite")] + [
+        (k, C.c_float) for k in ("loss", "q_taken_mean", "q_taken_min", "q_taken_max", "q_max_mean", "action_gap_mean",
+                                 "y_mean", "y_min", "y_max", "td_abs_mean", "td_abs_max", "weight_mean",
+                                 "grad_norm_global")] + [
+        ("reserved", C.c_uint32), ("argmax_counts", C.c_uint32 * 8), ("grad_norm", C.c_float * 16),
+        ("td_hist", C.c_uint32 * 16)]
+
+
+_NP_OF_C = {C.c_uint64: "<u8", C.c_uint32: "<u4", C.c_float: "<f4"}
+# the same row as a numpy structured dtype (what metrics() returns an array of)
+UPDATE_METRICS_DTYPE = np.dtype([(k, _NP_OF_C[t]) if t in _NP_OF_C else (k, _NP_OF_C[t._type_], (t._length_,))
+                                 for k, t in UpdateMetrics._fields_])
+
+
+def metrics_td_bin(x):
+    """the td_hist bin of |td| = x (qlx_metrics_td_bin, host only): the function the metrics kernel uses"""
+    return int(lib().qlx_metrics_td_bin(C.c_float(x)))
+
+
+class _Metrics:
+    """Per-update training metrics of a learner handle (qlx_*_metrics_enable / _info / _read)"""
+
+    def metrics_enable(self, capacity):
+        """a ring of `capacity` rows in device memory, one row per update from now on; 0 turns metrics off"""
+        _check(getattr(lib(), self._prefix + "_metrics_enable")(self.h, capacity))
+
+    def metrics_info(self):
+        """dict(capacity, recorded, unread) from host counters (no synchronisation)"""
+        cap, rec, unread = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(getattr(lib(), self._prefix + "_metrics_info")(self.h, C.byref(cap), C.byref(rec), C.byref(unread)))
+        return dict(capacity=cap.value, recorded=rec.value, unread=unread.value)
+
+    def metrics(self, max_rows=None):
+        """(rows, dropped): the unread rows, oldest first, as an array of UPDATE_METRICS_DTYPE (all of them, or at most
+        max_rows) and how many unread rows were overwritten since the previous call; synchronises"""
+        cap = self.metrics_info()["unread"] if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), UPDATE_METRICS_DTYPE)
+        n, dropped = C.c_uint64(), C.c_uint64()
+        _check(getattr(lib(), self._prefix + "_metrics_read")(self.h, _p(rows), cap, C.byref(n), C.byref(dropped)))
+        return rows[:n.value], dropped.value
+
+
 def _eval_config(n_envs, episodes_per_env=1, max_steps_per_episode=10_000, epsilon=0.0, env_seed=0x51A5EED,
                  policy_seed=1, poll_steps=0, flags=0):
     return EvalConfig(n_envs=n_envs, episodes_per_env=episodes_per_env, max_steps_per_episode=max_steps_per_episode,
@@ -195,6 +240,12 @@ def lib():
         "qlx_learner_last": ([vp, vp, vp, vp, vp, vp, vp, C.POINTER(u32)], i32),
         "qlx_learner_env": ([vp], vp), "qlx_learner_replay": ([vp], vp), "qlx_learner_model": ([vp, i32], vp),
         "qlx_learner_priorities": ([vp, vp, vp, vp], i32),
+        "qlx_metrics_td_bin": ([f32], i32),
+        "qlx_learner_metrics_enable": ([vp, u32], i32), "qlx_bg_learner_metrics_enable": ([vp, u32], i32),
+        "qlx_learner_metrics_info": ([vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64)], i32),
+        "qlx_bg_learner_metrics_info": ([vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64)], i32),
+        "qlx_learner_metrics_read": ([vp, vp, u64, C.POINTER(u64), C.POINTER(u64)], i32),
+        "qlx_bg_learner_metrics_read": ([vp, vp, u64, C.POINTER(u64), C.POINTER(u64)], i32),
         "qlx_learner_frame_sparsity": ([vp, vp], i32),
         "qlx_learner_action_counts": ([vp, vp], i32), "qlx_bg_learner_action_counts": ([vp, vp], i32),
         "qlx_learner_episode_rewards": ([vp, vp, u64, C.POINTER(u64)], i32),
@@ -602,7 +653,7 @@ class Evaluator:
         return dict(returns=ret, lengths=length, terminals=term.astype(bool), max_q_sums=qs)
 
 
-class SelfDrivingQLearner(_LearningStats):
+class SelfDrivingQLearner(_LearningStats, _Metrics):
     """SelfDrivingQLearner with n parallel envs on one GPU (vector-step generalisation)."""
     _n_actions = 3
 
@@ -876,7 +927,7 @@ class BallGameModel:
         return (float(loss[0]), g, nrm) if want_grads else float(loss[0])
 
 
-class BallGameLearner(_LearningStats):
+class BallGameLearner(_LearningStats, _Metrics):
     """SelfDrivingQLearner over n BallGame envs on one GPU (same vector-step semantics as SelfDrivingQLearner)."""
     _prefix = "qlx_bg_learner"
     _n_actions = 5
