@@ -534,6 +534,53 @@ int32_t qlx_tf_bundle_entry(const qlx_tf_bundle* b, int32_t i, char* name, size_
                             int32_t* ndims, int64_t* nbytes);
 int32_t qlx_tf_bundle_read(const qlx_tf_bundle* b, const char* name, void* out, size_t cap);
 
+/* ---------------- Device-tensor env and replay calls (beyond the reference) ----------------
+ * The env, the replay and its sampler for an agent that lives in device memory (a PyTorch module, say): every `_dev` call
+ * below takes device pointers, enqueues on the object's stream and returns; none synchronises, allocates per call or
+ * copies to the host (the replay reserves 32 KB of scratch and its flag word at the first such call and keeps them).
+ * Argument errors (QLX_E_INVALID, the field named in qlx_last_error) are found on the host before anything is launched:
+ * a null handle or out, an unknown layout, batch 0 or > 4096, n_step 0 or > QLX_NSTEP_MAX, a state pointer that is not
+ * 16-byte aligned, batch > len for sampling.  An index >= len cannot be seen on the host: the kernels read nothing for it,
+ * write an all-zero sample (states 0, actions 0, returns 0, discounts 0, terminals 1, last_indices = the index, steps 0)
+ * and set a sticky flag in device memory that qlx_replay_sync reports as QLX_E_INVALID, once, and clears (the env's
+ * bad-action flag pattern, qlx_env_sync).
+ * State layouts, both u8 and dense, 28,224 bytes per state: */
+#define QLX_OBS_NHWC_SLOT 0  /* [n][84][84][4] (x, y, ring slot): the bytes qlx_env_obs / qlx_replay_get_many give */
+#define QLX_OBS_NCHW_TIME 1  /* [n][4][84][84] (age, x, y): channel 0 oldest ... 3 newest */
+/* NCHW_TIME is read off the ring: the env's channel c is ring slot (next_slot + c) & 3; for a replay transition of
+ * episode step k, channel c of s' is slot (k + c) & 3 and of s slot (k - 1 + c) & 3, that is the frame of episode step
+ * k - 3 + c (s') or k - 4 + c (s), and zeros for steps below 1. */
+
+/* the object's HIP stream (a hipStream_t) */
+int32_t qlx_env_stream(qlx_env* env, void** hip_stream_out);
+int32_t qlx_replay_stream(qlx_replay* rb, void** hip_stream_out);
+/* the replay gives up its own stream (after waiting for it) and runs on the env's from now on, so that pushes, which run
+ * on the env's stream, and batches are ordered without events; the env must outlive the replay.  Same device only. */
+int32_t qlx_replay_share_stream(qlx_replay* rb, qlx_env* env);
+/* waits for the replay's stream; QLX_E_INVALID once if a _dev call since the last sync met an index >= len */
+int32_t qlx_replay_sync(qlx_replay* rb);
+
+/* the current states of all envs in `layout` into d_out [n_envs] states */
+int32_t qlx_env_obs_dev(qlx_env* env, int32_t layout, uint8_t* d_out);
+/* qlx_env_reset with a device mask [n_envs] (or NULL: every env) */
+int32_t qlx_env_reset_dev(qlx_env* env, const uint8_t* d_mask_or_null);
+
+/* qlx_replay_sample_distinct into a device array [batch] */
+int32_t qlx_replay_sample_distinct_dev(qlx_replay* rb, uint64_t seed, uint32_t update_idx, uint32_t rank, uint32_t batch,
+                                       uint64_t* d_out_indices);
+
+typedef struct qlx_batch_dev {     /* device pointers [batch], any may be NULL */
+  uint8_t* s; uint8_t* s_next;     /* states in `layout`; s_next = s' of the n-step window's LAST transition */
+  uint8_t* actions; float* returns; float* discounts; uint8_t* terminals;
+  uint64_t* last_indices; uint32_t* steps;   /* qlx_replay_nstep's definitions, unchanged */
+} qlx_batch_dev;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_batch_dev) == 64, "qlx_batch_dev ABI size");
+#endif
+/* qlx_replay_get_many + qlx_replay_nstep for the logical indices in d_indices [batch] (device), on the replay's stream */
+int32_t qlx_replay_batch_dev(qlx_replay* rb, const uint64_t* d_indices, uint32_t batch, uint32_t n_step, float gamma,
+                             int32_t layout, const qlx_batch_dev* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ struct qlx_replay {
   qlx::DeviceBuffer<float> d_reward;
   qlx::DeviceBuffer<uint32_t> d_epstep;
   qlx::DeviceBuffer<uint64_t> d_idx;    // scratch for sampling [max_batch]
+  qlx::DeviceBuffer<uint64_t> d_win_last;   // [4096] qlx_replay_batch_dev: each window's last index (reserved at its first call, kept)
+  qlx::DeviceBuffer<uint32_t> d_flags;      // [4] sticky bad-index flag of the _dev calls (with d_win_last)
   uint64_t len() const { return total < cap ? total : cap; }
 };
 

@@ -132,6 +132,15 @@ class UpdateMetrics(C.Structure):
         ("td_hist", C.c_uint32 * 16)]
 
 
+class BatchDev(C.Structure):
+    """qlx_batch_dev: the device pointers qlx_replay_batch_dev writes (any may be None)"""
+    _fields_ = [(k, C.c_void_p) for k in ("s", "s_next", "actions", "returns", "discounts", "terminals", "last_indices",
+                                          "steps")]
+
+
+OBS_NHWC_SLOT = 0   # QLX_OBS_NHWC_SLOT: [n][84][84][4] (x, y, ring slot)
+OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 oldest
+
 _NP_OF_C = {C.c_uint64: "<u8", C.c_uint32: "<u4", C.c_float: "<f4"}
 # the same row as a numpy structured dtype (what metrics() returns an array of)
 UPDATE_METRICS_DTYPE = np.dtype([(k, _NP_OF_C[t]) if t in _NP_OF_C else (k, _NP_OF_C[t._type_], (t._length_,))
@@ -219,6 +228,12 @@ def lib():
         "qlx_replay_sample_distinct": ([vp, u64, u32, u32, u32, vp], i32),
         "qlx_replay_get_many": ([vp, vp, u32, vp, vp, vp, vp, vp], i32),
         "qlx_replay_nstep": ([vp, vp, u32, u32, f32, vp, vp, vp, vp, vp], i32),
+        # device-tensor calls (qlx_torch.py is their caller)
+        "qlx_env_stream": ([vp, C.POINTER(vp)], i32), "qlx_replay_stream": ([vp, C.POINTER(vp)], i32),
+        "qlx_replay_share_stream": ([vp, vp], i32), "qlx_replay_sync": ([vp], i32),
+        "qlx_env_obs_dev": ([vp, i32, vp], i32), "qlx_env_reset_dev": ([vp, vp], i32),
+        "qlx_replay_sample_distinct_dev": ([vp, u64, u32, u32, u32, vp], i32),
+        "qlx_replay_batch_dev": ([vp, vp, u32, u32, f32, i32, C.POINTER(BatchDev)], i32),
         "qlx_model_create": ([i32, u64, i32, C.POINTER(vp)], i32), "qlx_model_destroy": ([vp], i32),
         "qlx_model_num_vars": ([], i32), "qlx_model_var_size": ([i32], C.c_int64), "qlx_model_hparams": ([vp], i32),
         "qlx_bg_model_hparams": ([vp], i32),

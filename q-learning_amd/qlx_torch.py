@@ -1,0 +1,288 @@
+"""The batched Breakout env, the HBM replay and its sampler for an agent that lives in PyTorch device tensors.
+
+Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls",
+DESIGN.md §15): observations, steps, pushes and sampled n-step batches go from kernel to tensor without touching the
+host.  No call synchronises; order against torch's work is kept by stream waits (below).
+
+One HIP runtime per process.  torch's wheel carries a libamdhip64 of its own, libqlx.so asks for the system's by
+SONAME.  With torch loaded first the loader gives libqlx torch's copy, and a pointer or stream of one is the other's;
+with libqlx loaded first the process holds two runtimes, and is of no use here.  So this module imports torch, then
+loads libqlx, then checks /proc/self/maps: import qlx_torch before any other use of qlx.
+
+Streams.  Each object runs on its own HIP stream (a TorchReplay made from an env shares the env's).  Every call makes
+that stream wait for torch's current stream, enqueues, and makes the current stream wait for it, so tensors computed by
+torch just before a call are complete when the kernel reads them, and results can be used by torch at once: a call
+behaves like a torch op on the current stream.  Tensors handed in or out are record_stream'ed on that current stream,
+which the wait has put behind the kernel, and never on the object's own stream: torch's allocator records an event on
+every recorded stream when such a tensor is freed, which may be after close() has destroyed the object's stream.
+
+Dtypes: states, actions, terminals, dones and masks are uint8; rewards, returns and discounts float32; indices and
+last_indices are int64 holding the ABI's uint64 (a negative value reads as an index >= len), steps int32 (uint32).
+"""
+import collections
+import ctypes as C
+import os
+import weakref
+
+import torch
+
+import qlx
+from qlx import OBS_NCHW_TIME, OBS_NHWC_SLOT, QlError
+
+_L = qlx.lib()
+
+
+def mapped_hip_runtimes():
+    """paths of the libamdhip64 images mapped into this process"""
+    paths = set()
+    with open("/proc/self/maps") as f:
+        for line in f:
+            parts = line.split(None, 5)
+            if len(parts) == 6 and os.path.basename(parts[5].strip()).startswith("libamdhip64.so"):
+                paths.add(parts[5].strip())
+    return sorted(paths)
+
+
+def _check_one_runtime():
+    rts = mapped_hip_runtimes()
+    if len(rts) != 1:
+        raise QlError("qlx_torch must be imported before any other use of qlx: this process maps "
+                      f"{len(rts)} HIP runtimes ({', '.join(rts) or 'none'}), so torch and libqlx cannot share "
+                      "pointers and streams")
+
+
+_check_one_runtime()
+
+MAX_BATCH = 4096
+_LAYOUTS = {"nhwc_slot": OBS_NHWC_SLOT, "nchw_time": OBS_NCHW_TIME}
+_STATE_SHAPE = {OBS_NHWC_SLOT: (qlx.FRAME, qlx.FRAME, qlx.SLOTS), OBS_NCHW_TIME: (qlx.SLOTS, qlx.FRAME, qlx.FRAME)}
+
+_FIELDS = ("s", "s_next", "actions", "returns", "discounts", "terminals", "last_indices", "steps")   # qlx_batch_dev
+_BATCH_DTYPES = dict(actions=torch.uint8, returns=torch.float32, discounts=torch.float32, terminals=torch.uint8,
+                     last_indices=torch.int64, steps=torch.int32)
+
+
+class Batch(collections.namedtuple("Batch", "s s_next actions returns discounts terminals indices steps")):
+    """(s, s_next, actions, returns, discounts, terminals, indices, steps); `indices` are the transitions asked for or
+    drawn, and the attribute `last_indices` holds each n-step window's last transition (the one s_next belongs to)"""
+    last_indices = None
+
+
+def _layout(layout):
+    try:
+        return _LAYOUTS[layout]
+    except (KeyError, TypeError):
+        raise ValueError(f"layout must be 'nchw_time' or 'nhwc_slot', not {layout!r}") from None
+
+
+def _device(device):
+    d = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+    if d.type != "cuda":
+        raise ValueError(f"device must be a CUDA (HIP) device, not {d}")
+    return torch.device("cuda", torch.cuda.current_device() if d.index is None else d.index)
+
+
+def _arg(name, t, device, dtype, shape):
+    """`t` as the kernels need it, or ValueError before anything is launched"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if not t.is_cuda or t.device != device:
+        raise ValueError(f"{name} must be on {device}, not {t.device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name} must be 16-byte aligned")
+    return t
+
+
+class _Streamed:
+    """an object of libqlx with a HIP stream of its own, ordered against torch's current stream call by call"""
+
+    def _wrap_stream(self, getter):
+        p = C.c_void_p()
+        qlx._check(getter(self.h, C.byref(p)))
+        self.stream = torch.cuda.ExternalStream(p.value or 0, device=self.device)
+
+    class _Ordered:
+        def __init__(self, obj, tensors):
+            self.obj, self.tensors = obj, tensors
+
+        def __enter__(self):
+            o = self.obj
+            if o.h is None:
+                raise QlError("the object is closed")
+            self.current = torch.cuda.current_stream(o.device)
+            o.stream.wait_stream(self.current)
+
+        def __exit__(self, *exc):
+            self.current.wait_stream(self.obj.stream)
+            for t in self.tensors:
+                if t is not None:
+                    t.record_stream(self.current)   # a no-op for a tensor allocated on it, the usual case
+            return False
+
+    def _ordered(self, *tensors):
+        return self._Ordered(self, tensors)
+
+
+class TorchEnv(_Streamed):
+    """n batched Breakout envs stepped with device tensors"""
+
+    ACTION_SPACE = qlx.ACTION_SPACE
+
+    def __init__(self, n_envs, seed=0x51A5EED, device="cuda:0"):
+        self.device = _device(device)
+        self._env = qlx.BreakoutEnvironment(n_envs, seed, self.device.index)
+        self.h = self._env.h
+        self.n = self._env.n
+        self._wrap_stream(_L.qlx_env_stream)
+        self._sharing = weakref.WeakSet()   # replays that run on this env's stream: closed before it
+
+    def close(self):
+        for rb in list(getattr(self, "_sharing", ())):
+            rb.close()
+        env = getattr(self, "_env", None)
+        if env is not None:
+            env.close()
+        self.h = None
+
+    def obs(self, layout="nchw_time", out=None):
+        """current states: uint8 [n, 4, 84, 84] (channel 0 oldest) or, 'nhwc_slot', [n, 84, 84, 4] (x, y, ring slot)"""
+        lay = _layout(layout)
+        shape = (self.n,) + _STATE_SHAPE[lay]
+        out = torch.empty(shape, dtype=torch.uint8, device=self.device) if out is None else _arg("out", out, self.device, torch.uint8, shape)
+        with self._ordered(out):
+            qlx._check(_L.qlx_env_obs_dev(self.h, lay, out.data_ptr()))
+        return out
+
+    def step(self, actions):
+        """one step of every env with uint8 actions [n] (values >= 3: action 0 and an error at sync()); (rewards, dones)"""
+        a = _arg("actions", actions, self.device, torch.uint8, (self.n,))
+        rewards = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        dones = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+        with self._ordered(a, rewards, dones):
+            qlx._check(_L.qlx_env_step_dev(self.h, a.data_ptr(), rewards.data_ptr(), dones.data_ptr()))
+        return rewards, dones
+
+    def reset(self, mask=None):
+        """reset every env, or those with mask[i] != 0 (uint8 device tensor [n])"""
+        m = None if mask is None else _arg("mask", mask, self.device, torch.uint8, (self.n,))
+        with self._ordered(m):
+            qlx._check(_L.qlx_env_reset_dev(self.h, None if m is None else m.data_ptr()))
+
+    def sync(self):
+        """wait for the env's stream; QlError if a step met an action >= 3"""
+        qlx._check(_L.qlx_env_sync(self.h))
+
+    def mechanics(self):
+        return self._env.mechanics()
+
+    def hashes(self):
+        return self._env.hashes()
+
+
+class TorchReplay(_Streamed):
+    """the HBM replay ring read into device tensors.  TorchReplay(capacity, env) makes a replay on the env's stream;
+    TorchReplay(handle=h, n_envs=n, device=d) wraps a handle someone else owns (a learner's replay) on its own stream."""
+
+    def __init__(self, capacity=0, env=None, handle=None, n_envs=None, device=None):
+        if handle is None:
+            if env is None:
+                raise ValueError("TorchReplay needs an env (or a handle)")
+            self.device = env.device
+            self.n = env.n
+            self._rb = qlx.ReplayBuffer(capacity, env.n, self.device.index)
+            self._env = env   # the stream is the env's: keep it alive
+            self.h = self._rb.h
+            qlx._check(_L.qlx_replay_share_stream(self.h, env.h))
+            env._sharing.add(self)
+        else:
+            if n_envs is None:
+                raise ValueError("a wrapped replay handle needs n_envs")
+            self.device = _device("cuda:0" if device is None else device)
+            self.n = n_envs
+            self._rb = qlx.ReplayBuffer(0, 0, handle=handle)
+            self.h = handle
+        self._wrap_stream(_L.qlx_replay_stream)
+
+    def close(self):
+        rb = getattr(self, "_rb", None)
+        if rb is not None:
+            rb.close()
+        self.h = None
+
+    def __len__(self):
+        return len(self._rb)
+
+    def add(self, env, actions, rewards, dones):
+        """the transition every env just made: the actions given to env.step and what it returned"""
+        if env.n != self.n or env.device != self.device:
+            raise ValueError("env does not match the replay (n_envs, device)")
+        a = _arg("actions", actions, self.device, torch.uint8, (self.n,))
+        r = _arg("rewards", rewards, self.device, torch.float32, (self.n,))
+        d = _arg("dones", dones, self.device, torch.uint8, (self.n,))
+        # the push runs on the env's stream (it reads the env's ring); with a shared stream the two are one
+        with env._ordered(a, r, d), self._ordered(a, r, d):
+            qlx._check(_L.qlx_replay_push_dev(self.h, env.h, a.data_ptr(), r.data_ptr(), d.data_ptr()))
+
+    def sample_indices(self, batch, seed, update_idx, rank=0):
+        """`batch` distinct logical indices < len from stream (seed, update_idx, rank), int64 [batch]"""
+        if not 0 < batch <= MAX_BATCH:
+            raise ValueError(f"batch must be in 1..{MAX_BATCH}")
+        if batch > len(self):
+            raise ValueError(f"batch {batch} > len {len(self)}")
+        idx = torch.empty(batch, dtype=torch.int64, device=self.device)
+        with self._ordered(idx):
+            qlx._check(_L.qlx_replay_sample_distinct_dev(self.h, seed, update_idx, rank, batch, idx.data_ptr()))
+        return idx
+
+    def batch(self, indices, n_step=1, gamma=0.99, layout="nchw_time", out=None, fields=None):
+        """The transitions at `indices` (int64 [B]) as a Batch: s, s_next (the state after the n-step window's last
+        transition), actions, returns = sum_{j<m} gamma^j r_j, discounts = gamma^m, terminals, indices (as given) and
+        steps = m, with the windows' last indices as its attribute last_indices.  `fields`: the qlx_batch_dev names to
+        produce (default all; the rest are None and cost nothing); `out`: a dict of tensors to write into, by those
+        names.  An index >= len gives an all-zero sample and an error at sync()."""
+        lay = _layout(layout)
+        if not isinstance(indices, torch.Tensor) or indices.dim() != 1:
+            raise ValueError("indices must be a 1-d tensor")
+        B = indices.shape[0]
+        if not 0 < B <= MAX_BATCH:
+            raise ValueError(f"batch must be in 1..{MAX_BATCH}")
+        if not 1 <= n_step <= 32:
+            raise ValueError("n_step must be in 1..32")
+        idx = _arg("indices", indices, self.device, torch.int64, (B,))
+        out = dict(out or {})
+        names = _FIELDS if fields is None else tuple(fields)
+        unknown = (set(names) | set(out)) - set(_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown batch fields {sorted(unknown)}")
+        res = {}
+        for k in _FIELDS:
+            if k in ("s", "s_next"):
+                dtype, shape = torch.uint8, (B,) + _STATE_SHAPE[lay]
+            else:
+                dtype, shape = _BATCH_DTYPES[k], (B,)
+            if k in out:
+                res[k] = _arg(f"out[{k!r}]", out[k], self.device, dtype, shape)
+            elif k in names:
+                res[k] = torch.empty(shape, dtype=dtype, device=self.device)
+            else:
+                res[k] = None
+        o = qlx.BatchDev(**{k: (None if t is None else t.data_ptr()) for k, t in res.items()})
+        with self._ordered(idx, *res.values()):
+            qlx._check(_L.qlx_replay_batch_dev(self.h, idx.data_ptr(), B, n_step, gamma, lay, C.byref(o)))
+        b = Batch(res["s"], res["s_next"], res["actions"], res["returns"], res["discounts"], res["terminals"], idx, res["steps"])
+        b.last_indices = res["last_indices"]
+        return b
+
+    def sample(self, batch, seed, update_idx, n_step=1, gamma=0.99, layout="nchw_time", rank=0, out=None):
+        """sample_indices + batch: `batch` distinct transitions drawn from stream (seed, update_idx, rank)"""
+        return self.batch(self.sample_indices(batch, seed, update_idx, rank), n_step, gamma, layout, out)
+
+    def sync(self):
+        """wait for the replay's stream; QlError, once, if a call since the last sync met an index >= len"""
+        qlx._check(_L.qlx_replay_sync(self.h))
