@@ -17,7 +17,7 @@ LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
         $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o \
         $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o $(OUT)/obj/learner_core.o $(OUT)/obj/learner_snapshot.o \
-        $(OUT)/obj/metrics.o $(OUT)/obj/batch_dev.o
+        $(OUT)/obj/metrics.o $(OUT)/obj/batch_dev.o $(OUT)/obj/model_dev.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
 
@@ -39,6 +39,10 @@ $(OUT)/obj/replay.o: $(SRC)/replay.hip $(HDRS) | $(OUT)/obj
 
 # device-tensor env / replay calls: its window arithmetic is replay_dev.h's, under replay.o's flags
 $(OUT)/obj/batch_dev.o: $(SRC)/batch_dev.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# device-tensor Q-net calls: byte-moving and pointer-table kernels only, model.o's flags
+$(OUT)/obj/model_dev.o: $(SRC)/model_dev.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # (bf16 Q-net on the default scheduler since round 5: 789K -> 797K env-steps/s against max-ILP, the slab reduction

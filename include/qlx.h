@@ -581,6 +581,59 @@ static_assert(sizeof(qlx_batch_dev) == 64, "qlx_batch_dev ABI size");
 int32_t qlx_replay_batch_dev(qlx_replay* rb, const uint64_t* d_indices, uint32_t batch, uint32_t n_step, float gamma,
                              int32_t layout, const qlx_batch_dev* out);
 
+/* ---------------- Q-network on device tensors (beyond the reference) ----------------
+ * The Q-net's forward and its whole update (forward, Huber, backward, clip_by_norm, Adam) for an agent that computes its
+ * own targets in device memory: states are read where they lie (dense device states, the replay ring through logical
+ * indices, or an env's current ring), actions, targets, per-sample weights and all results are device arrays.  The
+ * conventions are those of the section above: arguments are checked on the host, then everything is enqueued on the
+ * model's stream; no `_dev` call synchronises, allocates or copies to the host.  qlx_model_reserve is the one call that
+ * sizes the workspace: a `_dev` call with n above the reserved size (or before any reserve) fails with QLX_E_STATE and
+ * launches nothing.  (The backward's gradient buffers are the backend's own and grow, once, at the first training batch
+ * larger than any before, as they do for qlx_model_train and the learner.)
+ * Host checks (QLX_E_INVALID, the field named in qlx_last_error), made before any handle is read: a null model, src or
+ * required pointer; not exactly one state source; indices without replay or the reverse; an unknown layout; which not
+ * 0 / 1; obs not 16-byte aligned; n 0 or > 8192; batch 0 or > 4096; all outputs of qlx_model_q_dev null.  After the
+ * handle is read: the reserve check (QLX_E_STATE), an env or replay on another device, an env whose count is not n.
+ * Data the host cannot see: an index >= len reads nothing and is the all-zero state; an action >= 3 trains as action 0
+ * (the kernels read a checked copy); either sets a sticky flag that qlx_model_sync reports as QLX_E_INVALID, once. */
+typedef struct qlx_states_dev {          /* exactly one source: obs, or replay + indices, or env */
+  const uint8_t*  obs;       /* dense device states [n] in `layout`, 16-byte aligned */
+  qlx_replay*     replay;    /* with indices: the transitions at these logical indices ... */
+  const uint64_t* indices;   /* ... device array [n] */
+  qlx_env*        env;       /* the env's current states; n must equal its env count */
+  int32_t         layout;    /* QLX_OBS_NHWC_SLOT / QLX_OBS_NCHW_TIME: the channel order the net sees, for every source */
+  int32_t         which;     /* replay source: 0 = s, 1 = s' of that transition (pass a batch's last_indices for n-step) */
+} qlx_states_dev;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_states_dev) == 40, "qlx_states_dev ABI size");
+#endif
+/* `layout` is the network's input-channel convention, not only the byte order of `obs`: NHWC_SLOT feeds ring slot j as
+ * channel j (the reference's tensor view: what qlx_model_predict, qlx_model_train and the learner feed), NCHW_TIME feeds
+ * the oldest frame as channel 0.  For the env and replay sources it only permutes the four frame pointers by the rules
+ * above (env: slot (next_slot + c) & 3; replay: (k + c) & 3 for s', (k - 1 + c) & 3 for s; a frame the episode does not
+ * have is a zero frame); no state byte moves.  Use a model with one convention throughout: the two train different nets. */
+
+/* the model's HIP stream (a hipStream_t) */
+int32_t qlx_model_stream(qlx_model* m, void** hip_stream_out);
+/* the model gives up its own stream (after waiting for it) and runs on the env's from now on, as qlx_replay_share_stream;
+ * the env must outlive the model.  Same device only. */
+int32_t qlx_model_share_stream(qlx_model* m, qlx_env* env);
+/* workspace for _dev calls of up to max_n states (1..8192), the flag word and the argument scratch; synchronises, may
+ * allocate.  A smaller max_n than an earlier one changes nothing. */
+int32_t qlx_model_reserve(qlx_model* m, uint32_t max_n);
+/* Q(s) of n states: d_q [n][3], d_actions [n] = first argmax, d_max_q [n] = max_a Q; any may be NULL, not all three */
+int32_t qlx_model_q_dev(qlx_model* m, const qlx_states_dev* src, uint32_t n, float* d_q, uint8_t* d_actions,
+                        float* d_max_q);
+/* one update as qlx_model_train runs it (forward, Huber(1) mean of weights * h, backward, clip_by_norm(1), Adam,
+ * iterations + 1) on `batch` (1..4096) states with device actions [batch], targets d_y [batch] and optional per-sample
+ * loss weights; d_loss (one float) and d_td_abs [batch] = |q_a - y| are optional outputs */
+int32_t qlx_model_train_dev(qlx_model* m, const qlx_states_dev* src, const uint8_t* d_actions, const float* d_y,
+                            const float* d_weights_or_null, uint32_t batch, float* d_loss_or_null, float* d_td_abs_or_null);
+/* qlx_model_copy_weights without a host synchronisation: the copy runs on dst's stream behind what src's stream holds
+ * now, and src's stream waits for it (nothing of either when they share a stream) */
+int32_t qlx_model_copy_weights_dev(qlx_model* dst, qlx_model* src);
+/* qlx_model_sync (above) also reports, once, a flag set by a _dev call since the last sync */
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,7 @@ int32_t qlx_model_destroy(qlx_model* m) {
     (void)hipStreamSynchronize(m->stream);
     m->f32 ? f32_destroy(m) : bf16_destroy(m);
     if (m->own_stream) (void)hipStreamDestroy(m->stream);
+    if (m->dev_event) (void)hipEventDestroy(m->dev_event);
     delete m;
   });
 }
@@ -399,6 +400,15 @@ int32_t qlx_model_sync(qlx_model* m) {
   return guard([&] {
     QLX_CHECK(m, QLX_E_INVALID, "null model");
     QLX_HIP(hipStreamSynchronize(m->stream));
+    if (!m->d_dev_flag) return;   // only the _dev calls (model_dev.hip) set the flag, and they need a reserve
+    QLX_HIP(hipSetDevice(m->device));
+    uint32_t flag = 0;
+    QLX_HIP(hipMemcpy(&flag, m->d_dev_flag, 4, hipMemcpyDeviceToHost));
+    if (flag) QLX_HIP(hipMemset(m->d_dev_flag, 0, 4));
+    QLX_CHECK(flag == 0, QLX_E_INVALID,
+              flag == 1 ? "replay index out of range (>= len) in a device call"
+                        : flag == 2 ? "action out of range (>= 3) in a device call"
+                                    : "replay index out of range (>= len) and action out of range (>= 3) in device calls");
   });
 }
 

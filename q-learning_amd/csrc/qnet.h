@@ -65,6 +65,14 @@ struct qlx_model {
   int last_batch = 0;
   qlx::CommonWs w;
   qlx::Profiler* prof = nullptr;   // set by the learner while profiling
+  // the _dev calls (model_dev.hip), all set by qlx_model_reserve: the largest n they may run, the sticky flag word
+  // (bit 0 an index >= len, bit 1 an action >= 3), the checked copy of the caller's actions and the max-Q head's zero
+  // rewards / dones; the event orders qlx_model_copy_weights_dev across two streams (created at its first use)
+  uint32_t dev_reserved = 0;
+  qlx::DeviceBuffer<uint32_t> d_dev_flag;
+  qlx::DeviceBuffer<uint8_t> d_dev_act;
+  qlx::DeviceBuffer<float> d_dev_zero;
+  hipEvent_t dev_event = nullptr;
   // the backend's own state (operand copies, activations, norm partials, update-tail flags): exactly one is set, and
   // only that backend's file sees inside it
   qlx::Bf16Net* bf16 = nullptr;

@@ -138,6 +138,13 @@ class BatchDev(C.Structure):
                                           "steps")]
 
 
+class StatesDev(C.Structure):
+    """qlx_states_dev: the one state source of a qlx_model_*_dev call (obs, or replay + indices, or env), the channel
+    order the net sees (OBS_*) and, for the replay source, which state of the transition (0 = s, 1 = s')"""
+    _fields_ = [("obs", C.c_void_p), ("replay", C.c_void_p), ("indices", C.c_void_p), ("env", C.c_void_p),
+                ("layout", C.c_int32), ("which", C.c_int32)]
+
+
 OBS_NHWC_SLOT = 0   # QLX_OBS_NHWC_SLOT: [n][84][84][4] (x, y, ring slot)
 OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 oldest
 
@@ -245,6 +252,12 @@ def lib():
         "qlx_model_last_activation": ([vp, i32, vp], i32),
         "qlx_model_write_checkpoint": ([vp, C.c_char_p], i32), "qlx_model_read_checkpoint": ([vp, C.c_char_p], i32),
         "qlx_model_sync": ([vp], i32),
+        # the Q-net on device tensors (qlx_torch.TorchQNet is their caller)
+        "qlx_model_stream": ([vp, C.POINTER(vp)], i32), "qlx_model_share_stream": ([vp, vp], i32),
+        "qlx_model_reserve": ([vp, u32], i32),
+        "qlx_model_q_dev": ([vp, C.POINTER(StatesDev), u32, vp, vp, vp], i32),
+        "qlx_model_train_dev": ([vp, C.POINTER(StatesDev), vp, vp, vp, u32, vp, vp], i32),
+        "qlx_model_copy_weights_dev": ([vp, vp], i32),
         "qlx_params_default": ([vp], None),
         "qlx_learner_create": ([C.POINTER(Params), i32, C.POINTER(vp)], i32), "qlx_learner_destroy": ([vp], i32),
         "qlx_learner_vector_step": ([vp], i32), "qlx_learner_run": ([vp, u64], i32), "qlx_learner_sync": ([vp], i32),

@@ -1,8 +1,9 @@
-"""The batched Breakout env, the HBM replay and its sampler for an agent that lives in PyTorch device tensors.
+"""The batched Breakout env, the HBM replay, its sampler and the Q-net for an agent that lives in PyTorch device tensors.
 
-Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls",
-DESIGN.md §15): observations, steps, pushes and sampled n-step batches go from kernel to tensor without touching the
-host.  No call synchronises; order against torch's work is kept by stream waits (below).
+Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls" and
+"Q-network on device tensors"): observations, steps, pushes, sampled n-step batches, Q-values and
+whole updates go from kernel to tensor without touching the host.  No call synchronises; order against torch's work is
+kept by stream waits (below).
 
 One HIP runtime per process.  torch's wheel carries a libamdhip64 of its own, libqlx.so asks for the system's by
 SONAME.  With torch loaded first the loader gives libqlx torch's copy, and a pointer or stream of one is the other's;
@@ -20,6 +21,7 @@ Dtypes: states, actions, terminals, dones and masks are uint8; rewards, returns 
 last_indices are int64 holding the ABI's uint64 (a negative value reads as an index >= len), steps int32 (uint32).
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -286,3 +288,147 @@ class TorchReplay(_Streamed):
     def sync(self):
         """wait for the replay's stream; QlError, once, if a call since the last sync met an index >= len"""
         qlx._check(_L.qlx_replay_sync(self.h))
+
+
+MAX_STATES = 8192
+_ARCHS = {"f32": qlx.PREC_F32, "bf16": qlx.PREC_BF16}
+_WHICH = {"s": 0, "s_next": 1}
+_WANT = ("q", "actions", "max_q")
+
+
+class TorchQNet(_Streamed):
+    """The Nature-DQN Q-net (fp32 or bf16 kernels) on device tensors (include/qlx.h "Q-network on device tensors",
+    DESIGN.md §16): Q-values of, and one whole update (forward, Huber, backward, clip, Adam) on, states that are dense
+    tensors, transitions of a TorchReplay given by their indices, or a TorchEnv's current states, with targets computed in
+    torch.  TorchQNet(env=env) runs on the env's stream and is closed with it; otherwise it has a stream of its own.
+    TorchQNet(handle=h, device=d) wraps a model someone else owns (a learner's).  `reserve`: the largest n of any call.
+
+    `layout` names the channel order the net sees, for every source: 'nchw_time' feeds the oldest frame as channel 0,
+    'nhwc_slot' ring slot j as channel j (what the learner and DeepQLearningModel feed).  Use one throughout."""
+
+    def __init__(self, arch="f32", seed=2, device="cuda:0", env=None, reserve=MAX_STATES, handle=None):
+        if arch not in _ARCHS:
+            raise ValueError(f"arch must be 'f32' or 'bf16', not {arch!r}")
+        if not 0 < reserve <= MAX_STATES:
+            raise ValueError(f"reserve must be in 1..{MAX_STATES}")
+        self.device = env.device if env is not None else _device(device)
+        self.arch = arch
+        if handle is None:
+            self._m = qlx.DeepQLearningModel(seed, self.device.index, precision=_ARCHS[arch])
+        else:
+            self._m = qlx.DeepQLearningModel(handle=handle)
+        self.h = self._m.h
+        self._env = env   # with env=: the stream is the env's, keep it alive
+        if env is not None:
+            qlx._check(_L.qlx_model_share_stream(self.h, env.h))
+            env._sharing.add(self)
+        qlx._check(_L.qlx_model_reserve(self.h, reserve))
+        self.reserved = reserve
+        self._wrap_stream(_L.qlx_model_stream)
+
+    def close(self):
+        m = getattr(self, "_m", None)
+        if m is not None:
+            m.close()
+        self.h = None
+
+    @property
+    def model(self):
+        """the qlx.DeepQLearningModel underneath (host calls: get / set, checkpoints, iterations)"""
+        return self._m
+
+    def _source(self, obs, env, replay, indices, which, layout):
+        """(StatesDev, n, the tensors it reads) or ValueError before anything is launched"""
+        lay = _layout(layout)
+        if which not in _WHICH:
+            raise ValueError(f"which must be 's' or 's_next', not {which!r}")
+        if (obs is not None) + (env is not None) + (replay is not None or indices is not None) != 1:
+            raise ValueError("exactly one state source: obs, env or replay + indices")
+        s = qlx.StatesDev(layout=lay, which=_WHICH[which])
+        if obs is not None:
+            if not isinstance(obs, torch.Tensor) or obs.dim() != 4:
+                raise ValueError("obs must be a 4-d tensor")
+            n = obs.shape[0]
+            t = _arg("obs", obs, self.device, torch.uint8, (n,) + _STATE_SHAPE[lay])
+            s.obs = t.data_ptr()
+            return s, n, (t,)
+        if env is not None:
+            if env.device != self.device:
+                raise ValueError(f"env must be on {self.device}")
+            s.env = env.h
+            return s, env.n, ()
+        if replay is None or indices is None:
+            raise ValueError("replay and indices go together")
+        if replay.device != self.device:
+            raise ValueError(f"replay must be on {self.device}")
+        if not isinstance(indices, torch.Tensor) or indices.dim() != 1:
+            raise ValueError("indices must be a 1-d tensor")
+        n = indices.shape[0]
+        t = _arg("indices", indices, self.device, torch.int64, (n,))
+        s.replay, s.indices = replay.h, t.data_ptr()
+        return s, n, (t,)
+
+    def _others(self, env, replay):
+        """the objects whose streams a call reads from: ordered like this one (a shared stream is entered once)"""
+        seen, out = {self.stream.cuda_stream}, []
+        for o in (env, replay):
+            if o is not None and o.stream.cuda_stream not in seen:
+                seen.add(o.stream.cuda_stream)
+                out.append(o)
+        return out
+
+    def _run(self, env, replay, tensors, call):
+        with contextlib.ExitStack() as stack:
+            for o in self._others(env, replay):
+                stack.enter_context(o._ordered())
+            stack.enter_context(self._ordered(*tensors))
+            qlx._check(call())
+
+    def q(self, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time", want=_WANT, out=None):
+        """Q(s) of n states: the tensors named in `want`, in that order (one name: that tensor alone) - 'q' float32
+        [n, 3], 'actions' uint8 [n] (first argmax), 'max_q' float32 [n].  `out`: a dict of tensors to write into, by those
+        names.  A replay index >= len gives the Q of the all-zero state and an error at sync()."""
+        s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < n <= self.reserved:
+            raise ValueError(f"n must be in 1..{self.reserved} (the reserve)")
+        names = (want,) if isinstance(want, str) else tuple(want)
+        out = dict(out or {})
+        if not names or set(names) - set(_WANT) or set(out) - set(names):
+            raise ValueError(f"want must name some of {_WANT}, and out only what want names")
+        spec = dict(q=(torch.float32, (n, 3)), actions=(torch.uint8, (n,)), max_q=(torch.float32, (n,)))
+        res = {k: (_arg(f"out[{k!r}]", out[k], self.device, *spec[k]) if k in out else
+                   torch.empty(spec[k][1], dtype=spec[k][0], device=self.device)) for k in names}
+        ptr = [res[k].data_ptr() if k in res else None for k in _WANT]
+        self._run(env, replay, ins + tuple(res.values()), lambda: _L.qlx_model_q_dev(self.h, C.byref(s), n, *ptr))
+        return res[want] if isinstance(want, str) else tuple(res[k] for k in names)
+
+    def train(self, actions, y, weights=None, *, obs=None, env=None, replay=None, indices=None, which="s",
+              layout="nchw_time", want_td_abs=False):
+        """One update on B states with uint8 actions [B], float32 targets y [B] and optional float32 per-sample loss
+        weights [B]: (loss, td_abs), loss a 0-d float32 device tensor, td_abs = |q_a - y| float32 [B] or None.  An action
+        >= 3 trains as action 0 and gives an error at sync()."""
+        s, B, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < B <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"batch must be in 1..{min(MAX_BATCH, self.reserved)}")
+        a = _arg("actions", actions, self.device, torch.uint8, (B,))
+        t = _arg("y", y, self.device, torch.float32, (B,))
+        w = None if weights is None else _arg("weights", weights, self.device, torch.float32, (B,))
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        td = torch.empty(B, dtype=torch.float32, device=self.device) if want_td_abs else None
+        self._run(env, replay, ins + (a, t, w, loss, td),
+                  lambda: _L.qlx_model_train_dev(self.h, C.byref(s), a.data_ptr(), t.data_ptr(), None if w is None else w.data_ptr(),
+                                                 B, loss.data_ptr(), None if td is None else td.data_ptr()))
+        return loss, td
+
+    def copy_weights_from(self, other):
+        """the weights of `other` (a TorchQNet), as a target-network sync: no host synchronisation"""
+        if not isinstance(other, TorchQNet) or other.device != self.device:
+            raise ValueError(f"other must be a TorchQNet on {self.device}")
+        if other.h is None:
+            raise QlError("the object is closed")
+        with self._ordered():
+            qlx._check(_L.qlx_model_copy_weights_dev(self.h, other.h))
+
+    def sync(self):
+        """wait for the model's stream; QlError, once, if a call since the last sync met an index >= len or an action >= 3"""
+        qlx._check(_L.qlx_model_sync(self.h))

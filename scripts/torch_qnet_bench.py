@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Timings of the Q-net's device-tensor calls (qlx_torch.TorchQNet) beside the paths they replace.
+
+  python scripts/torch_qnet_bench.py act    [--envs 8192] [--arch f32|bf16]   q(env=) | q(env.obs()) | host predict
+  python scripts/torch_qnet_bench.py update [--batch 1024] [--arch f32|bf16]  train(replay=) | batch + train(obs=) | host train
+  python scripts/torch_qnet_bench.py pack   [--n 1024]     the two staging kernels, to be run under a kernel trace:
+      rocprofv3 --kernel-trace --stats -d DIR -- python scripts/torch_qnet_bench.py pack --n 8192
+      (k_pack_states: the dense source of q(); k_pack_obs: the host call qlx_model_predict on the same states)
+
+Device paths are timed with events on torch's current stream around one call (every call makes that stream wait for the
+model's), host paths with a wall clock around the synchronising call; each figure is the median [min..max] of --reps
+calls after --warmup calls."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "q-learning_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import qlx_torch as QT  # noqa: E402  (before any other use of qlx)
+
+DEV = torch.device("cuda:0")
+
+
+def fmt(us):
+    return f"{statistics.median(us):9.1f} us [{min(us):.1f}..{max(us):.1f}]"
+
+
+def time_device(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return out
+
+
+def time_host(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t) * 1e6)
+    return out
+
+
+def played_env(n, steps, rb=None):
+    env = QT.TorchEnv(n, seed=1, device=DEV)
+    rb = QT.TorchReplay(rb, env) if rb else None
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for _ in range(steps):
+        a = torch.randint(0, 3, (n,), device=DEV, dtype=torch.uint8, generator=g)
+        r, d = env.step(a)
+        if rb is not None:
+            rb.add(env, a, r, d)
+        env.reset(d)
+    env.sync()
+    return env, rb
+
+
+def act(args):
+    env, _ = played_env(args.envs, 12)
+    net = QT.TorchQNet(args.arch, env=env, reserve=args.envs)
+    lay = "nhwc_slot"
+    rows = [("q(env=env)", time_device(lambda: net.q(env=env, layout=lay, want="actions"), args.reps, args.warmup)),
+            ("q(env.obs())", time_device(lambda: net.q(env.obs(lay), layout=lay, want="actions"), args.reps, args.warmup)),
+            ("host predict(env.state())", time_host(lambda: net.model.q_values(env._env.state()), max(3, args.reps // 4), 1))]
+    print(f"acting, {args.envs} envs, {args.arch}:")
+    for name, us in rows:
+        print(f"  {name:28s} {fmt(us)}")
+    net.sync()
+    env.close()
+
+
+def update(args):
+    B = args.batch
+    env, rb = played_env(256, 40, rb=20_000)
+    net = QT.TorchQNet(args.arch, env=env, reserve=B)
+    lay = "nhwc_slot"
+    idx = rb.sample_indices(B, seed=3, update_idx=0)
+    b = rb.batch(idx, layout=lay, fields=("s", "actions"))
+    y = torch.randn(B, device=DEV)
+    s_host, a_host, y_host = b.s.cpu().numpy(), b.actions.cpu().numpy(), y.cpu().numpy()
+
+    def by_obs():
+        s = rb.batch(idx, layout=lay, fields=("s",)).s
+        net.train(b.actions, y, obs=s, layout=lay)
+
+    rows = [("train(replay=, indices=)", time_device(lambda: net.train(b.actions, y, replay=rb, indices=idx, layout=lay), args.reps, args.warmup)),
+            ("rb.batch + train(obs=)", time_device(by_obs, args.reps, args.warmup)),
+            ("host qlx_model_train", time_host(lambda: net.model.train(s_host, a_host, y_host), max(3, args.reps // 4), 1))]
+    print(f"update, B = {B}, {args.arch}:")
+    for name, us in rows:
+        print(f"  {name:28s} {fmt(us)}")
+    net.sync()
+    env.close()
+
+
+def pack(args):
+    n = args.n
+    net = QT.TorchQNet("bf16", reserve=n)
+    x = torch.randint(0, 256, (n, 84, 84, 4), device=DEV, dtype=torch.uint8)
+    x_host = x.cpu().numpy()
+    for _ in range(args.reps):
+        net.q(x, layout="nhwc_slot", want="actions")                       # k_pack_states<NHWC_SLOT>
+        net.q(x.view(n, 4, 84, 84), layout="nchw_time", want="actions")     # k_pack_states<NCHW_TIME> (any bytes do)
+    net.sync()
+    for _ in range(max(2, args.reps // 4)):
+        net.model.q_values(x_host)                                         # k_pack_obs
+    print(f"pack: n = {n}, {2 * 28224 * n} bytes read + written per launch; kernel times are the trace's")
+    net.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=("act", "update", "pack"))
+    ap.add_argument("--envs", type=int, default=8192)
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--arch", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    {"act": act, "update": update, "pack": pack}[args.what](args)
+
+
+if __name__ == "__main__":
+    np.random.seed(0)
+    main()
