@@ -634,6 +634,39 @@ int32_t qlx_model_train_dev(qlx_model* m, const qlx_states_dev* src, const uint8
 int32_t qlx_model_copy_weights_dev(qlx_model* dst, qlx_model* src);
 /* qlx_model_sync (above) also reports, once, a flag set by a _dev call since the last sync */
 
+/* ---------------- Prioritized replay on device tensors (beyond the reference) ----------------
+ * The learner's proportional prioritized replay (the sum tree above: same heap, same draws, same weights, same priority
+ * write) kept inside a qlx_replay and driven one batch per call from device memory.  Conventions of "Device-tensor env and
+ * replay calls": arguments are checked on the host before anything is launched, the `_dev` calls enqueue on the replay's
+ * stream and neither synchronise, allocate nor copy to the host.
+ * Semantics: one fp32 heap of 2L nodes (L = next power of two >= capacity), leaf L + slot = priority^alpha of the PHYSICAL
+ * ring slot, node i = t[2i] + t[2i + 1].  A pushed transition enters at per_max (1 at first, then the largest priority
+ * ever written).  Draw b of a batch: x = (T / B)(b + r_b), r_b from stream (seed, update_idx, rank, purpose 7, word b),
+ * descending left iff x < left or right == 0; weight (len leaf / T)^-beta divided by the batch maximum; the result is the
+ * logical index (slot + cap - start) % cap, start = (total - len) % cap.  Draws are with replacement: batch > len is fine.
+ * Host checks (QLX_E_INVALID, the field named): a null handle or required pointer, batch 0 or > 4096, n > 4096, beta or
+ * alpha not finite or < 0, eps not finite or <= 0, len == 0 for a draw.  After them: priorities not enabled, QLX_E_STATE.
+ * Data the host cannot see: an index >= len, or a td_abs that is NaN, infinite or negative, writes nothing (leaf and
+ * per_max stay) and sets the replay's sticky flag, which qlx_replay_sync reports as QLX_E_INVALID, once. */
+/* Allocates the tree (12 bytes per leaf), gives the len live slots priority 1 and the rest 0, per_max = 1, builds the tree
+ * and synchronises; a second call resets to that state.  From here on every push (qlx_replay_push_dev, qlx_replay_push, a
+ * learner's) also writes per_max into the pushed slots and rebuilds the tree, on the stream the push runs on; a replay
+ * without priorities pushes exactly as before.  Snapshots do not store priorities. */
+int32_t qlx_replay_per_enable(qlx_replay* rb);
+/* one batch of `batch` (1..4096) draws into d_out_indices [batch] and, unless NULL, d_out_weights [batch] */
+int32_t qlx_replay_per_sample_dev(qlx_replay* rb, uint64_t seed, uint32_t update_idx, uint32_t rank, uint32_t batch, float beta,
+                                  uint64_t* d_out_indices, float* d_out_weights_or_null);
+/* leaf = (td_abs + eps)^alpha for n (0..4096; 0 launches nothing) logical indices; an index that appears more than once
+ * keeps the value of its LAST position.  The indices are logical indices as they are NOW: as with qlx_replay_batch_dev,
+ * indices drawn before a push on a full ring no longer name the same transitions (each push of n_envs transitions moves
+ * every logical index down by n_envs once len == capacity), so write the priorities of a batch before the next push.
+ * After the call the tree is consistent: a draw needs no build. */
+int32_t qlx_replay_per_update_dev(qlx_replay* rb, const uint64_t* d_indices, const float* d_td_abs, uint32_t n, float alpha,
+                                  float eps);
+/* read-out for tests and diagnostics (host outputs, any may be NULL; synchronises): the leaves by physical slot
+ * [capacity], the whole heap [2L] (node 0 unused), L, the total t[1], per_max and start */
+int32_t qlx_replay_per_get(qlx_replay* rb, float* leaves, float* tree, uint32_t* L, float* total, float* per_max, uint64_t* start);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@
 // the episode does not have yet is zero-filled without a load.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "objects.h"
 #include "replay_dev.h"
 
@@ -223,7 +225,9 @@ int32_t qlx_replay_sync(qlx_replay* r) {
     uint32_t flag = 0;
     QLX_HIP(hipMemcpy(&flag, r->d_flags, 4, hipMemcpyDeviceToHost));
     if (flag) QLX_HIP(hipMemset(r->d_flags, 0, 4));
-    QLX_CHECK(flag == 0, QLX_E_INVALID, "replay index out of range (>= len) in a device call");
+    QLX_CHECK(flag == 0, QLX_E_INVALID,
+              "replay index out of range (>= len) in a device call (or, in a priority write, a td_abs that is NaN, infinite or "
+              "negative)");
   });
 }
 
@@ -291,6 +295,86 @@ int32_t qlx_replay_batch_dev(qlx_replay* r, const uint64_t* d_indices, uint32_t 
       src.flag = r->d_flags;
       launch_unpack(layout, dim3(batch, o.s && o.s_next ? 2 : 1), r->stream, src);
     }
+  });
+}
+
+// ---- prioritized replay on device tensors: the kernels and their launchers are per.hip's ----
+
+int32_t qlx_replay_per_enable(qlx_replay* r) {
+  return guard([&] {
+    QLX_CHECK(r, QLX_E_INVALID, "null replay");
+    QLX_HIP(hipSetDevice(r->device));
+    QLX_HIP(hipDeviceSynchronize());   // pushes may be in flight on an env's stream
+    reserve_dev_scratch(r);
+    PerState& st = r->prio;
+    if (!st.d_tree) {
+      try {
+        st.init(r->cap, 0);
+      } catch (...) {   // a failure part-way releases what was built
+        st = PerState();
+        throw;
+      }
+    }
+    const float one = 1.0f;
+    QLX_HIP(hipMemsetAsync(st.d_tree, 0, st.d_tree.bytes(), r->stream));
+    QLX_HIP(hipMemsetAsync(st.d_owner, 0, st.d_owner.bytes(), r->stream));
+    QLX_HIP(hipMemcpyAsync(st.d_max, &one, sizeof(float), hipMemcpyHostToDevice, r->stream));
+    if (r->len()) QLX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(st.leaves()), (int)f32_bits(one), r->len(), r->stream));
+    per_launch_build(r->stream, st.d_tree, st.L);
+    QLX_HIP(hipStreamSynchronize(r->stream));
+    r->per_on = true;
+  });
+}
+
+int32_t qlx_replay_per_sample_dev(qlx_replay* r, uint64_t seed, uint32_t update_idx, uint32_t rank, uint32_t batch, float beta,
+                                  uint64_t* d_out_indices, float* d_out_weights) {
+  return guard([&] {
+    QLX_CHECK(r, QLX_E_INVALID, "null replay");
+    QLX_CHECK(d_out_indices, QLX_E_INVALID, "null d_out_indices");
+    QLX_CHECK(batch > 0 && batch <= kMaxBatch, QLX_E_INVALID, "batch must be in 1..4096");
+    QLX_CHECK(std::isfinite(beta) && beta >= 0.0f, QLX_E_INVALID, "beta must be finite and >= 0");
+    QLX_CHECK(r->len() > 0, QLX_E_INVALID, "prioritized draw: the replay is empty (len == 0)");
+    QLX_CHECK(r->per_on, QLX_E_STATE, "priorities are not enabled (qlx_replay_per_enable)");
+    QLX_HIP(hipSetDevice(r->device));
+    const uint64_t len = r->len();
+    per_launch_draw(r->stream, r->prio.d_tree, r->prio.L, seed, update_idx, rank, len, beta, batch, r->cap,
+                    (r->total - len) % r->cap, d_out_indices, d_out_weights);
+  });
+}
+
+int32_t qlx_replay_per_update_dev(qlx_replay* r, const uint64_t* d_indices, const float* d_td_abs, uint32_t n, float alpha,
+                                  float eps) {
+  return guard([&] {
+    QLX_CHECK(r, QLX_E_INVALID, "null replay");
+    QLX_CHECK(n <= kMaxBatch, QLX_E_INVALID, "n must be in 0..4096");
+    QLX_CHECK(n == 0 || d_indices, QLX_E_INVALID, "null d_indices");
+    QLX_CHECK(n == 0 || d_td_abs, QLX_E_INVALID, "null d_td_abs");
+    QLX_CHECK(std::isfinite(alpha) && alpha >= 0.0f, QLX_E_INVALID, "alpha must be finite and >= 0");
+    QLX_CHECK(std::isfinite(eps) && eps > 0.0f, QLX_E_INVALID, "eps must be finite and > 0");
+    QLX_CHECK(r->per_on, QLX_E_STATE, "priorities are not enabled (qlx_replay_per_enable)");
+    if (n == 0) return;
+    QLX_HIP(hipSetDevice(r->device));
+    PerState& st = r->prio;
+    const uint64_t len = r->len(), start = (r->total - len) % r->cap;
+    per_launch_update_guarded(r->stream, d_indices, d_td_abs, n, len, r->cap, start, alpha, eps, st.d_owner, st.leaves(), st.d_max,
+                              r->d_flags);
+    per_launch_build(r->stream, st.d_tree, st.L);   // a refit of the changed paths alone measured no faster
+  });
+}
+
+int32_t qlx_replay_per_get(qlx_replay* r, float* leaves, float* tree, uint32_t* L, float* total, float* per_max, uint64_t* start) {
+  return guard([&] {
+    QLX_CHECK(r, QLX_E_INVALID, "null replay");
+    QLX_CHECK(r->per_on, QLX_E_STATE, "priorities are not enabled (qlx_replay_per_enable)");
+    QLX_HIP(hipSetDevice(r->device));
+    QLX_HIP(hipDeviceSynchronize());
+    const PerState& st = r->prio;
+    if (leaves) QLX_HIP(hipMemcpy(leaves, st.leaves(), r->cap * 4, hipMemcpyDeviceToHost));
+    if (tree) QLX_HIP(hipMemcpy(tree, st.d_tree, st.d_tree.bytes(), hipMemcpyDeviceToHost));
+    if (L) *L = st.L;
+    if (total) QLX_HIP(hipMemcpy(total, st.d_tree + 1, 4, hipMemcpyDeviceToHost));
+    if (per_max) QLX_HIP(hipMemcpy(per_max, st.d_max, 4, hipMemcpyDeviceToHost));
+    if (start) *start = (r->total - r->len()) % r->cap;
   });
 }
 

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "per.h"
 #include "qlx_internal.h"
 
 struct qlx_env {
@@ -40,6 +41,8 @@ struct qlx_replay {
   qlx::DeviceBuffer<uint64_t> d_idx;    // scratch for sampling [max_batch]
   qlx::DeviceBuffer<uint64_t> d_win_last;   // [4096] qlx_replay_batch_dev: each window's last index (reserved at its first call, kept)
   qlx::DeviceBuffer<uint32_t> d_flags;      // [4] sticky bad-index flag of the _dev calls (with d_win_last)
+  qlx::PerState prio;                       // priorities of the device-tensor calls (qlx_replay_per_enable)
+  bool per_on = false;
   uint64_t len() const { return total < cap ? total : cap; }
 };
 

@@ -31,4 +31,14 @@ void per_launch_push(hipStream_t s, float* leaves, uint64_t cap, uint64_t first,
 void per_launch_update(hipStream_t s, const uint64_t* idx, const float* td_abs, uint32_t n, uint64_t cap, uint64_t start,
                        float alpha, float eps, uint32_t* owner, float* leaves, float* per_max);
 
+// ---- one batch per call (the replay's device-tensor calls) ----
+// B <= 4096 draws of update `update_idx` from a built tree: k_per_sample's draws bit for bit; w_out may be null
+void per_launch_draw(hipStream_t s, const float* tree, uint32_t L, uint64_t seed, uint32_t update_idx, uint32_t rank, uint64_t len,
+                     float beta, uint32_t B, uint64_t cap, uint64_t start, uint64_t* idx_out, float* w_out);
+// per_launch_update with the data the host cannot see guarded: an index >= len or a td_abs that is NaN, infinite or
+// negative writes nothing and sets *flag
+void per_launch_update_guarded(hipStream_t s, const uint64_t* idx, const float* td_abs, uint32_t n, uint64_t len, uint64_t cap,
+                               uint64_t start, float alpha, float eps, uint32_t* owner, float* leaves, float* per_max,
+                               uint32_t* flag);
+
 }  // namespace qlx

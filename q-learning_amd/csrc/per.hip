@@ -184,6 +184,195 @@ void per_launch_update(hipStream_t s, const uint64_t* idx, const float* td_abs, 
   QLX_HIP(hipGetLastError());
 }
 
+// ---------------- one batch per call (the replay's device-tensor calls) ----------------
+// k_per_sample is shaped for the learner: one block per update, 64 of them side by side, each lane's draws one after the
+// other, 20 dependent loads per draw at L = 2^20.  One batch alone is a pure dependent-latency problem, so k_per_draw
+// resolves three tree levels per round trip: below node i the children lie at t[2i .. 2i + 1], the grandchildren at
+// t[4i .. 4i + 3], the great-grandchildren at t[8i .. 8i + 7], each group contiguous and aligned to its size (8, 16 and
+// 32 bytes), so the three loads issue together and the three decisions are made in registers - with the binary descent's
+// own comparisons and subtractions, in its order, so every draw is k_per_sample's bit for bit.  One 1024-thread workgroup
+// (the batch maximum stays inside it), D = ceil(B / 1024) <= 4 draws per lane, all of them in flight in every round.
+
+// one level of the descent over the pair (left, right) below the current node: the bit taken, x and the value reached
+__device__ __forceinline__ uint32_t per_step(float left, float right, float& x, float& val) {
+  if (x < left || right == 0.0f) {
+    val = left;
+    return 0u;
+  }
+  x -= left;
+  val = right;
+  return 1u;
+}
+
+constexpr uint32_t kDrawThreads = 1024;
+
+template <int D>
+__global__ __launch_bounds__(kDrawThreads) void k_per_draw(const float* __restrict__ t, uint32_t logL, uint64_t seed,
+                                                           uint32_t update, uint32_t rank, uint64_t len, float beta, uint32_t B,
+                                                           uint64_t cap, uint64_t start, uint64_t* __restrict__ idx_out,
+                                                           float* __restrict__ w_out) {
+  __shared__ float red[kDrawThreads / 64];
+  const uint32_t tid = threadIdx.x;
+  const float T = t[1];
+  const float seg = T / (float)B;
+  float x[D], val[D];
+  uint32_t node[D];
+  bool act[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    const uint32_t b = tid + d * kDrawThreads;
+    act[d] = b < B;
+    node[d] = 1;
+    val[d] = T;   // L = 1: the root is the leaf
+    x[d] = 0.0f;
+    if (act[d]) {
+      RngStream s(seed, update, rank, P_PER, b);
+      const float r = uniform_f32(s, 0.0f, 1.0f);
+      x[d] = seg * ((float)b + r);
+    }
+  }
+  uint32_t lev = 0;
+  for (; lev + 3 <= logL; lev += 3) {   // nodes 8i + 7 < 16 * 2^lev <= 2L
+    float2 c[D];
+    float4 g[D], h0[D], h1[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (act[d]) {
+        const size_t i = node[d];
+        c[d] = *reinterpret_cast<const float2*>(t + 2 * i);
+        g[d] = *reinterpret_cast<const float4*>(t + 4 * i);
+        h0[d] = *reinterpret_cast<const float4*>(t + 8 * i);
+        h1[d] = *reinterpret_cast<const float4*>(t + 8 * i + 4);
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (act[d]) {
+        const uint32_t b1 = per_step(c[d].x, c[d].y, x[d], val[d]);
+        const uint32_t b2 = per_step(b1 ? g[d].z : g[d].x, b1 ? g[d].w : g[d].y, x[d], val[d]);
+        const float4 h = b1 ? h1[d] : h0[d];
+        const uint32_t b3 = per_step(b2 ? h.z : h.x, b2 ? h.w : h.y, x[d], val[d]);
+        node[d] = 8 * node[d] + 4 * b1 + 2 * b2 + b3;
+      }
+    }
+  }
+  if (logL - lev == 2) {   // nodes 4i + 3 < 8 * 2^lev = 2L
+    float2 c[D];
+    float4 g[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (act[d]) {
+        const size_t i = node[d];
+        c[d] = *reinterpret_cast<const float2*>(t + 2 * i);
+        g[d] = *reinterpret_cast<const float4*>(t + 4 * i);
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (act[d]) {
+        const uint32_t b1 = per_step(c[d].x, c[d].y, x[d], val[d]);
+        const uint32_t b2 = per_step(b1 ? g[d].z : g[d].x, b1 ? g[d].w : g[d].y, x[d], val[d]);
+        node[d] = 4 * node[d] + 2 * b1 + b2;
+      }
+    }
+  } else if (logL - lev == 1) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (act[d]) {
+        const float2 c = *reinterpret_cast<const float2*>(t + 2 * (size_t)node[d]);
+        node[d] = 2 * node[d] + per_step(c.x, c.y, x[d], val[d]);
+      }
+    }
+  }
+  const uint32_t L = 1u << logL;
+  float w[D];
+  float wmax = 0.0f;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    w[d] = 0.0f;
+    if (act[d]) {
+      const uint64_t slot = node[d] - L;
+      idx_out[tid + d * kDrawThreads] = (slot + cap - start) % cap;
+      if (w_out) {
+        const float p = val[d] / T;   // val = t[node]: the value the last step reached
+        w[d] = per_powf((float)len * p, -beta);
+        wmax = fmaxf(wmax, w[d]);
+      }
+    }
+  }
+  if (!w_out) return;   // uniform over the workgroup
+  for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o));
+  if ((tid & 63) == 0) red[tid >> 6] = wmax;
+  __syncthreads();
+  wmax = red[0];
+#pragma unroll
+  for (uint32_t k = 1; k < kDrawThreads / 64; ++k) wmax = fmaxf(wmax, red[k]);
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+    if (act[d]) w_out[tid + d * kDrawThreads] = w[d] / wmax;
+}
+
+void per_launch_draw(hipStream_t s, const float* tree, uint32_t L, uint64_t seed, uint32_t update_idx, uint32_t rank, uint64_t len,
+                     float beta, uint32_t B, uint64_t cap, uint64_t start, uint64_t* idx_out, float* w_out) {
+  QLX_CHECK(len > 0 && len <= cap && cap <= L && start < cap, QLX_E_INVALID, "prioritized draw: bad replay range");
+  QLX_CHECK(B > 0 && B <= 4 * kDrawThreads, QLX_E_INVALID, "prioritized draw: batch must be in 1..4096");
+  uint32_t logL = 0;
+  while ((1u << logL) < L) ++logL;
+  const auto k = B <= kDrawThreads ? k_per_draw<1> : B <= 2 * kDrawThreads ? k_per_draw<2> : k_per_draw<4>;
+  hipLaunchKernelGGL(k, dim3(1), dim3(kDrawThreads), 0, s, tree, logL, seed, update_idx, rank, len, beta, B, cap, start, idx_out,
+                     w_out);
+  QLX_HIP(hipGetLastError());
+}
+
+// The priority write's claim / write pair with the data the host cannot see guarded.  An entry is valid iff its index is
+// < len and its td_abs is finite and >= 0; only valid entries claim, so "last writer wins" holds among them, and only they
+// store (through the claim) and raise per_max.  Both kernels evaluate the same predicate.  (A valid entry's priority is
+// finite for alpha <= 1: td_abs + eps <= FLT_MAX.)
+__device__ __forceinline__ bool per_entry(const uint64_t* idx, const float* td_abs, uint32_t k, uint64_t len, uint64_t* i,
+                                          float* td) {
+  *i = idx[k];
+  *td = td_abs[k];
+  return *i < len && *td >= 0.0f && !__builtin_isinf(*td);   // NaN fails the comparison
+}
+
+__global__ void k_per_claim_guarded(const uint64_t* idx, const float* td_abs, uint32_t n, uint64_t len, uint64_t cap,
+                                    uint64_t start, uint32_t* owner, uint32_t* flag) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  uint64_t i;
+  float td;
+  if (per_entry(idx, td_abs, k, len, &i, &td))
+    atomicMax(&owner[(start + i) % cap], k + 1);
+  else
+    atomicOr(flag, 1u);
+}
+
+__global__ void k_per_write_guarded(const uint64_t* idx, const float* td_abs, uint32_t n, uint64_t len, uint64_t cap,
+                                    uint64_t start, float alpha, float eps, uint32_t* owner, float* leaves, float* per_max) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  uint64_t i;
+  float td;
+  if (!per_entry(idx, td_abs, k, len, &i, &td)) return;
+  const uint64_t slot = (start + i) % cap;
+  const float pr = per_powf(td + eps, alpha);
+  if (owner[slot] == k + 1) {
+    leaves[slot] = pr;
+    owner[slot] = 0;
+  }
+  atomicMax(reinterpret_cast<uint32_t*>(per_max), f32_bits(pr));
+}
+
+void per_launch_update_guarded(hipStream_t s, const uint64_t* idx, const float* td_abs, uint32_t n, uint64_t len, uint64_t cap,
+                               uint64_t start, float alpha, float eps, uint32_t* owner, float* leaves, float* per_max,
+                               uint32_t* flag) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_per_claim_guarded, dim3((n + 255) / 256), dim3(256), 0, s, idx, td_abs, n, len, cap, start, owner, flag);
+  hipLaunchKernelGGL(k_per_write_guarded, dim3((n + 255) / 256), dim3(256), 0, s, idx, td_abs, n, len, cap, start, alpha, eps, owner,
+                     leaves, per_max);
+  QLX_HIP(hipGetLastError());
+}
+
 uint32_t per_leaves(uint64_t cap) {
   uint32_t L = 1;
   while (L < cap) L <<= 1;

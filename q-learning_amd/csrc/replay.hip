@@ -152,6 +152,10 @@ void replay_launch_push(qlx_replay* rb, qlx_env* env, hipStream_t s, const uint8
                      d_actions, d_rewards, d_dones, rb->d_frames, rb->d_action, rb->d_reward, rb->d_done, rb->d_epstep,
                      rb->total, rb->cap, rb->F);
   QLX_HIP(hipGetLastError());
+  if (rb->per_on) {   // priorities enabled (qlx_replay_per_enable): the pushed slots enter at per_max, the tree follows
+    per_launch_push(s, rb->prio.leaves(), rb->cap, rb->total, env->n, rb->prio.d_max);
+    per_launch_build(s, rb->prio.d_tree, rb->prio.L);
+  }
   rb->total += env->n;
 }
 

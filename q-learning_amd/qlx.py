@@ -241,6 +241,10 @@ def lib():
         "qlx_env_obs_dev": ([vp, i32, vp], i32), "qlx_env_reset_dev": ([vp, vp], i32),
         "qlx_replay_sample_distinct_dev": ([vp, u64, u32, u32, u32, vp], i32),
         "qlx_replay_batch_dev": ([vp, vp, u32, u32, f32, i32, C.POINTER(BatchDev)], i32),
+        "qlx_replay_per_enable": ([vp], i32),
+        "qlx_replay_per_sample_dev": ([vp, u64, u32, u32, u32, f32, vp, vp], i32),
+        "qlx_replay_per_update_dev": ([vp, vp, vp, u32, f32, f32], i32),
+        "qlx_replay_per_get": ([vp, vp, vp, vp, vp, vp, vp], i32),
         "qlx_model_create": ([i32, u64, i32, C.POINTER(vp)], i32), "qlx_model_destroy": ([vp], i32),
         "qlx_model_num_vars": ([], i32), "qlx_model_var_size": ([i32], C.c_int64), "qlx_model_hparams": ([vp], i32),
         "qlx_bg_model_hparams": ([vp], i32),
@@ -482,6 +486,7 @@ class ReplayBuffer:
             _check(lib().qlx_replay_create(capacity, n_envs, device, C.byref(h)))
             handle = h.value
         self.h = handle
+        self.capacity = capacity or None   # unknown for a wrapped handle
 
     def close(self):
         if getattr(self, "_owned", False) and getattr(self, "h", None):
@@ -542,6 +547,27 @@ class ReplayBuffer:
         steps = np.zeros(B, np.uint32)
         _check(lib().qlx_replay_nstep(self.h, _p(idx), B, n_step, gamma, _p(ret), _p(disc), _p(last), _p(term), _p(steps)))
         return dict(returns=ret, discounts=disc, last_indices=last, terminals=term.astype(bool), steps=steps)
+
+    # prioritized replay on device tensors (include/qlx.h); the d_* arguments are device addresses
+    def per_enable(self):
+        """priorities on: every live slot at 1, per_max = 1 (again: reset to that); pushes keep the tree from here on"""
+        _check(lib().qlx_replay_per_enable(self.h))
+
+    def per_sample_dev(self, seed, update_idx, batch, beta, d_out_indices, d_out_weights=None, rank=0):
+        _check(lib().qlx_replay_per_sample_dev(self.h, seed, update_idx, rank, batch, beta, d_out_indices, d_out_weights))
+
+    def per_update_dev(self, d_indices, d_td_abs, n, alpha, eps):
+        _check(lib().qlx_replay_per_update_dev(self.h, d_indices, d_td_abs, n, alpha, eps))
+
+    def per_get(self):
+        """dict(leaves [capacity] by physical slot ([L] when the capacity is not known), tree [2L], total, per_max, start)"""
+        L, total, pmax, start = C.c_uint32(), C.c_float(), C.c_float(), C.c_uint64()
+        _check(lib().qlx_replay_per_get(self.h, None, None, C.byref(L), None, None, None))
+        tree = np.zeros(2 * L.value, np.float32)
+        leaves = np.zeros(L.value, np.float32)
+        _check(lib().qlx_replay_per_get(self.h, _p(leaves), _p(tree), None, C.byref(total), C.byref(pmax), C.byref(start)))
+        return dict(leaves=leaves[:self.capacity], tree=tree, total=np.float32(total.value), per_max=np.float32(pmax.value),
+                    start=int(start.value))
 
 
 class DeepQLearningModel:

@@ -1,8 +1,9 @@
 """The batched Breakout env, the HBM replay, its sampler and the Q-net for an agent that lives in PyTorch device tensors.
 
-Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls" and
-"Q-network on device tensors"): observations, steps, pushes, sampled n-step batches, Q-values and
-whole updates go from kernel to tensor without touching the host.  No call synchronises; order against torch's work is
+Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls",
+"Q-network on device tensors" and "Prioritized replay on device tensors"): observations, steps,
+pushes, sampled n-step batches, prioritized draws and priority writes, Q-values and whole updates go from kernel to tensor
+without touching the host.  No call synchronises; order against torch's work is
 kept by stream waits (below).
 
 One HIP runtime per process.  torch's wheel carries a libamdhip64 of its own, libqlx.so asks for the system's by
@@ -285,8 +286,47 @@ class TorchReplay(_Streamed):
         """sample_indices + batch: `batch` distinct transitions drawn from stream (seed, update_idx, rank)"""
         return self.batch(self.sample_indices(batch, seed, update_idx, rank), n_step, gamma, layout, out)
 
+    def enable_priorities(self):
+        """Proportional prioritized replay from here on: the transitions held now get priority 1, later
+        ones enter at the largest priority written so far.  Synchronises; a second call resets to that state."""
+        if self.h is None:
+            raise QlError("the object is closed")
+        self._rb.per_enable()
+
+    def sample_prioritized(self, batch, seed, update_idx, beta=0.4, rank=0):
+        """`batch` draws (with replacement) in proportion to the priorities, from stream (seed, update_idx, rank):
+        (indices int64 [batch], importance weights float32 [batch] = (len P(i))^-beta over the batch's largest)"""
+        if not 0 < batch <= MAX_BATCH:
+            raise ValueError(f"batch must be in 1..{MAX_BATCH}")
+        idx = torch.empty(batch, dtype=torch.int64, device=self.device)
+        w = torch.empty(batch, dtype=torch.float32, device=self.device)
+        with self._ordered(idx, w):
+            self._rb.per_sample_dev(seed, update_idx, batch, beta, idx.data_ptr(), w.data_ptr(), rank)
+        return idx, w
+
+    def update_priorities(self, indices, td_abs, alpha=0.6, eps=1e-6):
+        """priority (td_abs + eps)^alpha for the transitions at `indices` (int64 [n], as they are now: before the next
+        add on a full ring), td_abs float32 [n]; the last of a repeated index wins.  An index >= len or a td_abs that
+        is NaN, infinite or negative writes nothing and gives an error at sync()."""
+        if not isinstance(indices, torch.Tensor) or indices.dim() != 1:
+            raise ValueError("indices must be a 1-d tensor")
+        n = indices.shape[0]
+        if n > MAX_BATCH:
+            raise ValueError(f"at most {MAX_BATCH} priorities per call")
+        idx = _arg("indices", indices, self.device, torch.int64, (n,))
+        td = _arg("td_abs", td_abs, self.device, torch.float32, (n,))
+        with self._ordered(idx, td):
+            self._rb.per_update_dev(idx.data_ptr() or None, td.data_ptr() or None, n, alpha, eps)
+
+    def priorities(self):
+        """read-out (synchronises): dict of numpy leaves [capacity] by physical slot, tree [2L], total, per_max, start"""
+        if self.h is None:
+            raise QlError("the object is closed")
+        return self._rb.per_get()
+
     def sync(self):
-        """wait for the replay's stream; QlError, once, if a call since the last sync met an index >= len"""
+        """wait for the replay's stream; QlError, once, if a call since the last sync met an index >= len (or, with
+        priorities, a td_abs that is NaN, infinite or negative)"""
         qlx._check(_L.qlx_replay_sync(self.h))
 
 

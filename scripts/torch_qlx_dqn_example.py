@@ -5,7 +5,11 @@ target is computed in a few lines of torch, and forward, backward, clip and Adam
 kernels on states that never leave the replay ring.  It shows the calls in the order an agent makes them and prints loss and
 env-steps/s; a few hundred updates teach nothing, and nothing here is a learning claim.
 
-  python scripts/torch_qlx_dqn_example.py [--envs 256] [--updates 300] [--batch 64] [--n-step 3] [--arch f32|bf16]
+--per draws the batch in proportion to the priorities instead: sample_prioritized, batch, targets, train
+with the importance weights and want_td_abs, update_priorities - before the next add, which moves the logical indices of a
+full ring - then add; none of these calls synchronises or copies to the host.
+
+  python scripts/torch_qlx_dqn_example.py [--envs 256] [--updates 300] [--batch 64] [--n-step 3] [--arch f32|bf16] [--per]
 """
 import argparse
 import os
@@ -30,12 +34,17 @@ def main():
     ap.add_argument("--warmup-steps", type=int, default=20)
     ap.add_argument("--target-sync", type=int, default=100)
     ap.add_argument("--arch", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--per", action="store_true", help="prioritized replay: sample_prioritized / update_priorities")
+    ap.add_argument("--per-alpha", type=float, default=0.6)
+    ap.add_argument("--per-beta", type=float, default=0.4)
     args = ap.parse_args()
 
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     env = QT.TorchEnv(args.envs, seed=1, device=dev)
     rb = QT.TorchReplay(args.replay, env)
+    if args.per:
+        rb.enable_priorities()   # every transition added from here on enters at the largest priority so far
     reserve = max(args.envs, args.batch)
     online = QT.TorchQNet(args.arch, seed=2, env=env, reserve=reserve)    # env, replay and both nets on one stream
     target = QT.TorchQNet(args.arch, seed=3, env=env, reserve=reserve)
@@ -56,7 +65,10 @@ def main():
         steps += 1
         if steps < args.warmup_steps:
             continue
-        idx = rb.sample_indices(args.batch, seed=42, update_idx=updates)
+        if args.per:
+            idx, weights = rb.sample_prioritized(args.batch, seed=42, update_idx=updates, beta=args.per_beta)
+        else:
+            idx, weights = rb.sample_indices(args.batch, seed=42, update_idx=updates), None
         b = rb.batch(idx, n_step=args.n_step, gamma=args.gamma, layout=lay,
                      fields=("actions", "returns", "discounts", "terminals", "last_indices"))   # no state is copied
         # double DQN over the n-step window: the online net picks a*, the target net values it
@@ -64,7 +76,9 @@ def main():
         q_next = target.q(replay=rb, indices=b.last_indices, which="s_next", layout=lay, want="q")
         bootstrap = q_next.gather(1, a_star.long().unsqueeze(1)).squeeze(1)
         y = b.returns + b.discounts * bootstrap * (1.0 - b.terminals.float())
-        last_loss, _ = online.train(b.actions, y, replay=rb, indices=idx, layout=lay)
+        last_loss, td_abs = online.train(b.actions, y, weights, replay=rb, indices=idx, layout=lay, want_td_abs=args.per)
+        if args.per:
+            rb.update_priorities(idx, td_abs, alpha=args.per_alpha)   # before the next add
         updates += 1
         if updates % args.target_sync == 0:
             target.copy_weights_from(online)
@@ -76,7 +90,7 @@ def main():
     rb.sync()
     online.sync()
     target.sync()
-    print(f"done: {updates} updates, {steps} vector steps x {args.envs} envs in {dt:.2f} s = {steps * args.envs / dt:,.0f} env-steps/s "
+    print(f"done ({'prioritized' if args.per else 'uniform'} replay): {updates} updates, {steps} vector steps x {args.envs} envs in {dt:.2f} s = {steps * args.envs / dt:,.0f} env-steps/s "
           f"(acting net, replay and updates included), last loss {float(last_loss):.5f}")
     env.close()   # closes the replay and the nets that share its stream first
 
