@@ -634,6 +634,32 @@ int32_t qlx_model_train_dev(qlx_model* m, const qlx_states_dev* src, const uint8
 int32_t qlx_model_copy_weights_dev(qlx_model* dst, qlx_model* src);
 /* qlx_model_sync (above) also reports, once, a flag set by a _dev call since the last sync */
 
+/* ---- a caller's own loss: backward and optimizer as separate steps ----
+ * For a loss L(Q) computed outside the library the caller passes dq = dL/dQ [batch][3]; the backward gives the gradient of
+ * sum_{b,n} dq[b][n] * Q(src)[b][n], i.e. dL/dvariables, through the same kernels as the built-in update (a dq row that is
+ * zero except at the taken action reproduces that update's gradient value for value).  Same conventions and host checks as
+ * above (a null model / src / d_dq / out pointer, the source's cases, batch 0 or > 4096, unknown step flags: QLX_E_INVALID
+ * before any handle is read; then the reserve check QLX_E_STATE, device mismatches, the env count).
+ * Source stability: the env and replay sources are read in place, by the forward and again by the backward (the conv1
+ * weight gradient reads the frames).  The caller must not step the env or push into the replay between a forward and the
+ * backward that belongs to it, and a dense `obs` passed to a recomputing backward must hold what the forward saw. */
+#define QLX_STEP_GRADS_WRITTEN 1u  /* qlx_model_step_dev: the caller modified the buffer through qlx_model_grads_dev */
+/* identifies the model's most recent forward pass (any caller); never 0 */
+int32_t qlx_model_forward_ticket(qlx_model* m, uint64_t* ticket_out);
+/* raw gradients of sum_{b,n} dq[b][n] * Q(src)[b][n] w.r.t. all ten variables -> the model's gradient buffer
+ * (overwritten, not accumulated).  No clip, no Adam, iterations unchanged.  Enqueue only.  With `ticket` the model's
+ * current ticket, that forward over `batch` samples and its activations still usable, no table is built and no forward
+ * runs; otherwise, and always for ticket 0, the table is built from src and the trunk forward runs again.  Both ways give
+ * identical gradients.  An index >= len behaves as in qlx_model_q_dev: zero state, sticky flag. */
+int32_t qlx_model_backward_dev(qlx_model* m, const qlx_states_dev* src, const float* d_dq /*[batch][3]*/,
+                               uint32_t batch, uint64_t ticket);
+/* clip_by_norm per variable + Adam on the gradient buffer, iterations + 1.  QLX_E_STATE before any backward or train has
+ * filled the buffer.  flags: 0 or QLX_STEP_GRADS_WRITTEN */
+int32_t qlx_model_step_dev(qlx_model* m, uint32_t flags);
+/* device pointer to the flat fp32 gradient buffer [1,685,667], variable order of qlx_model_train's grads_out;
+ * valid for the model's lifetime */
+int32_t qlx_model_grads_dev(qlx_model* m, float** d_grads_out, uint64_t* count_out);
+
 /* ---------------- Prioritized replay on device tensors (beyond the reference) ----------------
  * The learner's proportional prioritized replay (the sum tree above: same heap, same draws, same weights, same priority
  * write) kept inside a qlx_replay and driven one batch per call from device memory.  Conventions of "Device-tensor env and

@@ -59,11 +59,13 @@ void ws_common(qlx_model* m, Arena& a, int B) {
 
 void model_workspace(qlx_model* m, int B) {
   if (B <= m->ws_batch) return;
+  m->fwd_reusable = false;   // the activations go with the old allocation
   m->f32 ? f32_workspace(m, B) : bf16_workspace(m, B);
 }
 
 void model_pack(qlx_model* m) {
   m->version += 1;
+  m->fwd_reusable = false;
   if (!m->f32) bf16_pack(m);   // the fp32 path reads the master weights directly
 }
 
@@ -72,6 +74,9 @@ void model_set_batch_invariant(qlx_model* m) {
 }
 
 void model_forward_trunk(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool store_acts) {
+  if (++m->fwd_ticket == 0) m->fwd_ticket = 1;
+  m->fwd_table = table;
+  m->fwd_reusable = m->f32 || store_acts;   // (the fp32 forward always stores a1 .. a3)
   m->f32 ? f32_forward(m, table, B, s) : bf16_forward(m, table, B, s, store_acts);
 }
 
@@ -96,11 +101,21 @@ void model_backward_dense(qlx_model* m, int B, const uint8_t* actions, const flo
          : bf16_backward_dense(m, B, actions, y, loss_dev, s, weights, td_abs);
 }
 
+void model_backward_dq(qlx_model* m, const uint8_t* const* table, int B, const float* dq, hipStream_t s, bool fuse_update) {
+  model_backward_dq_dense(m, B, dq, s);
+  model_backward_conv(m, table, B, s, fuse_update);
+}
+
+void model_backward_dq_dense(qlx_model* m, int B, const float* dq, hipStream_t s) {
+  m->f32 ? f32_backward_dense_dq(m, B, dq, s) : bf16_backward_dense_dq(m, B, dq, s);
+}
+
 // the conv part of the backward (after model_backward_dense on the same batch): dz3 -> dz2 -> dz1 and the
 // three conv weight gradients into m->d_grads
 void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update, hipEvent_t dense_ready,
                          float dense_scale) {
   m->f32 ? f32_backward_conv(m, table, B, s, fuse_update, dense_ready, dense_scale) : bf16_backward_conv(m, table, B, s);
+  m->grads_filled = true;
 }
 
 void model_gradient_replaced(qlx_model* m) { m->f32 ? f32_gradient_replaced(m) : bf16_gradient_replaced(m); }
@@ -111,7 +126,10 @@ void model_norms_dense(qlx_model* m, hipStream_t s, float scale) {
 
 void model_norms(qlx_model* m, hipStream_t s, float scale) { m->f32 ? f32_norms(m, s, scale) : bf16_norms(m, s, scale); }
 
-void model_adam(qlx_model* m, hipStream_t s, float scale) { m->f32 ? f32_adam(m, s, scale) : bf16_adam(m, s, scale); }
+void model_adam(qlx_model* m, hipStream_t s, float scale) {
+  m->f32 ? f32_adam(m, s, scale) : bf16_adam(m, s, scale);
+  m->fwd_reusable = false;   // the activations belong to the weights before this update
+}
 
 static void model_frame_table_from_host(qlx_model* m, const uint8_t* obs_host, int B) {
   model_workspace(m, B);
@@ -303,6 +321,7 @@ int32_t qlx_model_apply_gradient(qlx_model* m, const float* grads, float scale, 
     hipStream_t s = m->stream;
     model_workspace(m, std::max(m->ws_batch, 1));   // (the norm partial buffers)
     QLX_HIP(hipMemcpyAsync(m->d_grads, grads, kNumParams * 4, hipMemcpyHostToDevice, s));
+    m->grads_filled = true;
     model_gradient_replaced(m);
     model_norms(m, s, scale);
     model_adam(m, s, scale);

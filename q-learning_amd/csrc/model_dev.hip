@@ -271,6 +271,59 @@ int32_t qlx_model_train_dev(qlx_model* m, const qlx_states_dev* src, const uint8
   });
 }
 
+int32_t qlx_model_forward_ticket(qlx_model* m, uint64_t* ticket_out) {
+  return guard([&] {
+    QLX_CHECK(m, QLX_E_INVALID, "null model");
+    QLX_CHECK(ticket_out, QLX_E_INVALID, "null ticket_out");
+    *ticket_out = m->fwd_ticket;
+  });
+}
+
+// The last forward's activations serve when the ticket is that forward's, it ran over `batch` samples of the model's own
+// table (a _dev or host call built it, and it is still in place), it stored its activations, and neither the weights nor
+// the workspace changed since (model_forward_trunk / model_adam / model_pack / model_workspace keep fwd_reusable).  The
+// bf16 forward may have left a4 as pending fc1 partials: either way the dq head finishes a4 exactly as the forward's head
+// did (fc2_args), so both ways give the same gradient.
+int32_t qlx_model_backward_dev(qlx_model* m, const qlx_states_dev* src, const float* d_dq, uint32_t batch, uint64_t ticket) {
+  return guard([&] {
+    QLX_CHECK(m, QLX_E_INVALID, "null model");
+    check_source(src);
+    QLX_CHECK(d_dq, QLX_E_INVALID, "null d_dq");
+    QLX_CHECK(batch > 0 && batch <= kMaxTrain, QLX_E_INVALID, "batch must be in 1..4096");
+    const qlx_states_dev s = *src;
+    check_handles(m, s, batch);
+    QLX_HIP(hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    const int B = (int)batch;
+    const bool reuse = ticket != 0 && ticket == m->fwd_ticket && m->fwd_reusable && m->last_batch == B && m->fwd_table == m->w.table;
+    if (!reuse) model_forward_trunk(m, states_table(m, s, batch), B, st);
+    model_backward_dq(m, m->w.table, B, d_dq, st, false);
+  });
+}
+
+int32_t qlx_model_step_dev(qlx_model* m, uint32_t flags) {
+  return guard([&] {
+    QLX_CHECK(m, QLX_E_INVALID, "null model");
+    QLX_CHECK((flags & ~(uint32_t)QLX_STEP_GRADS_WRITTEN) == 0, QLX_E_INVALID, "unknown flags");
+    QLX_CHECK(m->grads_filled, QLX_E_STATE, "no gradient yet: qlx_model_backward_dev (or a train call) first");
+    QLX_HIP(hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    if (flags & QLX_STEP_GRADS_WRITTEN) model_gradient_replaced(m);
+    model_norms(m, st, 1.0f);
+    model_adam(m, st, 1.0f);
+  });
+}
+
+int32_t qlx_model_grads_dev(qlx_model* m, float** d_grads_out, uint64_t* count_out) {
+  return guard([&] {
+    QLX_CHECK(m, QLX_E_INVALID, "null model");
+    QLX_CHECK(d_grads_out, QLX_E_INVALID, "null d_grads_out");
+    QLX_CHECK(count_out, QLX_E_INVALID, "null count_out");
+    *d_grads_out = m->d_grads.get();
+    *count_out = (uint64_t)kNumParams;
+  });
+}
+
 int32_t qlx_model_copy_weights_dev(qlx_model* dst, qlx_model* src) {
   return guard([&] {
     QLX_CHECK(dst, QLX_E_INVALID, "null dst");

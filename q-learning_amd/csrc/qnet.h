@@ -63,6 +63,14 @@ struct qlx_model {
   qlx::DeviceBuffer<uint8_t> ws;   // one allocation: the common buffers (w), then the backend's
   int ws_batch = 0;
   int last_batch = 0;
+  // The last trunk forward (model_forward_trunk), for qlx_model_backward_dev: its ticket (a counter, never 0), the table it
+  // read, and whether a backward may still use what it left - it stored its activations, and neither the weights
+  // (model_adam, model_pack) nor the workspace changed since.  grads_filled: a backward (or qlx_model_apply_gradient) has
+  // written d_grads.
+  uint64_t fwd_ticket = 1;
+  const uint8_t* const* fwd_table = nullptr;
+  bool fwd_reusable = false;
+  bool grads_filled = false;
   qlx::CommonWs w;
   qlx::Profiler* prof = nullptr;   // set by the learner while profiling
   // the _dev calls (model_dev.hip), all set by qlx_model_reserve: the largest n they may run, the sticky flag word
@@ -131,6 +139,12 @@ void model_backward(qlx_model* m, const uint8_t* const* table, int B, const uint
                     hipStream_t s, const float* weights = nullptr, float* td_abs = nullptr, bool fuse_update = false);
 void model_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                           const float* weights = nullptr, float* td_abs = nullptr);
+// The backward of sum_{b,n} dq[b][n] Q[b][n] for a caller's dq [B][3] (device) in place of the Huber head, after
+// model_forward_trunk on the same batch: raw gradients -> m->d_grads.  = model_backward_dq_dense (the dq head, fc1 and the
+// dense-3 gradients; no loss) followed by model_backward_conv as it is.  A dq row that is 0 except at one action gives
+// model_backward's gradients value for value.
+void model_backward_dq(qlx_model* m, const uint8_t* const* table, int B, const float* dq, hipStream_t s, bool fuse_update = false);
+void model_backward_dq_dense(qlx_model* m, int B, const float* dq, hipStream_t s);
 // dense_ready (data parallel): the dense bucket's all-reduce event; the fp32 reduction launch then waits for it and computes
 // the dense variables' clip-norm partials of the reduced gradient x dense_scale as its extra blocks (bf16 ignores both)
 void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update = false,
@@ -189,6 +203,7 @@ Fc2Args bf16_fc2_args(qlx_model* m, int B);
 void bf16_head(int mode, const Fc2Args& a, int B, hipStream_t s);
 void bf16_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                          const float* weights, float* td_abs);
+void bf16_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s);
 void bf16_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s);
 void bf16_gradient_replaced(qlx_model* m);
 void bf16_norms(qlx_model* m, hipStream_t s, float scale);
@@ -203,6 +218,7 @@ Fc2Args f32_fc2_args(qlx_model* m, int B);
 void f32_head(int mode, const Fc2Args& a, int B, hipStream_t s);   // mode 3 = training head
 void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                         const float* weights, float* td_abs);
+void f32_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s);
 void f32_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s, bool fuse_update,
                        hipEvent_t dense_ready = nullptr, float dense_scale = 1.0f);
 void f32_gradient_replaced(qlx_model* m);

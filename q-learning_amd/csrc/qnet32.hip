@@ -215,6 +215,43 @@ __global__ __launch_bounds__(256) void k_head32(Fc2Args A) {
   }
 }
 
+// The dense-3 backward for a caller's dq [B][3] (model_backward_dq): dz4[b][k] = (a4 > 0) ? the fmaf chain over n ascending
+// of W4[k][n] dq[b][n], first product rounded : 0.  A dq row that is 0 except at one action leaves the chain at that
+// single rounded product (a product with 0 adds nothing), i.e. k_head32<3>'s dz4.  No Q chain, so no MFMA fragment and
+// no LDS: thread (k4, h) holds W4 rows 4 k4 .. + 3 (12 consecutive floats, three 16-byte loads), the a4 float4 of its
+// kHsDq / 2 samples and their dq, every load issued before the first use (one memory round), and stores dz4 as float4s.
+// kHsDq = 4 samples per block as the training head: 256 blocks at B = 1024.
+constexpr int kHsDq = 4;
+__global__ __launch_bounds__(256) void k_head32_dq(const float* __restrict__ a4, const float* __restrict__ w4,
+                                                   const float* __restrict__ dq, int B, float* __restrict__ dz4) {
+  const int k4 = threadIdx.x & 127, h = threadIdx.x >> 7;
+  const int s0 = blockIdx.x * kHsDq;
+  f32x4 wr[3], xr[kHsDq / 2];
+  float dv[kHsDq / 2][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) wr[r] = ld4(w4 + 12 * k4 + 4 * r);
+#pragma unroll
+  for (int i = 0; i < kHsDq / 2; ++i) {
+    const int b = s0 + h + 2 * i, bc = b < B ? b : s0;   // (rows past B read row s0 and store nothing)
+    xr[i] = ld4(a4 + (size_t)bc * 512 + 4 * k4);
+#pragma unroll
+    for (int n = 0; n < 3; ++n) dv[i][n] = dq[(size_t)bc * 3 + n];
+  }
+  const float wv[12] = {wr[0][0], wr[0][1], wr[0][2], wr[0][3], wr[1][0], wr[1][1], wr[1][2], wr[1][3],
+                        wr[2][0], wr[2][1], wr[2][2], wr[2][3]};   // W4[4 k4 + e][n] at 3 e + n
+#pragma unroll
+  for (int i = 0; i < kHsDq / 2; ++i) {
+    const int b = s0 + h + 2 * i;
+    if (b < B) {
+      f32x4 d;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        d[e] = xr[i][e] > 0.0f ? fmaf(wv[3 * e + 2], dv[i][2], fmaf(wv[3 * e + 1], dv[i][1], __fmul_rn(wv[3 * e], dv[i][0]))) : 0.0f;
+      *reinterpret_cast<f32x4*>(dz4 + (size_t)b * 512 + 4 * k4) = d;
+    }
+  }
+}
+
 // clip_by_norm sums of squares: segment j of variable v = elements [j S, min(n_v, (j + 1) S)), S = kNormSeg = 2048;
 // thread t chains t = fmaf(x, x, t) over its elements j S + 4 t .. + 3, then j S + 1024 + 4 t .. + 3 (x = g * scale);
 // wave xor butterfly (32, 16, .., 1); then ((w0 + w1) + w2) + w3 -> partial j.  Norm_v from its partials in k_update32.
@@ -893,6 +930,22 @@ Fc2Args f32_fc2_args(qlx_model* m, int B) {
   return a;
 }
 
+// dW3 + db3 and dz3 tiles in one grid, dW4 / db4 / loss (the side: SideFc2 or SideFc2Dq) as its leading blocks
+template <class Side>
+static void f32_fc1_bwd(qlx_model* m, int B, const Side& S, hipStream_t s) {
+  F32Net& w = *m->fp32;
+  float* G = m->d_grads;
+  const float* p = m->d_params;
+  PFc1WgradS Pw{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), w.fa3, w.fdz4, G + var_offset(6), G + var_offset(7), B};
+  PFc1DgradS Pd{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), w.fdz4, p + var_offset(6), w.fa3, w.fdz3, B};
+  if (bg_rows(m)) {   // conv3's background-row dz3 sums (the compacted conv3 weight gradient)
+    Pd.pbg = w.fpbg3;
+    Pd.bg = w.fbg3;
+    Pd.bg_ld = w.fneed_ld;
+  }
+  launch_pair(m, Pw, Pd, S, "f32_fc1_bwd", 2.0 * 2.0 * B * 512 * 3136, s);   // (3 blocks per CU: 72.8 vs 61.8 us, w23)
+}
+
 void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                         const float* weights, float* td_abs) {
   F32Net& w = *m->fp32;
@@ -900,7 +953,6 @@ void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float
   w.dense_partials = false;   // partials of an earlier gradient (an update that threw before its Adam)
   f32_grad_workspace(m, B);
   float* G = m->d_grads;
-  const float* p = m->d_params;
   float *gs = m->w.gs, *hs = m->w.hs;
   {
     ProfScope ps(m->prof, "f32_head", s);
@@ -914,17 +966,24 @@ void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float
     a.dz4_out = w.fdz4;
     f32_head(3, a, B, s);
   }
-  {  // dW3 + db3 and dz3 tiles in one grid, dW4 / db4 / loss as its leading blocks
-    PFc1WgradS Pw{grid(3136, PFc1WgradS::BM, 512, PFc1WgradS::BN, 1), w.fa3, w.fdz4, G + var_offset(6), G + var_offset(7), B};
-    PFc1DgradS Pd{grid(B, PFc1DgradS::BM, 3136, PFc1DgradS::BN, 1), w.fdz4, p + var_offset(6), w.fa3, w.fdz3, B};
-    if (bg_rows(m)) {   // conv3's background-row dz3 sums (the compacted conv3 weight gradient)
-      Pd.pbg = w.fpbg3;
-      Pd.bg = w.fbg3;
-      Pd.bg_ld = w.fneed_ld;
-    }
-    SideFc2 S{w.fa4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev};
-    launch_pair(m, Pw, Pd, S, "f32_fc1_bwd", 2.0 * 2.0 * B * 512 * 3136, s);   // (3 blocks per CU: 72.8 vs 61.8 us, w23)
+  f32_fc1_bwd(m, B, SideFc2{w.fa4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev}, s);
+}
+
+// the same for a caller's dq [B][3] in place of the Huber head: k_head32_dq, then the fc1 backward with SideFc2Dq
+void f32_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s) {
+  F32Net& w = *m->fp32;
+  QLX_CHECK(B <= w.fchunk && B == m->last_batch, QLX_E_STATE, "f32 backward: batch must follow its forward");
+  w.dense_partials = false;
+  f32_grad_workspace(m, B);
+  float* G = m->d_grads;
+  {
+    ProfScope ps(m->prof, "f32_head_dq", s);
+    hipLaunchKernelGGL(k_head32_dq, dim3((B + kHsDq - 1) / kHsDq), dim3(256), 0, s, (const float*)w.fa4,
+                       (const float*)(m->d_params + var_offset(8)), dq, B, w.fdz4);
+    QLX_HIP(hipGetLastError());
+    debug_sync(s, "k_head32_dq");
   }
+  f32_fc1_bwd(m, B, SideFc2Dq{w.fa4, nullptr, nullptr, nullptr, B, G + var_offset(8), G + var_offset(9), m->w.loss, dq}, s);
 }
 
 static void seg_tables(int* seg_first, int64_t* off) {

@@ -1796,7 +1796,10 @@ using PConv2DgradP = PConv2DgradPx<64, 64, 2, 2>;
 // all-ones row 512 gives db4 and the loss sum, fmaf(1, v, s) = s + v).  Per HB samples the block's four waves load
 // the tile's a4 columns and [dq | h] into LDS with every load in flight at once (40 KB),
 // then wave 0 runs the chain from LDS: two memory latencies per launch instead of one per few MFMAs.
-struct SideFc2 {
+// DQ (model_backward_dq): the [dq | h] rows are the caller's dq [B][3] and h = 0 (the loss word it writes is unused); the
+// chains are the same, and a dq row that is 0 except at one action is the row the training form builds.
+template <bool DQ>
+struct SideFc2T {
   static constexpr int BLOCKS = 33;   // 512 rows of a4^T + the ones row
   __host__ __device__ int blocks() const { return BLOCKS; }
   static constexpr int HB = 512;      // samples per LDS pass (40 KB; 256 measured slower: 73.4 vs 71.2 us per fc1 backward,
@@ -1810,6 +1813,7 @@ struct SideFc2 {
   float* dw4;
   float* db4;
   float* loss;
+  const float* dq = nullptr;   // DQ: [B][3]
   __device__ void run(int t, float* lds) const {
     float* as = lds;              // [HB][16] a4 columns t*16 .. +15
     float* ds = lds + HB * 16;    // [HB][4]  dq0, dq1, dq2, h
@@ -1831,9 +1835,13 @@ struct SideFc2 {
         const int bl = tid + 256 * j, b = b0 + bl;
         f32x4 v = zero4();
         if (b < B) {
-          const int a = act[b];
-          const float gv = gs[b];
-          v = f32x4{a == 0 ? gv : 0.0f, a == 1 ? gv : 0.0f, a == 2 ? gv : 0.0f, hs[b]};
+          if constexpr (DQ) {
+            v = f32x4{dq[(size_t)b * 3], dq[(size_t)b * 3 + 1], dq[(size_t)b * 3 + 2], 0.0f};
+          } else {
+            const int a = act[b];
+            const float gv = gs[b];
+            v = f32x4{a == 0 ? gv : 0.0f, a == 1 ? gv : 0.0f, a == 2 ? gv : 0.0f, hs[b]};
+          }
         }
         *reinterpret_cast<f32x4*>(ds + bl * 4) = v;
       }
@@ -1860,6 +1868,8 @@ struct SideFc2 {
     }
   }
 };
+using SideFc2 = SideFc2T<false>;
+using SideFc2Dq = SideFc2T<true>;
 
 #ifndef QLX_Q32_POLICIES_ONLY   // (scripts/q32_host_check.hip replays the policies on the host without the kernels)
 // conv1 (8x8 stride 4, 4 -> 32 channels) from the u8 frames, one sample at a time per block with the sample's four

@@ -256,6 +256,30 @@ __global__ __launch_bounds__(256) void k_fc2_train(Fc2Args A, bf16* dz4) {
   *reinterpret_cast<bf16x8*>(dz4 + (size_t)b * 512 + lane * 8) = d;
 }
 
+// The dense-3 backward for a caller's dq [B][3] (model_backward_dq), one wave per sample like k_fc2_train and without
+// its Q chain: a4 as the head finishes it (fc2_load_a4), dz4[b][k] = (a4 > 0) ? the fmaf chain over n ascending of
+// W4[k][n] dq[b][n], first product rounded : 0.  A dq row that is 0 except at one action leaves the single rounded
+// product g * W4[k][a] of k_fc2_train (a product with 0 adds nothing).
+__global__ __launch_bounds__(256) void k_fc2_dq(Fc2Args A, const float* __restrict__ dq, bf16* dz4) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= A.B) return;
+  const float d0 = dq[(size_t)b * 3], d1 = dq[(size_t)b * 3 + 1], d2 = dq[(size_t)b * 3 + 2];
+  float4 wr[6];   // W4[8 lane + e][n] at 3 e + n: 24 consecutive floats
+#pragma unroll
+  for (int r = 0; r < 6; ++r) wr[r] = *reinterpret_cast<const float4*>(A.w4 + lane * 24 + 4 * r);
+  const bf16x8 v = fc2_load_a4(A, b, lane);
+  const float* wv = reinterpret_cast<const float*>(wr);
+  bf16x8 d;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
+    const float p0 = wv[3 * e] * d0;
+    d[e] = (bf16)((float)v[e] > 0.0f ? fmaf(wv[3 * e + 2], d2, fmaf(wv[3 * e + 1], d1, p0)) : 0.0f);
+  }
+  *reinterpret_cast<bf16x8*>(dz4 + (size_t)b * 512 + lane * 8) = d;
+}
+
 // dW4[k][a] = sum_b a4[b][k] g_b [a_b == a]: block j < 64 owns k = 8j .. 8j+7 and reads those 16 bytes of every
 // a4 row once; block 64 sums db4[a] = sum_b g_b [a_b == a] and the loss = sum_b h_b / B.  Per-thread strided
 // sums, an xor butterfly per wave, then the 4 wave sums in order: deterministic.  Runs as trailing blocks of
@@ -271,9 +295,14 @@ struct Fc2WgradArgs {
   float* loss;
   float* sq_w4;   // [64] square sums of each block's 24 dW4 values
   float* sq_b4;   // [1]
+  const float* dq = nullptr;   // DQ form: the caller's dq [B][3] in place of (actions, gs, hs)
 };
 constexpr int kFc2WgradBlocks = 65;
 
+// With A.dq (model_backward_dq; a flag of the launch, so that one k_fc1_bwd serves both forms): dW4[k][n] = sum_b
+// a4[b][k] dq[b][n] and db4[n] = sum_b dq[b][n] in the same per-thread, wave and block order, each product rounded
+// before it is added (as v below is); a dq row that is 0 except at one action adds what the training form adds.
+// h = 0: the loss word is written and unused.
 template <int NT>
 __device__ __forceinline__ void fc2_wgrad_block(const Fc2WgradArgs& A, int j, float* red /* LDS [NT / 64][24] + 24 */) {
   constexpr int NWV = NT / 64;
@@ -281,7 +310,29 @@ __device__ __forceinline__ void fc2_wgrad_block(const Fc2WgradArgs& A, int j, fl
   float s[24];
 #pragma unroll
   for (int i = 0; i < 24; ++i) s[i] = 0.0f;
-  if (j == 64) {
+  if (A.dq) {   // (uniform: a kernel argument)
+#pragma clang fp contract(off)
+    if (j == 64) {
+      for (int b = tid; b < A.B; b += NT) {
+#pragma unroll
+        for (int n = 0; n < 3; ++n) s[n] += A.dq[(size_t)b * 3 + n];
+      }
+    } else {
+      const int k0 = j * 8;
+      for (int b = tid; b < A.B; b += NT) {
+        const bf16x8 x = ld8(A.a4 + (size_t)b * 512 + k0);
+        const float d[3] = {A.dq[(size_t)b * 3], A.dq[(size_t)b * 3 + 1], A.dq[(size_t)b * 3 + 2]};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+#pragma unroll
+          for (int n = 0; n < 3; ++n) {
+            const float v = (float)x[e] * d[n];
+            s[e * 3 + n] += v;
+          }
+        }
+      }
+    }
+  } else if (j == 64) {
     for (int b = tid; b < A.B; b += NT) {
       const int a = A.actions[b];
       const float g = A.gs[b];
@@ -693,6 +744,30 @@ Fc2Args bf16_fc2_args(qlx_model* m, int B) {
   return a;
 }
 
+// fc1 backward in one launch of two independent GEMMs (both only read dz4 / a3), plus dW4 / db4 / loss (F; with F.dq
+// the form of those blocks that reads the caller's dq):
+//   dW3 = a3^T dz4 and db3 (row 3136 = the all-ones row; db3 follows dW3 [3136][512] in the flat gradient)
+//   dz3 = (dz4 W3^T) * (a3 > 0)
+static void bf16_fc1_bwd(qlx_model* m, int B, const Fc2WgradArgs& F, hipStream_t s) {
+  Bf16Net& w = *m->bf16;
+  float* G = m->d_grads;
+  ProfScope ps(m->prof, "fc1_bwd", s, 2.0 * 2.0 * B * 512 * 3136);
+  const auto Pd = bproblem(BOp{w.dz4, 512, B}, BOp{w.wb3, 512, 3136}, B, 3136, 512, 1, 128, 128,
+                           Epi4ReluMask{w.dz3, w.a3, 3136, kA3Ld});
+  // dW3 rows 0..3135 and db3 as row 3136 (a3's ones column), written straight into the flat gradient (b3 follows W3)
+  const auto Pw = bproblem(BOp{w.a3, kA3Ld, 3137}, BOp{w.dz4, 512, 512}, 3137, 512, B, 1, 128, 128,
+                           Epi4StoreF32{G + var_offset(6), 512, w.d_sqf + sq_first(6)}, 3136);
+  QLX_CHECK(Pw.tiles() == kFc1WgradTiles, QLX_E_STATE, "fc1 wgrad tiling changed: update kSqSlots");
+  bgemm_check<CfgFc1Wg>(Pw);
+  bgemm_check<CfgFc1Dg>(Pd);
+  fc1_bwd_map(w, Pw, Pd, kFc2WgradBlocks, s);
+  constexpr size_t lds_req = CfgFc1Wg::LDS;
+  static_assert(lds_req >= (kFc1BwdThreads / 64 + 1) * 24 * sizeof(float), "fc2 wgrad block scratch");
+  auto kern = k_fc1_bwd<Epi4StoreF32, Epi4ReluMask>;
+  set_lds_attr(kern, lds_req);
+  hipLaunchKernelGGL(kern, dim3(w.fc1bwd_grid), dim3(kFc1BwdThreads), lds_req, s, Pw, Pd, F, (const int*)w.d_fc1bwd_map);
+}
+
 // the head and dense part of the backward: Huber (+ dz4), dW4 / db4 / loss, dW3 / db3 and dz3
 void bf16_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float* y, float* loss_dev, hipStream_t s,
                          const float* weights, float* td_abs) {
@@ -711,30 +786,23 @@ void bf16_backward_dense(qlx_model* m, int B, const uint8_t* actions, const floa
     a.td_abs = td_abs;
     hipLaunchKernelGGL(k_fc2_train, dim3((B + 3) / 4), dim3(256), 0, s, a, w.dz4);
   }
-  // fc1 in one launch of two independent GEMMs (both only read dz4 / a3), plus dW4 / db4 / loss:
-  //   dW3 = a3^T dz4 and db3 (row 3136 = the all-ones row; db3 follows dW3 [3136][512] in the flat gradient)
-  //   dz3 = (dz4 W3^T) * (a3 > 0)
+  bf16_fc1_bwd(m, B, Fc2WgradArgs{w.a4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev,
+                                  w.d_sqf + sq_first(8), w.d_sqf + sq_first(9)}, s);
+  QLX_HIP(hipGetLastError());
+}
+
+// the same for a caller's dq [B][3] in place of the Huber head: k_fc2_dq, then the fc1 backward with the DQ dense-3 blocks
+void bf16_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s) {
+  Bf16Net& w = *m->bf16;
+  w.fused_valid = false;
+  float* G = m->d_grads;
   {
-    ProfScope ps(m->prof, "fc1_bwd", s, 2.0 * 2.0 * B * 512 * 3136);
-    const auto Pd = bproblem(BOp{w.dz4, 512, B}, BOp{w.wb3, 512, 3136}, B, 3136, 512, 1, 128, 128,
-                             Epi4ReluMask{w.dz3, w.a3, 3136, kA3Ld});
-    const Fc2WgradArgs F{w.a4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev,
-                         w.d_sqf + sq_first(8), w.d_sqf + sq_first(9)};
-    auto launch = [&](const auto& Pw, auto kern) {
-      QLX_CHECK(Pw.tiles() == kFc1WgradTiles, QLX_E_STATE, "fc1 wgrad tiling changed: update kSqSlots");
-      bgemm_check<CfgFc1Wg>(Pw);
-      bgemm_check<CfgFc1Dg>(Pd);
-      fc1_bwd_map(w, Pw, Pd, kFc2WgradBlocks, s);
-      constexpr size_t lds_req = CfgFc1Wg::LDS;
-      static_assert(lds_req >= (kFc1BwdThreads / 64 + 1) * 24 * sizeof(float), "fc2 wgrad block scratch");
-      set_lds_attr(kern, lds_req);
-      hipLaunchKernelGGL(kern, dim3(w.fc1bwd_grid), dim3(kFc1BwdThreads), lds_req, s, Pw, Pd, F, (const int*)w.d_fc1bwd_map);
-    };
-    // dW3 rows 0..3135 and db3 as row 3136 (a3's ones column), written straight into the flat gradient (b3 follows W3)
-    launch(bproblem(BOp{w.a3, kA3Ld, 3137}, BOp{w.dz4, 512, 512}, 3137, 512, B, 1, 128, 128,
-                    Epi4StoreF32{G + var_offset(6), 512, w.d_sqf + sq_first(6)}, 3136),
-           k_fc1_bwd<Epi4StoreF32, Epi4ReluMask>);
+    ProfScope ps(m->prof, "fc2_head_dq", s);
+    const Fc2Args a = bf16_fc2_args(m, B);
+    hipLaunchKernelGGL(k_fc2_dq, dim3((B + 3) / 4), dim3(256), 0, s, a, dq, w.dz4);
   }
+  bf16_fc1_bwd(m, B, Fc2WgradArgs{w.a4, nullptr, nullptr, nullptr, B, G + var_offset(8), G + var_offset(9), m->w.loss,
+                                  w.d_sqf + sq_first(8), w.d_sqf + sq_first(9), dq}, s);
   QLX_HIP(hipGetLastError());
 }
 

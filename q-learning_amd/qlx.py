@@ -147,6 +147,7 @@ class StatesDev(C.Structure):
 
 OBS_NHWC_SLOT = 0   # QLX_OBS_NHWC_SLOT: [n][84][84][4] (x, y, ring slot)
 OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 oldest
+STEP_GRADS_WRITTEN = 1   # QLX_STEP_GRADS_WRITTEN: qlx_model_step_dev after the caller wrote the gradient buffer
 
 _NP_OF_C = {C.c_uint64: "<u8", C.c_uint32: "<u4", C.c_float: "<f4"}
 # the same row as a numpy structured dtype (what metrics() returns an array of)
@@ -262,6 +263,10 @@ def lib():
         "qlx_model_q_dev": ([vp, C.POINTER(StatesDev), u32, vp, vp, vp], i32),
         "qlx_model_train_dev": ([vp, C.POINTER(StatesDev), vp, vp, vp, u32, vp, vp], i32),
         "qlx_model_copy_weights_dev": ([vp, vp], i32),
+        "qlx_model_forward_ticket": ([vp, C.POINTER(C.c_uint64)], i32),
+        "qlx_model_backward_dev": ([vp, C.POINTER(StatesDev), vp, u32, u64], i32),
+        "qlx_model_step_dev": ([vp, u32], i32),
+        "qlx_model_grads_dev": ([vp, C.POINTER(vp), C.POINTER(C.c_uint64)], i32),
         "qlx_params_default": ([vp], None),
         "qlx_learner_create": ([C.POINTER(Params), i32, C.POINTER(vp)], i32), "qlx_learner_destroy": ([vp], i32),
         "qlx_learner_vector_step": ([vp], i32), "qlx_learner_run": ([vp, u64], i32), "qlx_learner_sync": ([vp], i32),

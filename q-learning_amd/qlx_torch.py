@@ -2,8 +2,8 @@
 
 Everything here is plumbing over libqlx's device-pointer calls (include/qlx.h "Device-tensor env and replay calls",
 "Q-network on device tensors" and "Prioritized replay on device tensors"): observations, steps,
-pushes, sampled n-step batches, prioritized draws and priority writes, Q-values and whole updates go from kernel to tensor
-without touching the host.  No call synchronises; order against torch's work is
+pushes, sampled n-step batches, prioritized draws and priority writes, Q-values, whole updates and the gradients of a
+loss written in torch go from kernel to tensor without touching the host.  No call synchronises; order against torch's work is
 kept by stream waits (below).
 
 One HIP runtime per process.  torch's wheel carries a libamdhip64 of its own, libqlx.so asks for the system's by
@@ -144,6 +144,7 @@ class TorchEnv(_Streamed):
         self.n = self._env.n
         self._wrap_stream(_L.qlx_env_stream)
         self._sharing = weakref.WeakSet()   # replays that run on this env's stream: closed before it
+        self.writes = 0   # steps and resets so far: a TorchQNet backward checks that its forward's states still stand
 
     def close(self):
         for rb in list(getattr(self, "_sharing", ())):
@@ -167,6 +168,7 @@ class TorchEnv(_Streamed):
         a = _arg("actions", actions, self.device, torch.uint8, (self.n,))
         rewards = torch.empty(self.n, dtype=torch.float32, device=self.device)
         dones = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+        self.writes += 1
         with self._ordered(a, rewards, dones):
             qlx._check(_L.qlx_env_step_dev(self.h, a.data_ptr(), rewards.data_ptr(), dones.data_ptr()))
         return rewards, dones
@@ -174,6 +176,7 @@ class TorchEnv(_Streamed):
     def reset(self, mask=None):
         """reset every env, or those with mask[i] != 0 (uint8 device tensor [n])"""
         m = None if mask is None else _arg("mask", mask, self.device, torch.uint8, (self.n,))
+        self.writes += 1
         with self._ordered(m):
             qlx._check(_L.qlx_env_reset_dev(self.h, None if m is None else m.data_ptr()))
 
@@ -211,6 +214,7 @@ class TorchReplay(_Streamed):
             self._rb = qlx.ReplayBuffer(0, 0, handle=handle)
             self.h = handle
         self._wrap_stream(_L.qlx_replay_stream)
+        self.writes = 0   # pushes through add() so far (see TorchEnv.writes)
 
     def close(self):
         rb = getattr(self, "_rb", None)
@@ -228,6 +232,7 @@ class TorchReplay(_Streamed):
         a = _arg("actions", actions, self.device, torch.uint8, (self.n,))
         r = _arg("rewards", rewards, self.device, torch.float32, (self.n,))
         d = _arg("dones", dones, self.device, torch.uint8, (self.n,))
+        self.writes += 1
         # the push runs on the env's stream (it reads the env's ring); with a shared stream the two are one
         with env._ordered(a, r, d), self._ordered(a, r, d):
             qlx._check(_L.qlx_replay_push_dev(self.h, env.h, a.data_ptr(), r.data_ptr(), d.data_ptr()))
@@ -336,6 +341,38 @@ _WHICH = {"s": 0, "s_next": 1}
 _WANT = ("q", "actions", "max_q")
 
 
+class _Pass:
+    """one differentiable forward of a TorchQNet: its source, ticket and the write counts of what it read in place"""
+
+    def __init__(self, src, n, ins, env, replay, ticket):
+        self.src, self.n, self.ins, self.env, self.replay, self.ticket = src, n, ins, env, replay, ticket
+        self.writes = [(o, o.writes) for o in (env, replay) if o is not None]
+
+
+class _QFunction(torch.autograd.Function):
+    """q = Q(states) with the backward through the net's HIP kernels.  The states are bytes, so the graph hangs on `anchor`,
+    a scalar the net owns; the gradients go to the net's gradient buffer (TorchQNet.grads), not to a tensor."""
+
+    @staticmethod
+    def forward(ctx, anchor, net, source):
+        ctx.net = net
+        q, ctx.rec = net._forward_pass(*source)
+        return q
+
+    @staticmethod
+    def backward(ctx, grad_q):
+        ctx.net._backward_pass(ctx.rec, grad_q)
+        return None, None, None
+
+
+class _DeviceFloats:
+    """a device float32 array of libqlx as torch.as_tensor reads it (zero copy); keeps its owner alive"""
+
+    def __init__(self, ptr, count, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = dict(shape=(count,), typestr="<f4", data=(ptr, False), version=2, strides=None)
+
+
 class TorchQNet(_Streamed):
     """The Nature-DQN Q-net (fp32 or bf16 kernels) on device tensors (include/qlx.h "Q-network on device tensors",
     DESIGN.md §16): Q-values of, and one whole update (forward, Huber, backward, clip, Adam) on, states that are dense
@@ -344,7 +381,13 @@ class TorchQNet(_Streamed):
     TorchQNet(handle=h, device=d) wraps a model someone else owns (a learner's).  `reserve`: the largest n of any call.
 
     `layout` names the channel order the net sees, for every source: 'nchw_time' feeds the oldest frame as channel 0,
-    'nhwc_slot' ring slot j as channel j (what the learner and DeepQLearningModel feed).  Use one throughout."""
+    'nhwc_slot' ring slot j as channel j (what the learner and DeepQLearningModel feed).  Use one throughout.
+
+    A loss of one's own: net(states) - forward() - returns q [n, 3] with a grad_fn; loss.backward() runs
+    the net's backward kernels on dloss/dq and leaves the raw gradients of all ten variables in the net's gradient buffer
+    (grads()), step() clips and applies Adam.  One backward per step(): gradients are overwritten, not accumulated, and
+    the states an env or a replay source was read from must stand until the backward (no env.step / reset, no
+    replay.add in between).  Gradients with respect to the states do not exist."""
 
     def __init__(self, arch="f32", seed=2, device="cuda:0", env=None, reserve=MAX_STATES, handle=None):
         if arch not in _ARCHS:
@@ -365,12 +408,17 @@ class TorchQNet(_Streamed):
         qlx._check(_L.qlx_model_reserve(self.h, reserve))
         self.reserved = reserve
         self._wrap_stream(_L.qlx_model_stream)
+        self._anchor = torch.zeros((), dtype=torch.float32, device=self.device, requires_grad=True)
+        self._pending = False   # a backward has filled the gradient buffer and no step() / discard_grad() followed
+        self.reuse_activations = True   # False: every autograd backward runs the trunk forward again (ticket 0)
+        self._grads = None
 
     def close(self):
         m = getattr(self, "_m", None)
         if m is not None:
             m.close()
         self.h = None
+        self._grads = None
 
     @property
     def model(self):
@@ -455,10 +503,96 @@ class TorchQNet(_Streamed):
         w = None if weights is None else _arg("weights", weights, self.device, torch.float32, (B,))
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         td = torch.empty(B, dtype=torch.float32, device=self.device) if want_td_abs else None
+        self._pending = False   # (the update overwrites the gradient buffer)
         self._run(env, replay, ins + (a, t, w, loss, td),
                   lambda: _L.qlx_model_train_dev(self.h, C.byref(s), a.data_ptr(), t.data_ptr(), None if w is None else w.data_ptr(),
                                                  B, loss.data_ptr(), None if td is None else td.data_ptr()))
         return loss, td
+
+    # ---- a loss written in torch: forward with a grad_fn, backward into the gradient buffer, step ----
+
+    def forward(self, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time"):
+        """q float32 [n, 3] (n <= 4096) of the states, differentiable: q carries a grad_fn whose backward runs the net's
+        backward kernels.  Under torch.no_grad() this is q(want='q')."""
+        if not torch.is_grad_enabled():
+            return self.q(obs, env=env, replay=replay, indices=indices, which=which, layout=layout, want="q")
+        return _QFunction.apply(self._anchor, self, (obs, env, replay, indices, which, layout))
+
+    __call__ = forward
+
+    def forward_ticket(self):
+        """the ticket of the model's most recent forward pass (qlx_model_forward_ticket)"""
+        t = C.c_uint64()
+        qlx._check(_L.qlx_model_forward_ticket(self.h, C.byref(t)))
+        return t.value
+
+    def _forward_pass(self, obs, env, replay, indices, which, layout):
+        s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < n <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"n must be in 1..{min(MAX_BATCH, self.reserved)} for a differentiable forward")
+        q = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        self._run(env, replay, ins + (q,), lambda: _L.qlx_model_q_dev(self.h, C.byref(s), n, q.data_ptr(), None, None))
+        return q, _Pass(s, n, ins, env, replay, self.forward_ticket())
+
+    def _backward_pass(self, rec, grad_q):
+        if self.h is None:
+            raise RuntimeError("backward through a closed TorchQNet")
+        if self._pending:
+            raise RuntimeError("a second backward before step() or discard_grad(): gradients are not accumulated")
+        for o, count in rec.writes:
+            if o.h is None or o.writes != count:
+                raise RuntimeError(f"the {type(o).__name__} this forward read was stepped, reset, pushed to or closed before "
+                                   "the backward: its states are read in place")
+        self.backward_dq(grad_q, rec.ticket if self.reuse_activations else 0, _pass=rec)
+
+    def backward_dq(self, dq, ticket=0, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time",
+                    _pass=None):
+        """qlx_model_backward_dev: the raw gradients of sum(dq * Q(states)) into the gradient buffer, dq float32 [n, 3].
+        `ticket`: that of the forward over these very states (forward_ticket() right after it) to reuse its activations;
+        0 runs the trunk forward again.  The autograd path calls this; on its own it makes none of that path's checks."""
+        if _pass is None:
+            s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        else:
+            s, n, ins, env, replay = _pass.src, _pass.n, _pass.ins, _pass.env, _pass.replay
+        if not 0 < n <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"batch must be in 1..{min(MAX_BATCH, self.reserved)}")
+        if not isinstance(dq, torch.Tensor) or tuple(dq.shape) != (n, 3) or dq.device != self.device:
+            raise ValueError(f"dq must be a tensor of shape {(n, 3)} on {self.device}")
+        g = dq.detach().to(torch.float32).contiguous()
+        self._run(env, replay, ins + (g,), lambda: _L.qlx_model_backward_dev(self.h, C.byref(s), g.data_ptr(), n, ticket))
+        self._pending = True
+
+    def step(self, grads_written=False):
+        """clip_by_norm per variable + Adam on the gradient buffer, iterations + 1.  grads_written: the buffer was modified
+        through grads() since the backward (its clip norms are then taken from the buffer as it stands)."""
+        with self._ordered():
+            qlx._check(_L.qlx_model_step_dev(self.h, qlx.STEP_GRADS_WRITTEN if grads_written else 0))
+        self._pending = False
+
+    def discard_grad(self):
+        """drop the pending gradient, so that another backward may run without a step()"""
+        self._pending = False
+
+    def grads(self):
+        """the ten variables' gradients as float32 views of the gradient buffer, in the Keras shapes (qlx.VAR_SHAPES).
+        They show what the model's stream has written: read or write them between a backward and step(), and pass
+        step(grads_written=True) after a write.  Valid until close()."""
+        if self.h is None:
+            raise QlError("the object is closed")
+        if self._grads is None:
+            p, n = C.c_void_p(), C.c_uint64()
+            qlx._check(_L.qlx_model_grads_dev(self.h, C.byref(p), C.byref(n)))
+            flat = torch.as_tensor(_DeviceFloats(p.value, n.value, self._m), device=self.device)
+            views, off = [], 0
+            for shape in qlx.VAR_SHAPES:
+                k = 1
+                for d in shape:
+                    k *= d
+                views.append(flat[off:off + k].view(shape))
+                off += k
+            assert off == n.value
+            self._grads = tuple(views)
+        return self._grads
 
     def copy_weights_from(self, other):
         """the weights of `other` (a TorchQNet), as a target-network sync: no host synchronisation"""

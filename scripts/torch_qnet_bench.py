@@ -3,6 +3,9 @@
 
   python scripts/torch_qnet_bench.py act    [--envs 8192] [--arch f32|bf16]   q(env=) | q(env.obs()) | host predict
   python scripts/torch_qnet_bench.py update [--batch 1024] [--arch f32|bf16]  train(replay=) | batch + train(obs=) | host train
+  python scripts/torch_qnet_bench.py grad   [--batch 1024] [--arch f32|bf16]  a loss written in torch:
+      net(replay=) + torch Huber + backward() + step(), reusing the forward's activations and recomputing them, |
+      train(replay=); `--reps 0 --kernels N` only runs N of each for a kernel trace
   python scripts/torch_qnet_bench.py pack   [--n 1024]     the two staging kernels, to be run under a kernel trace:
       rocprofv3 --kernel-trace --stats -d DIR -- python scripts/torch_qnet_bench.py pack --n 8192
       (k_pack_states: the dense source of q(); k_pack_obs: the host call qlx_model_predict on the same states)
@@ -109,6 +112,44 @@ def update(args):
     env.close()
 
 
+def grad(args):
+    B = args.batch
+    env, rb = played_env(256, 40, rb=20_000)
+    net = QT.TorchQNet(args.arch, env=env, reserve=B)
+    lay = "nhwc_slot"
+    idx = rb.sample_indices(B, seed=3, update_idx=0)
+    a = rb.batch(idx, layout=lay, fields=("actions",)).actions
+    a_idx = a.long().unsqueeze(1)
+    y = torch.randn(B, device=DEV)
+
+    def own_loss():
+        q = net(replay=rb, indices=idx, layout=lay)
+        loss = torch.nn.functional.huber_loss(q.gather(1, a_idx).squeeze(1), y, delta=1.0)
+        loss.backward()
+        net.step()
+
+    def builtin():
+        net.train(a, y, replay=rb, indices=idx, layout=lay)
+
+    if args.kernels:   # for rocprofv3 --kernel-trace --stats: the same launches, untimed
+        for _ in range(args.kernels):
+            own_loss()
+            builtin()
+        net.sync()
+        env.close()
+        return
+    rows = []
+    for name, reuse in (("forward + Huber + backward + step", True), ("the same, activations recomputed", False)):
+        net.reuse_activations = reuse
+        rows.append((name, time_device(own_loss, args.reps, args.warmup)))
+    rows.append(("train(replay=, indices=)", time_device(builtin, args.reps, args.warmup)))
+    print(f"own loss, B = {B}, {args.arch}:")
+    for name, us in rows:
+        print(f"  {name:34s} {fmt(us)}")
+    net.sync()
+    env.close()
+
+
 def pack(args):
     n = args.n
     net = QT.TorchQNet("bf16", reserve=n)
@@ -126,15 +167,16 @@ def pack(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("act", "update", "pack"))
+    ap.add_argument("what", choices=("act", "update", "grad", "pack"))
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--arch", choices=("f32", "bf16"), default="f32")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kernels", type=int, default=0, help="grad: run this many of each path untimed (kernel trace)")
     args = ap.parse_args()
-    {"act": act, "update": update, "pack": pack}[args.what](args)
+    {"act": act, "update": update, "grad": grad, "pack": pack}[args.what](args)
 
 
 if __name__ == "__main__":
