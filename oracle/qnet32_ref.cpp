@@ -395,15 +395,20 @@ float qnet32_loss_backward(const QNet& q, const uint8_t* x8, const uint8_t* acti
   }
   // dense 3136 -> 512
   float* dW3 = g.g[6].data();
+  // The build's chain skips nothing and runs over whole 32-sample slabs, zeros past B (PFc1WgradT): a zero product is
+  // not always a no-op - +0 (a dead a3 unit times a dz4 that is not negative, or the padding) turns an accumulator that
+  // an underflowed negative product left at -0 into +0.  So every term is taken, and one 0 * 0 term stands for the padding.
+  const bool padded = B % 32 != 0;
 #pragma omp parallel for schedule(static)
   for (int k = 0; k < 3136; ++k) {
     float* row = dW3 + (size_t)k * 512;
     for (int b = 0; b < B; ++b) {
       const float v = a.a3[(size_t)b * 3136 + k];
-      if (v == 0.0f) continue;
       const float* d = dz4.data() + (size_t)b * 512;
       for (int n = 0; n < 512; ++n) row[n] = fma32(v, d[n], row[n]);
     }
+    if (padded)
+      for (int n = 0; n < 512; ++n) row[n] = fma32(0.0f, 0.0f, row[n]);
   }
   for (int n = 0; n < 512; ++n) {   // db3: four chains over b mod 4, ((C0 + C1) + C2) + C3
     float C[4] = {0.0f, 0.0f, 0.0f, 0.0f};

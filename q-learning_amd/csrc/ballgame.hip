@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void k_adam(float* w, float* m, float* vv, con
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < kParams; i += (int64_t)gridDim.x * blockDim.x) {
     int var = 0;
     while (var + 1 < kVars && i >= var_off(var + 1)) ++var;
-    const float gc = (g[i] * clipnorm) / fmaxf(norms[var], clipnorm);
+    const float gc = (g[i] * clipnorm) / clip_denom(norms[var], clipnorm);
     float mi = m[i], vi = vv[i], wi = w[i];
     mi += (gc - mi) * (1.0f - beta1);
     vi += (gc * gc - vi) * (1.0f - beta2);

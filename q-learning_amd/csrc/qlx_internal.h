@@ -145,6 +145,10 @@ __host__ __device__ inline uint64_t uniform_usize_single(RngStream& s, uint64_t 
   }
 }
 
+// tf.clip_by_norm's denominator max(norm, clipnorm) as the reference graph's Maximum and the oracle's std::max form it: a
+// NaN norm comes through (fmaxf would return clipnorm), so one NaN gradient element makes its whole variable NaN
+__host__ __device__ inline float clip_denom(float norm, float clipnorm) { return norm < clipnorm ? clipnorm : norm; }
+
 // ---- the linear per-step checksum (shared definition with the oracle) ----
 constexpr uint64_t kH1 = 0x9E3779B97F4A7C15ull, kH2 = 0xC2B2AE3D27D4EB4Full, kH3 = 0x100000001B3ull;
 

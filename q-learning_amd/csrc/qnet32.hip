@@ -498,7 +498,7 @@ struct AdamDense {
       for (int u = 0; u < 2; ++u) {
         if (qq[u] >= n4) continue;
         const int64_t i0 = o6 + qq[u] * 4;
-        const float denom = fmaxf(nrm[var_of(A, i0)], A.clipnorm);
+        const float denom = clip_denom(nrm[var_of(A, i0)], A.clipnorm);
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -513,7 +513,7 @@ struct AdamDense {
       }
       if (q0 == n4 || q0 + st == n4)   // the tail group, element by element
         for (int64_t i = o6 + n4 * 4; i < count; ++i) {
-          const float denom = fmaxf(nrm[var_of(A, i)], A.clipnorm);
+          const float denom = clip_denom(nrm[var_of(A, i)], A.clipnorm);
           float mi = A.m[i], vi = A.v[i];
           A.w[i] = adam32_elem(A.g[i], A.scale, A.clipnorm, denom, A.alpha, A.beta1, A.beta2, A.eps, mi, vi, A.w[i]);
           A.m[i] = mi;
@@ -524,7 +524,7 @@ struct AdamDense {
     for (int64_t q = q0; q <= n4; q += st) {
       const int64_t i0 = o6 + q * 4;
       if (q < n4) {
-        const float denom = fmaxf(nrm[var_of(A, i0)], A.clipnorm);
+        const float denom = clip_denom(nrm[var_of(A, i0)], A.clipnorm);
         const f32x4 g = ld4(A.g + i0), w = ld4(A.w + i0);
         f32x4 m = ld4(A.m + i0), v = ld4(A.v + i0), o;
 #pragma unroll
@@ -539,7 +539,7 @@ struct AdamDense {
         *reinterpret_cast<f32x4*>(A.v + i0) = v;
       } else {
         for (int64_t i = i0; i < count; ++i) {
-          const float denom = fmaxf(nrm[var_of(A, i)], A.clipnorm);
+          const float denom = clip_denom(nrm[var_of(A, i)], A.clipnorm);
           float mi = A.m[i], vi = A.v[i];
           A.w[i] = adam32_elem(A.g[i], A.scale, A.clipnorm, denom, A.alpha, A.beta1, A.beta2, A.eps, mi, vi, A.w[i]);
           A.m[i] = mi;
@@ -609,7 +609,7 @@ __device__ __forceinline__ void conv_adam_block(const Adam32Args& A, const NormA
     }
   }
   __syncthreads();
-  const float denom = fmaxf(nrm, A.clipnorm);
+  const float denom = clip_denom(nrm, A.clipnorm);
   if (e < n) {
     f32x4 out;
 #pragma unroll

@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs A) {
     if (qq < n4) {
       const int64_t i0 = qq * 4;
       const int var = adam_var_of(i0);
-      const float denom = fmaxf(nrm[var], A.clipnorm);
+      const float denom = clip_denom(nrm[var], A.clipnorm);
       f32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs A) {
     } else if (qq == n4) {   // the tail (b4's last elements), element by element
       for (int64_t i = n4 * 4; i < A.count; ++i) {
         const int var = adam_var_of(i);
-        const float denom = fmaxf(nrm[var], A.clipnorm);
+        const float denom = clip_denom(nrm[var], A.clipnorm);
         float mi = A.m[i], vi = A.v[i];
         const float wi = adam_elem(A.g[i], A.scale, A.clipnorm, denom, A.alpha, A.beta1, A.beta2, A.eps, mi, vi, A.w[i]);
         A.m[i] = mi;
