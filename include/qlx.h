@@ -660,6 +660,47 @@ int32_t qlx_model_step_dev(qlx_model* m, uint32_t flags);
  * valid for the model's lifetime */
 int32_t qlx_model_grads_dev(qlx_model* m, float** d_grads_out, uint64_t* count_out);
 
+/* ---- a wide output head: Z = a4 Wh + bh beside the model's own 512 -> 3 head ----
+ * A dense layer 512 -> width (1..QLX_HEAD_MAX_WIDTH, any value) on a4, the ReLU output of fc1, attached to one fp32 model:
+ * the outputs a dueling, categorical, quantile or bootstrapped agent needs from the same trunk, with forward, backward and
+ * optimizer step, so its loss stays a few lines of the caller's own.  The head owns Wh [512][width] (GlorotUniform, fan_in
+ * 512, fan_out width, from stream (seed, 10, 0, purpose 4) in element order) and bh [width] (zero), their Adam m and v, a
+ * gradient buffer (Wh, then bh), its own iteration count and clip-norm scratch; it runs on the model's stream with the
+ * model's hyperparameters (qlx_model_hparams).  The model's ten variables, its checkpoints, snapshots and learner do not
+ * know the head: qlx_head_get_var / _set_var are its persistence.
+ * A model has at most one head (a second create: QLX_E_STATE); a bf16 model has none (QLX_E_INVALID); qlx_model_destroy of
+ * a model with a live head fails with QLX_E_STATE.  Conventions of the `_dev` section above: arguments are checked on the
+ * host before any handle is read (QLX_E_INVALID, the field named), then everything is enqueued on the model's stream; no
+ * call but create, destroy and the host get / set synchronises, allocates or copies to the host; n is bounded by
+ * qlx_model_reserve (QLX_E_STATE above it, nothing launched); an index >= len or a bad state source behaves as in
+ * qlx_model_q_dev.  Arithmetic: every output is one fmaf chain in a fixed order, independent of the width,
+ * of the column's position and of the batch; a width-3 head holding W4 and b4 gives the model's own Q, gradients and update
+ * bit for bit. */
+#define QLX_HEAD_MAX_WIDTH 1024
+typedef struct qlx_head qlx_head;
+int32_t qlx_head_create(qlx_model* m, uint32_t width, uint64_t seed, qlx_head** out);
+int32_t qlx_head_destroy(qlx_head* h);
+int32_t qlx_head_width(qlx_head* h);          /* -1 for a null head */
+int64_t qlx_head_iterations(qlx_head* h);     /* -1 for a null head */
+/* host arrays, synchronise: var 0 Wh [512][width], 1 bh [width]; which 0 weights, 1 Adam m, 2 Adam v */
+int32_t qlx_head_get_var(qlx_head* h, int32_t var, int32_t which, float* out);
+int32_t qlx_head_set_var(qlx_head* h, int32_t var, int32_t which, const float* in);
+/* one trunk forward over n states (n <= the reserve), then both heads: d_z [n][width] and, unless NULL, d_q [n][3];
+ * advances the model's forward ticket like any forward */
+int32_t qlx_head_forward_dev(qlx_head* h, const qlx_states_dev* src, uint32_t n, float* d_z, float* d_q_or_null);
+/* raw gradients of sum dz * Z + sum dq * Q (d_dz [batch][width]; d_dq [batch][3] or NULL: no Q term): the ten model
+ * variables into the model's gradient buffer (W4 and b4 zero without dq), Wh and bh into the head's; both overwritten, not
+ * accumulated.  batch 1..4096; the ticket rules are qlx_model_backward_dev's. */
+int32_t qlx_head_backward_dev(qlx_head* h, const qlx_states_dev* src, const float* d_dz, const float* d_dq_or_null,
+                              uint32_t batch, uint64_t ticket);
+/* device pointer to the head's flat fp32 gradient buffer: Wh [512][width], then bh [width]; count = 513 * width */
+int32_t qlx_head_grads_dev(qlx_head* h, float** d_grads_out, uint64_t* count_out);
+/* qlx_model_step_dev steps the head as well (per-variable clip_by_norm and Adam, Wh and bh two variables with norms of
+ * their own, the head's iterations + 1) when the gradient in the buffers came from qlx_head_backward_dev; after any other
+ * backward, or a train call, it leaves the head alone. */
+/* weights only, between heads of equal width on one device; orders the streams as qlx_model_copy_weights_dev does */
+int32_t qlx_head_copy_weights_dev(qlx_head* dst, qlx_head* src);
+
 /* ---------------- Prioritized replay on device tensors (beyond the reference) ----------------
  * The learner's proportional prioritized replay (the sum tree above: same heap, same draws, same weights, same priority
  * write) kept inside a qlx_replay and driven one batch per call from device memory.  Conventions of "Device-tensor env and

@@ -116,6 +116,7 @@ void model_backward_conv(qlx_model* m, const uint8_t* const* table, int B, hipSt
                          float dense_scale) {
   m->f32 ? f32_backward_conv(m, table, B, s, fuse_update, dense_ready, dense_scale) : bf16_backward_conv(m, table, B, s);
   m->grads_filled = true;
+  m->head_grads = false;   // (qlx_head_backward_dev sets it again after this call)
 }
 
 void model_gradient_replaced(qlx_model* m) { m->f32 ? f32_gradient_replaced(m) : bf16_gradient_replaced(m); }
@@ -210,6 +211,7 @@ int32_t qlx_model_create(int32_t arch, uint64_t seed, int32_t device, qlx_model*
 int32_t qlx_model_destroy(qlx_model* m) {
   return guard([&] {
     if (!m) return;
+    QLX_CHECK(!m->head, QLX_E_STATE, "the model has a live head: qlx_head_destroy first");
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
     m->f32 ? f32_destroy(m) : bf16_destroy(m);
@@ -322,6 +324,7 @@ int32_t qlx_model_apply_gradient(qlx_model* m, const float* grads, float scale, 
     model_workspace(m, std::max(m->ws_batch, 1));   // (the norm partial buffers)
     QLX_HIP(hipMemcpyAsync(m->d_grads, grads, kNumParams * 4, hipMemcpyHostToDevice, s));
     m->grads_filled = true;
+    m->head_grads = false;
     model_gradient_replaced(m);
     model_norms(m, s, scale);
     model_adam(m, s, scale);

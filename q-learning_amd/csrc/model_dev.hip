@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_train_args(const uint8_t* actions, uint
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // everything about a state source that can be judged without reading a handle
-static void check_source(const qlx_states_dev* s) {
+void check_source(const qlx_states_dev* s) {
   QLX_CHECK(s, QLX_E_INVALID, "null src");
   QLX_CHECK(!(s->indices && !s->replay), QLX_E_INVALID, "src->indices without src->replay");
   QLX_CHECK(!(s->replay && !s->indices), QLX_E_INVALID, "src->replay without src->indices");
@@ -143,7 +143,7 @@ static void check_source(const qlx_states_dev* s) {
 }
 
 // the checks that read the handles: nothing is launched before all of them passed
-static void check_handles(const qlx_model* m, const qlx_states_dev& s, uint32_t n) {
+void check_handles(const qlx_model* m, const qlx_states_dev& s, uint32_t n) {
   QLX_CHECK(n <= m->dev_reserved, QLX_E_STATE, "n is above the reserved size: qlx_model_reserve first");
   QLX_CHECK(!s.replay || s.replay->device == m->device, QLX_E_INVALID, "src->replay and the model are on different devices");
   QLX_CHECK(!s.env || s.env->device == m->device, QLX_E_INVALID, "src->env and the model are on different devices");
@@ -151,7 +151,7 @@ static void check_handles(const qlx_model* m, const qlx_states_dev& s, uint32_t 
 }
 
 // m->w.table for the n states of `s`, enqueued on the model's stream
-static const uint8_t* const* states_table(qlx_model* m, const qlx_states_dev& s, uint32_t n) {
+const uint8_t* const* states_table(qlx_model* m, const qlx_states_dev& s, uint32_t n) {
   hipStream_t st = m->stream;
   const int time = s.layout == QLX_OBS_NCHW_TIME;
   if (s.obs) {
@@ -311,6 +311,7 @@ int32_t qlx_model_step_dev(qlx_model* m, uint32_t flags) {
     if (flags & QLX_STEP_GRADS_WRITTEN) model_gradient_replaced(m);
     model_norms(m, st, 1.0f);
     model_adam(m, st, 1.0f);
+    if (m->head && m->head_grads) head_step(m->head, st);   // the gradient came from qlx_head_backward_dev
   });
 }
 

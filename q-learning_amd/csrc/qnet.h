@@ -50,6 +50,8 @@ struct F32Net;    // qnet32.hip
 
 }  // namespace qlx
 
+struct qlx_head;   // head_wide.hip
+
 struct qlx_model {
   int device = 0;
   bool f32 = true;   // QLX_ARCH_NATURE_DQN: fp32 (the reference's arithmetic); QLX_ARCH_NATURE_DQN_BF16: bf16 MFMA operands
@@ -71,6 +73,10 @@ struct qlx_model {
   const uint8_t* const* fwd_table = nullptr;
   bool fwd_reusable = false;
   bool grads_filled = false;
+  // the attached wide head (head_wide.hip; at most one, fp32 models only) and whether the gradient now in the buffers came
+  // from qlx_head_backward_dev: only then does qlx_model_step_dev step the head as well (every other backward clears it)
+  qlx_head* head = nullptr;
+  bool head_grads = false;
   qlx::CommonWs w;
   qlx::Profiler* prof = nullptr;   // set by the learner while profiling
   // the _dev calls (model_dev.hip), all set by qlx_model_reserve: the largest n they may run, the sticky flag word
@@ -164,6 +170,13 @@ void model_adam(qlx_model* m, hipStream_t s, float scale);
 void model_state_get(qlx_model* m, float* out3, int64_t* iterations);
 void model_state_put(qlx_model* m, const float* in3, int64_t iterations);
 
+// the state-source checks and the frame table of the _dev calls (model_dev.hip), shared with the wide head's entry points
+void check_source(const qlx_states_dev* s);
+void check_handles(const qlx_model* m, const qlx_states_dev& s, uint32_t n);
+const uint8_t* const* states_table(qlx_model* m, const qlx_states_dev& s, uint32_t n);
+// clip_by_norm + Adam of the attached head on its own gradient buffer, its iterations + 1 (head_wide.hip)
+void head_step(qlx_head* h, hipStream_t s);
+
 // (Re)allocates m->ws for B samples: the common buffers, then whatever `layout` takes from the arena for the backend
 void ws_common(qlx_model* m, Arena& a, int B);
 template <class Layout>
@@ -225,6 +238,12 @@ void f32_gradient_replaced(qlx_model* m);
 void f32_norms(qlx_model* m, hipStream_t s, float scale);
 void f32_adam(qlx_model* m, hipStream_t s, float scale);
 void f32_last_activation(qlx_model* m, int layer, float* out);
+// the wide head's backward (head_wide.hip) in place of k_head32_dq: a4 of the last forward; the dz4 buffer of a backward
+// over B samples (the checks and the gradient workspace of f32_backward_dense_dq); then the fc1 backward with SideFc2Dq
+// on the dz4 the caller wrote there
+const float* f32_a4(qlx_model* m);
+float* f32_dz4_begin(qlx_model* m, int B);
+void f32_backward_dense_dz4(qlx_model* m, int B, const float* dq, hipStream_t s);
 // fractions of a batch's fp32 conv work the exact skips leave out (qnet32.hip k_frame_sparsity; synchronises s):
 // out = {conv1 forward zero steps, conv1 weight-gradient zero steps, conv2 background rows, conv3 background rows}
 // d_cnt: 4 device counters, h_cnt: their pinned host copy (both the caller's, allocated once)

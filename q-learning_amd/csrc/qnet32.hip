@@ -19,6 +19,7 @@
 #include "profiler.h"
 #include "qnet.h"
 #include "qnet32_kernels.h"
+#include "update32_dev.h"
 
 namespace qlx {
 
@@ -257,7 +258,6 @@ __global__ __launch_bounds__(256) void k_head32_dq(const float* __restrict__ a4,
 // wave xor butterfly (32, 16, .., 1); then ((w0 + w1) + w2) + w3 -> partial j.  Norm_v from its partials in k_update32.
 // (Measured and reverted: the last block to finish - a device-scope counter - reducing the partials to the ten norms, so
 // Adam loads ten values: Adam 16.3 -> 12.5 us, but the per-block release fence took the norm launch 6.2 -> 24.6 us.)
-constexpr int kNormSeg = 2048;
 constexpr int kNormSegMax = 832;   // partials per variable (13 per lane; W3 has 784)
 struct NormArgs {
   const float* g;
@@ -266,50 +266,6 @@ struct NormArgs {
   int seg_first[kNumVars + 1];
   int64_t off[kNumVars + 1];
 };
-// thread tl (0 .. 255) of segment j of variable v (elements off[v] ..): its fmaf chain over its eight elements, then its
-// wave's xor butterfly (every lane ends with the wave sum); segments past the variable's end chain zeros.
-// The loads are split from the chain so a caller can put every segment's loads in flight before the first add: variables
-// whose length is a multiple of 4 (all but b4) read through a buffer descriptor spanning the variable, elements past its
-// end reading as zeros - no per-lane branch around the loads (round 5: the branchy form serialised the five segment
-// rounds of a conv update block).
-struct NormLd {
-  f32x4 x[2];
-};
-__device__ __forceinline__ NormLd norm32_load(const float* gall, const int64_t* off, int v, int j, int tl, bool live) {
-  const int64_t n = off[v + 1] - off[v];
-  const int64_t b = (int64_t)j * kNormSeg;
-  const float* g = gall + off[v];   // variable offsets are multiples of 4 floats (16-byte loads)
-  NormLd L;
-  if (n % 4 == 0) {   // wave-uniform
-    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(g, live ? (uint32_t)(n * 4) : 0u);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) L.x[h] = buf_ld4(rs, (uint32_t)((b + 1024 * h + 4 * tl) * 4), 0);
-    return L;
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int64_t i = b + 1024 * h + 4 * tl;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) L.x[h][k] = live && i + k < n ? g[i + k] : 0.0f;   // zeros leave the chain unchanged
-  }
-  return L;
-}
-__device__ __forceinline__ float norm32_chain(const NormLd& L, float scale) {
-  float t = 0.0f;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float y = __fmul_rn(L.x[h][k], scale);
-      t = fmaf(y, y, t);
-    }
-  for (int o = 32; o > 0; o >>= 1) t = __fadd_rn(t, __shfl_xor(t, o));
-  return t;
-}
-__device__ __forceinline__ float norm32_lane(const float* gall, const int64_t* off, float scale, int v, int j, int tl) {
-  return norm32_chain(norm32_load(gall, off, v, j, tl, true), scale);
-}
-
 // Conv weight gradients from the sample-chunk partials, two levels: the chunks in groups of kWGroup (group q = chunks
 // [16 q, 16 q + 16)), S_q = chain over its chunks in order, dW = chain over q of S_q (each chain t = 0; t = t + x).
 // Segment 0 conv3 [577][64], 1 conv2 [513][64], 2 conv1 [257][32], rows in HWIO order, the last row of each the bias.
@@ -407,15 +363,6 @@ struct Adam32Args {
   float* norms;
   float scale, alpha, beta1, beta2, eps, clipnorm;
 };
-
-// tf.clip_by_norm + ResourceApplyAdam per element, explicit roundings in the oracle's order
-__device__ __forceinline__ float adam32_elem(float g, float scale, float clipnorm, float denom, float alpha, float beta1,
-                                             float beta2, float eps, float& m, float& v, float w) {
-  const float gc = __fmul_rn(__fmul_rn(g, scale), clipnorm) / denom;
-  m = __fadd_rn(m, __fmul_rn(__fsub_rn(gc, m), 1.0f - beta1));
-  v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(gc, gc), v), 1.0f - beta2));
-  return __fsub_rn(w, __fmul_rn(m, alpha) / __fadd_rn(sqrtf(v), eps));
-}
 
 // the variable of flat element i (branch-free: the number of variable starts at or below i, minus one)
 __device__ __forceinline__ int var_of(const Adam32Args& A, int64_t i) {
@@ -969,21 +916,35 @@ void f32_backward_dense(qlx_model* m, int B, const uint8_t* actions, const float
   f32_fc1_bwd(m, B, SideFc2{w.fa4, actions, gs, hs, B, G + var_offset(8), G + var_offset(9), loss_dev}, s);
 }
 
-// the same for a caller's dq [B][3] in place of the Huber head: k_head32_dq, then the fc1 backward with SideFc2Dq
-void f32_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s) {
+const float* f32_a4(qlx_model* m) { return m->fp32->fa4; }
+
+// the dz4 buffer of a backward over B samples that follows its forward (the gradient workspace grows here, once)
+float* f32_dz4_begin(qlx_model* m, int B) {
   F32Net& w = *m->fp32;
   QLX_CHECK(B <= w.fchunk && B == m->last_batch, QLX_E_STATE, "f32 backward: batch must follow its forward");
   w.dense_partials = false;
   f32_grad_workspace(m, B);
+  return w.fdz4;
+}
+
+// the fc1 backward on the dz4 written there, dW4 / db4 from dq [B][3] as its leading blocks (SideFc2Dq)
+void f32_backward_dense_dz4(qlx_model* m, int B, const float* dq, hipStream_t s) {
+  F32Net& w = *m->fp32;
   float* G = m->d_grads;
+  f32_fc1_bwd(m, B, SideFc2Dq{w.fa4, nullptr, nullptr, nullptr, B, G + var_offset(8), G + var_offset(9), m->w.loss, dq}, s);
+}
+
+// the same for a caller's dq [B][3] in place of the Huber head: k_head32_dq, then the fc1 backward with SideFc2Dq
+void f32_backward_dense_dq(qlx_model* m, int B, const float* dq, hipStream_t s) {
+  float* dz4 = f32_dz4_begin(m, B);
   {
     ProfScope ps(m->prof, "f32_head_dq", s);
-    hipLaunchKernelGGL(k_head32_dq, dim3((B + kHsDq - 1) / kHsDq), dim3(256), 0, s, (const float*)w.fa4,
-                       (const float*)(m->d_params + var_offset(8)), dq, B, w.fdz4);
+    hipLaunchKernelGGL(k_head32_dq, dim3((B + kHsDq - 1) / kHsDq), dim3(256), 0, s, f32_a4(m),
+                       (const float*)(m->d_params + var_offset(8)), dq, B, dz4);
     QLX_HIP(hipGetLastError());
     debug_sync(s, "k_head32_dq");
   }
-  f32_fc1_bwd(m, B, SideFc2Dq{w.fa4, nullptr, nullptr, nullptr, B, G + var_offset(8), G + var_offset(9), m->w.loss, dq}, s);
+  f32_backward_dense_dz4(m, B, dq, s);
 }
 
 static void seg_tables(int* seg_first, int64_t* off) {

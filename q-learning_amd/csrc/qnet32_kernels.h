@@ -1871,7 +1871,9 @@ struct SideFc2T {
 using SideFc2 = SideFc2T<false>;
 using SideFc2Dq = SideFc2T<true>;
 
-#ifndef QLX_Q32_POLICIES_ONLY   // (scripts/q32_host_check.hip replays the policies on the host without the kernels)
+// (scripts/q32_host_check.hip replays the policies on the host without the kernels; QLX_Q32_NO_KERNELS: a second translation
+// unit - head_wide.hip - takes the device helpers above and leaves the conv1 kernels, one of them no template, to qnet32.hip)
+#if !defined(QLX_Q32_POLICIES_ONLY) && !defined(QLX_Q32_NO_KERNELS)
 // conv1 (8x8 stride 4, 4 -> 32 channels) from the u8 frames, one sample at a time per block with the sample's four
 // frames staged in LDS while the next sample's frames are in flight in registers.
 // LDS frame layout (rows): slot c, image row x, dword y / 4 holds pixels (x, y .. y + 3) at dword c * 1776 + x * 21 + y / 4.

@@ -148,6 +148,8 @@ class StatesDev(C.Structure):
 OBS_NHWC_SLOT = 0   # QLX_OBS_NHWC_SLOT: [n][84][84][4] (x, y, ring slot)
 OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 oldest
 STEP_GRADS_WRITTEN = 1   # QLX_STEP_GRADS_WRITTEN: qlx_model_step_dev after the caller wrote the gradient buffer
+HEAD_IN = 512            # the wide head's input: a4, the ReLU output of fc1
+HEAD_MAX_WIDTH = 1024    # QLX_HEAD_MAX_WIDTH
 
 _NP_OF_C = {C.c_uint64: "<u8", C.c_uint32: "<u4", C.c_float: "<f4"}
 # the same row as a numpy structured dtype (what metrics() returns an array of)
@@ -267,6 +269,14 @@ def lib():
         "qlx_model_backward_dev": ([vp, C.POINTER(StatesDev), vp, u32, u64], i32),
         "qlx_model_step_dev": ([vp, u32], i32),
         "qlx_model_grads_dev": ([vp, C.POINTER(vp), C.POINTER(C.c_uint64)], i32),
+        # the wide output head (WideHead; qlx_torch.TorchQNet.attach_head)
+        "qlx_head_create": ([vp, u32, u64, C.POINTER(vp)], i32), "qlx_head_destroy": ([vp], i32),
+        "qlx_head_width": ([vp], i32), "qlx_head_iterations": ([vp], C.c_int64),
+        "qlx_head_get_var": ([vp, i32, i32, vp], i32), "qlx_head_set_var": ([vp, i32, i32, vp], i32),
+        "qlx_head_forward_dev": ([vp, C.POINTER(StatesDev), u32, vp, vp], i32),
+        "qlx_head_backward_dev": ([vp, C.POINTER(StatesDev), vp, vp, u32, u64], i32),
+        "qlx_head_grads_dev": ([vp, C.POINTER(vp), C.POINTER(C.c_uint64)], i32),
+        "qlx_head_copy_weights_dev": ([vp, vp], i32),
         "qlx_params_default": ([vp], None),
         "qlx_learner_create": ([C.POINTER(Params), i32, C.POINTER(vp)], i32), "qlx_learner_destroy": ([vp], i32),
         "qlx_learner_vector_step": ([vp], i32), "qlx_learner_run": ([vp, u64], i32), "qlx_learner_sync": ([vp], i32),
@@ -588,6 +598,9 @@ class DeepQLearningModel:
         self.h = handle
 
     def close(self):
+        head = getattr(self, "_head", None)
+        if head is not None:   # (a model with a live head cannot be destroyed)
+            head.close()
         if getattr(self, "_owned", False) and getattr(self, "h", None):
             lib().qlx_model_destroy(self.h)
         self.h = None
@@ -673,6 +686,62 @@ class DeepQLearningModel:
 
     def read_checkpoint(self, path):
         _check(lib().qlx_model_read_checkpoint(self.h, path.encode()))
+
+
+class WideHead:
+    """qlx_head: a dense layer 512 -> width (1..HEAD_MAX_WIDTH) on a4 of one fp32 DeepQLearningModel, beside its own
+    512 -> 3 head.  Variables: 0 = Wh [512, width], 1 = bh [width]; which 0 weights, 1 Adam m, 2 Adam v.
+    The forward, backward and gradient calls take device pointers (qlx_torch.TorchQNet drives them); the model's
+    step_dev steps the head too after a backward through it.  Closed with its model (or before it)."""
+
+    def __init__(self, model, width, seed=0):
+        h = C.c_void_p()
+        _check(lib().qlx_head_create(model.h, width, seed, C.byref(h)))
+        self.h = h.value
+        self.model = model
+        self.width = int(width)
+        model._head = self
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().qlx_head_destroy(self.h)
+            if getattr(self.model, "_head", None) is self:
+                self.model._head = None
+        self.h = None
+
+    __del__ = close
+
+    def _shape(self, var):
+        return (HEAD_IN, self.width) if var == 0 else (self.width,)
+
+    def get(self, var, which=0):
+        out = np.zeros(self._shape(var) if var in (0, 1) else 1, np.float32)
+        _check(lib().qlx_head_get_var(self.h, var, which, _p(out)))
+        return out
+
+    def set(self, var, arr, which=0):
+        a = np.ascontiguousarray(arr, dtype=np.float32)
+        if var in (0, 1) and a.size != int(np.prod(self._shape(var))):
+            raise ValueError(f"variable {var} of a width-{self.width} head has shape {self._shape(var)}")
+        _check(lib().qlx_head_set_var(self.h, var, which, _p(a)))
+
+    def iterations(self):
+        return int(lib().qlx_head_iterations(self.h))
+
+    def forward_dev(self, src, n, d_z, d_q=None):
+        _check(lib().qlx_head_forward_dev(self.h, C.byref(src), n, d_z, d_q))
+
+    def backward_dev(self, src, d_dz, d_dq, batch, ticket=0):
+        _check(lib().qlx_head_backward_dev(self.h, C.byref(src), d_dz, d_dq, batch, ticket))
+
+    def grads_dev(self):
+        """(device pointer, count) of the head's flat gradient buffer: Wh [512, width], then bh [width]"""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        _check(lib().qlx_head_grads_dev(self.h, C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
+    def copy_weights_dev(self, other):
+        _check(lib().qlx_head_copy_weights_dev(self.h, other.h))
 
 
 class Evaluator:

@@ -365,6 +365,23 @@ class _QFunction(torch.autograd.Function):
         return None, None, None
 
 
+class _QZFunction(torch.autograd.Function):
+    """(q, z) = (Q(states), the attached wide head's Z(states)) from one trunk forward, with one backward through the net's
+    kernels for both: a missing grad for q passes no dq at all, a missing grad for z passes zeros."""
+
+    @staticmethod
+    def forward(ctx, anchor, net, source):
+        ctx.net = net
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
+        q, z, ctx.rec = net._forward_pass_head(*source)
+        return q, z
+
+    @staticmethod
+    def backward(ctx, grad_q, grad_z):
+        ctx.net._backward_pass(ctx.rec, grad_q, grad_z, head=True)
+        return None, None, None
+
+
 class _DeviceFloats:
     """a device float32 array of libqlx as torch.as_tensor reads it (zero copy); keeps its owner alive"""
 
@@ -412,13 +429,87 @@ class TorchQNet(_Streamed):
         self._pending = False   # a backward has filled the gradient buffer and no step() / discard_grad() followed
         self.reuse_activations = True   # False: every autograd backward runs the trunk forward again (ticket 0)
         self._grads = None
+        self._head = None         # the attached qlx.WideHead (attach_head)
+        self._head_grads = None
 
     def close(self):
+        head = getattr(self, "_head", None)
+        if head is not None:   # before its model: a model with a live head cannot be destroyed
+            head.close()
+        self._head = self._head_grads = None
         m = getattr(self, "_m", None)
         if m is not None:
             m.close()
         self.h = None
         self._grads = None
+
+    # ---- a wide output head beside the 512 -> 3 one ----
+
+    def attach_head(self, width, seed=0):
+        """Attach a dense layer 512 -> width (1..1024) on the trunk's a4 (qlx.WideHead; fp32 nets only, one per net) and
+        return it.  forward(..., head=True) then returns (q, z), z float32 [n, width]; a loss of either or both
+        backpropagates through one backward; step() steps the head's Wh and bh with the ten variables, each clipped by a
+        norm of its own; head_grads() shows their gradients.  The head's get / set are its persistence."""
+        if self.h is None:
+            raise QlError("the object is closed")
+        self._head = qlx.WideHead(self._m, width, seed)
+        self._head_grads = None
+        return self._head
+
+    @property
+    def head(self):
+        return self._head
+
+    def _need_head(self):
+        if self._head is None or self._head.h is None:
+            raise RuntimeError("head=True needs an attached head: attach_head(width) first")
+        return self._head
+
+    def _forward_head(self, n, s, ins, env, replay, want_q=True):
+        head = self._need_head()
+        z = torch.empty((n, head.width), dtype=torch.float32, device=self.device)
+        q = torch.empty((n, 3), dtype=torch.float32, device=self.device) if want_q else None
+        self._run(env, replay, ins + (z, q),
+                  lambda: _L.qlx_head_forward_dev(head.h, C.byref(s), n, z.data_ptr(), None if q is None else q.data_ptr()))
+        return q, z
+
+    def _forward_pass_head(self, obs, env, replay, indices, which, layout):
+        s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < n <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"n must be in 1..{min(MAX_BATCH, self.reserved)} for a differentiable forward")
+        q, z = self._forward_head(n, s, ins, env, replay)
+        return q, z, _Pass(s, n, ins, env, replay, self.forward_ticket())
+
+    def backward_dz(self, dz, dq=None, ticket=0, obs=None, *, env=None, replay=None, indices=None, which="s",
+                    layout="nchw_time", _pass=None):
+        """qlx_head_backward_dev: the raw gradients of sum(dz * Z) + sum(dq * Q) into the two gradient buffers, dz float32
+        [n, width], dq float32 [n, 3] or None (no Q term: dW4 and db4 come out zero).  `ticket` as in backward_dq."""
+        head = self._need_head()
+        if _pass is None:
+            s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        else:
+            s, n, ins, env, replay = _pass.src, _pass.n, _pass.ins, _pass.env, _pass.replay
+        if not 0 < n <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"batch must be in 1..{min(MAX_BATCH, self.reserved)}")
+        for name, t, shape in (("dz", dz, (n, head.width)), ("dq", dq, (n, 3))):
+            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != self.device):
+                raise ValueError(f"{name} must be a tensor of shape {shape} on {self.device}")
+        gz = dz.detach().to(torch.float32).contiguous()
+        gq = None if dq is None else dq.detach().to(torch.float32).contiguous()
+        self._run(env, replay, ins + (gz, gq),
+                  lambda: _L.qlx_head_backward_dev(head.h, C.byref(s), gz.data_ptr(), None if gq is None else gq.data_ptr(),
+                                                   n, ticket))
+        self._pending = True
+
+    def head_grads(self):
+        """(dWh [512, width], dbh [width]) as float32 views of the head's gradient buffer; as grads()"""
+        head = self._need_head()
+        if self._head_grads is None:
+            ptr, n = head.grads_dev()
+            flat = torch.as_tensor(_DeviceFloats(ptr, n, head), device=self.device)
+            k = qlx.HEAD_IN * head.width
+            self._head_grads = (flat[:k].view(qlx.HEAD_IN, head.width), flat[k:])
+        return self._head_grads
 
     @property
     def model(self):
@@ -511,9 +602,19 @@ class TorchQNet(_Streamed):
 
     # ---- a loss written in torch: forward with a grad_fn, backward into the gradient buffer, step ----
 
-    def forward(self, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time"):
+    def forward(self, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time", head=False):
         """q float32 [n, 3] (n <= 4096) of the states, differentiable: q carries a grad_fn whose backward runs the net's
-        backward kernels.  Under torch.no_grad() this is q(want='q')."""
+        backward kernels.  Under torch.no_grad() this is q(want='q').  head=True (after attach_head): (q, z) with z float32
+        [n, width] the wide head's output, from one trunk forward and with one backward for both; under torch.no_grad() the
+        plain forward of up to `reserve` states."""
+        if head:
+            self._need_head()
+            if not torch.is_grad_enabled():
+                s, n, ins = self._source(obs, env, replay, indices, which, layout)
+                if not 0 < n <= self.reserved:
+                    raise ValueError(f"n must be in 1..{self.reserved} (the reserve)")
+                return self._forward_head(n, s, ins, env, replay)
+            return _QZFunction.apply(self._anchor, self, (obs, env, replay, indices, which, layout))
         if not torch.is_grad_enabled():
             return self.q(obs, env=env, replay=replay, indices=indices, which=which, layout=layout, want="q")
         return _QFunction.apply(self._anchor, self, (obs, env, replay, indices, which, layout))
@@ -534,7 +635,7 @@ class TorchQNet(_Streamed):
         self._run(env, replay, ins + (q,), lambda: _L.qlx_model_q_dev(self.h, C.byref(s), n, q.data_ptr(), None, None))
         return q, _Pass(s, n, ins, env, replay, self.forward_ticket())
 
-    def _backward_pass(self, rec, grad_q):
+    def _backward_pass(self, rec, grad_q, grad_z=None, head=False):
         if self.h is None:
             raise RuntimeError("backward through a closed TorchQNet")
         if self._pending:
@@ -543,7 +644,13 @@ class TorchQNet(_Streamed):
             if o.h is None or o.writes != count:
                 raise RuntimeError(f"the {type(o).__name__} this forward read was stepped, reset, pushed to or closed before "
                                    "the backward: its states are read in place")
-        self.backward_dq(grad_q, rec.ticket if self.reuse_activations else 0, _pass=rec)
+        ticket = rec.ticket if self.reuse_activations else 0
+        if head:
+            if grad_z is None:
+                grad_z = torch.zeros((rec.n, self._need_head().width), dtype=torch.float32, device=self.device)
+            self.backward_dz(grad_z, grad_q, ticket, _pass=rec)
+        else:
+            self.backward_dq(grad_q, ticket, _pass=rec)
 
     def backward_dq(self, dq, ticket=0, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time",
                     _pass=None):
@@ -564,7 +671,8 @@ class TorchQNet(_Streamed):
 
     def step(self, grads_written=False):
         """clip_by_norm per variable + Adam on the gradient buffer, iterations + 1.  grads_written: the buffer was modified
-        through grads() since the backward (its clip norms are then taken from the buffer as it stands)."""
+        through grads() since the backward (its clip norms are then taken from the buffer as it stands).  After a backward
+        through an attached head (forward(head=True), backward_dz) the head's Wh and bh are stepped as well."""
         with self._ordered():
             qlx._check(_L.qlx_model_step_dev(self.h, qlx.STEP_GRADS_WRITTEN if grads_written else 0))
         self._pending = False
@@ -600,8 +708,13 @@ class TorchQNet(_Streamed):
             raise ValueError(f"other must be a TorchQNet on {self.device}")
         if other.h is None:
             raise QlError("the object is closed")
+        mine, theirs = self._head, other._head
+        if mine is not None and theirs is not None and mine.width != theirs.width:
+            raise ValueError(f"the heads have different widths ({mine.width} and {theirs.width})")
         with self._ordered():
             qlx._check(_L.qlx_model_copy_weights_dev(self.h, other.h))
+            if mine is not None and theirs is not None:   # both nets have a head: it is part of the sync
+                qlx._check(_L.qlx_head_copy_weights_dev(mine.h, theirs.h))
 
     def sync(self):
         """wait for the model's stream; QlError, once, if a call since the last sync met an index >= len or an action >= 3"""

@@ -6,6 +6,9 @@
   python scripts/torch_qnet_bench.py grad   [--batch 1024] [--arch f32|bf16]  a loss written in torch:
       net(replay=) + torch Huber + backward() + step(), reusing the forward's activations and recomputing them, |
       train(replay=); `--reps 0 --kernels N` only runs N of each for a kernel trace
+  python scripts/torch_qnet_bench.py head   [--batch 1024] [--widths 4,153,600]   the wide output head:
+      net(replay=, head=True) + a loss in torch + backward() + step() per width, beside `grad`'s update without a head on
+      the same states; `--kernels N` only runs N of each width for a kernel trace (k_headw_fwd / _dz / _wgrad)
   python scripts/torch_qnet_bench.py pack   [--n 1024]     the two staging kernels, to be run under a kernel trace:
       rocprofv3 --kernel-trace --stats -d DIR -- python scripts/torch_qnet_bench.py pack --n 8192
       (k_pack_states: the dense source of q(); k_pack_obs: the host call qlx_model_predict on the same states)
@@ -150,6 +153,67 @@ def grad(args):
     env.close()
 
 
+def head_loss(width, q, z, a_idx, y, dist):
+    """the loss a head of this width is for, cheap enough that the kernels stay visible: 1 + 3 outputs are a dueling head
+    (Q = V + A - mean A, Huber TD), 3 N outputs a categorical one (cross-entropy of the taken action's N logits against a
+    fixed target distribution, the shape of C51's projected target)"""
+    if width == 4:
+        adv = z[:, 1:4]
+        qd = z[:, :1] + adv - adv.mean(dim=1, keepdim=True)
+        return torch.nn.functional.huber_loss(qd.gather(1, a_idx).squeeze(1), y, delta=1.0)
+    n = width // 3
+    logits = z[:, :3 * n].view(-1, 3, n).gather(1, a_idx.unsqueeze(2).expand(-1, 1, n)).squeeze(1)
+    return -(dist[:, :n] * torch.log_softmax(logits, dim=1)).sum(dim=1).mean()
+
+
+def head(args):
+    B = args.batch
+    widths = [int(w) for w in args.widths.split(",")]
+    env, rb = played_env(256, 40, rb=20_000)
+    lay = "nhwc_slot"
+    idx = rb.sample_indices(B, seed=3, update_idx=0)
+    a = rb.batch(idx, layout=lay, fields=("actions",)).actions
+    a_idx = a.long().unsqueeze(1)
+    y = torch.randn(B, device=DEV)
+    dist = torch.softmax(torch.randn(B, max(widths) // 3 + 1, device=DEV), dim=1)
+    plain = QT.TorchQNet("f32", env=env, reserve=B)
+
+    def no_head():   # `grad`'s update
+        q = plain(replay=rb, indices=idx, layout=lay)
+        torch.nn.functional.huber_loss(q.gather(1, a_idx).squeeze(1), y, delta=1.0).backward()
+        plain.step()
+
+    nets = {}
+    for w in widths:
+        nets[w] = QT.TorchQNet("f32", env=env, reserve=B)
+        nets[w].attach_head(w, seed=w)
+
+    def with_head(w):
+        net = nets[w]
+
+        def run():
+            q, z = net.forward(replay=rb, indices=idx, layout=lay, head=True)
+            head_loss(w, q, z, a_idx, y, dist).backward()
+            net.step()
+        return run
+
+    if args.kernels:   # for rocprofv3 --kernel-trace --stats: the same launches, untimed
+        for _ in range(args.kernels):
+            no_head()
+            for w in widths:
+                with_head(w)()
+    else:
+        base = time_device(no_head, args.reps, args.warmup)
+        print(f"wide head, B = {B}, f32 (forward + loss in torch + backward + step):")
+        print(f"  {'no head (grad)':24s} {fmt(base)}")
+        for w in widths:
+            us = time_device(with_head(w), args.reps, args.warmup)
+            print(f"  {'width ' + str(w):24s} {fmt(us)}   + {statistics.median(us) - statistics.median(base):.1f} us")
+    for net in [plain] + list(nets.values()):
+        net.sync()
+    env.close()
+
+
 def pack(args):
     n = args.n
     net = QT.TorchQNet("bf16", reserve=n)
@@ -167,16 +231,17 @@ def pack(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("act", "update", "grad", "pack"))
+    ap.add_argument("what", choices=("act", "update", "grad", "head", "pack"))
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--arch", choices=("f32", "bf16"), default="f32")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--kernels", type=int, default=0, help="grad: run this many of each path untimed (kernel trace)")
+    ap.add_argument("--widths", default="4,153,600", help="head: the head widths, comma separated")
+    ap.add_argument("--kernels", type=int, default=0, help="grad, head: run this many of each path untimed (kernel trace)")
     args = ap.parse_args()
-    {"act": act, "update": update, "grad": grad, "pack": pack}[args.what](args)
+    {"act": act, "update": update, "grad": grad, "head": head, "pack": pack}[args.what](args)
 
 
 if __name__ == "__main__":
