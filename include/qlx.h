@@ -91,6 +91,15 @@ int32_t qlx_env_step_dev(qlx_env* env, const uint8_t* d_actions, float* d_reward
 /* ToMultiDimArray::batch_to_multi_dim_array view of the current states: out[n][84][84][4] (x,y,slot). */
 int32_t qlx_env_obs(qlx_env* env, uint8_t* out);
 int32_t qlx_env_states(qlx_env* env, qlx_breakout_state* out /* [n_envs] */);
+/* Directed start states (the mirror of qlx_bg_env_set_states): copies in[n_envs] over the mechanics on the env's
+ * stream and zeroes the per-episode step counts.  The ring frames, the running checksums and the sticky flags stay
+ * as they are.  QLX_E_INVALID, with nothing written, if any state has finished > 1, next_slot > 3 or
+ * bricks >= 2^60.  Floats are taken as given, NaN and infinity included: every loop of the physics tick is bounded
+ * (at most 65 moves per tick and 65 probes per bisection, either exhaustion raising fault bit 4), so no state can
+ * hang a step. */
+int32_t qlx_env_set_states(qlx_env* env, const qlx_breakout_state* in /* [n_envs] */);
+/* Steps taken by each env in its current episode (what the learner compares with max_steps_per_episode). */
+int32_t qlx_env_episode_steps(qlx_env* env, uint32_t* out /* [n_envs] */);
 /* Running per-env checksum of every step (state + new frame), see DESIGN.md §parity. */
 int32_t qlx_env_hashes(qlx_env* env, uint64_t* out /* [n_envs] */);
 int32_t qlx_env_sync(qlx_env* env);

@@ -76,8 +76,10 @@ struct Contact { float dist; V2 normal1; V2 normal2; };
 static void project_local_point(V2 he, V2 p, V2* proj, bool* is_inside, int* face_axis, bool* face_min) {
   const float mins_pt[2] = {-he.x - p.x, -he.y - p.y};
   const float pt_maxs[2] = {p.x - he.x, p.y - he.y};
-  const float shift[2] = {std::max(mins_pt[0], 0.0f) - std::max(pt_maxs[0], 0.0f),
-                          std::max(mins_pt[1], 0.0f) - std::max(pt_maxs[1], 0.0f)};
+  // Vector::sup(&zero) is f32::max per component, which returns the other operand for a NaN (std::max would
+  // return the NaN): a non-finite coordinate gives shift 0 and counts as inside, as in the product
+  const auto max0 = [](float v) { return v > 0.0f ? v : 0.0f; };
+  const float shift[2] = {max0(mins_pt[0]) - max0(pt_maxs[0]), max0(mins_pt[1]) - max0(pt_maxs[1])};
   const bool inside = shift[0] == 0.0f && shift[1] == 0.0f;
   if (!inside) {
     *proj = {p.x + shift[0], p.y + shift[1]};
@@ -97,7 +99,9 @@ static void project_local_point(V2 he, V2 p, V2* proj, bool* is_inside, int* fac
     }
   }
   float s[2] = {0.0f, 0.0f};
-  if (best_id < 0) { s[-best_id - 1] = best; *face_axis = -best_id - 1; *face_min = true; }
+  if (best_id == 0) { s[1] = best; *face_axis = 1; *face_min = true; }   // both coordinates NaN (the reference's index
+                                                                          // panics there); the projection is NaN either way
+  else if (best_id < 0) { s[-best_id - 1] = best; *face_axis = -best_id - 1; *face_min = true; }
   else { s[best_id - 1] = -best; *face_axis = best_id - 1; *face_min = false; }
   *proj = {p.x + s[0], p.y + s[1]};
   *is_inside = true;
@@ -106,7 +110,7 @@ static void project_local_point(V2 he, V2 p, V2* proj, bool* is_inside, int* fac
 // contact_ball_convex_polyhedron -> contact_convex_polyhedron_ball(pos12.inverse(), cuboid, ball)
 // then Contact::swapped().  Translation-only isometries: the identity rotations leave every
 // component unchanged (up to the sign of an exact zero, which no later comparison observes).
-static bool contact_test_circle_aabb(V2 c, float r, const AABB& bb, Contact* out) {
+static bool contact_test_circle_aabb(V2 c, float r, const AABB& bb, Contact* out, Census* cz) {
   const V2 bc = {(bb.min.x + bb.max.x) / 2.0f, (bb.min.y + bb.max.y) / 2.0f};   // AaBB::center
   const V2 he = {(bb.max.x - bb.min.x) / 2.0f, (bb.max.y - bb.min.y) / 2.0f};
   const V2 t12 = vsub(bc, c);          // pos1.inv_mul(pos2).translation
@@ -119,7 +123,7 @@ static bool contact_test_circle_aabb(V2 c, float r, const AABB& bb, Contact* out
   if (sq > FLT_EPSILON * FLT_EPSILON) {     // Unit::try_new_and_get(v, DEFAULT_EPSILON)
     const float len = std::sqrt(sq);
     const V2 dir = vdiv(d, len);
-    if (inside) { dist = -len - r; n1 = dir; }
+    if (inside) { dist = -len - r; n1 = dir; if (cz) cz->inside += 1; }
     else { dist = len - r; n1 = vneg(dir); }
   } else {
     // Degenerate branch: the ball centre lies on the cuboid boundary (proj == centre).
@@ -132,6 +136,7 @@ static bool contact_test_circle_aabb(V2 c, float r, const AABB& bb, Contact* out
     if (sx != 0.0f && sy != 0.0f) n1 = vdiv({sx, sy}, std::sqrt(sx * sx + sy * sy));
     else if (sx != 0.0f || sy != 0.0f) n1 = {sx, sy};
     else n1 = {0.0f, 1.0f};
+    if (cz) { cz->degenerate += 1; if (sx != 0.0f && sy != 0.0f) cz->degenerate_vertex += 1; }
     (void)fax; (void)fmin;
   }
   if (dist <= CONTACT_PREDICTION) {
@@ -171,13 +176,18 @@ static bool wall_top(V2 center, float radius, V2 mv, ContactSurface* out, int* f
 
 // ---- mechanics.rs:337-443 find_non_penetrating_collision ---------------------------------
 static ContactSurface binary_search_first_contact(V2 c, float r, V2 mv, float lo, float hi, const AABB& bb,
-                                                  int depth, int* fault) {
+                                                  int depth, int* fault, Census* cz) {
   // mechanics.rs:361-389, recursion unrolled into a loop
   for (;;) {
-    if (depth > MAX_BSEARCH) { *fault |= F_RECURSION; return {vlen(mv) * hi, 0.0f, {0.0f, 1.0f}}; }
+    if (depth > MAX_BSEARCH) {
+      *fault |= F_RECURSION;
+      if (cz) cz->bisect_exhausted += 1;
+      return {vlen(mv) * hi, 0.0f, {0.0f, 1.0f}};
+    }
+    if (cz && (uint32_t)depth > cz->bisect_max_depth) cz->bisect_max_depth = (uint32_t)depth;
     const float m = (lo + hi) / 2.0f;
     Contact ct;
-    const bool hit = contact_test_circle_aabb(vadd(c, vmul(mv, m)), r, bb, &ct);
+    const bool hit = contact_test_circle_aabb(vadd(c, vmul(mv, m)), r, bb, &ct, cz);
     if (!hit) { lo = m; }
     else if (ct.dist < -PENETRATION_LIMIT) { hi = m; }
     else return {vlen(mv) * m, ct.dist, ct.normal2};
@@ -185,17 +195,26 @@ static ContactSurface binary_search_first_contact(V2 c, float r, V2 mv, float lo
   }
 }
 
-static bool find_non_penetrating_collision(V2 c, float r, V2 mv, const AABB& bb, ContactSurface* out, int* fault) {
+static bool find_non_penetrating_collision(V2 c, float r, V2 mv, const AABB& bb, ContactSurface* out, int* fault,
+                                           Census* cz) {
   Contact ct;
-  if (!contact_test_circle_aabb(vadd(c, mv), r, bb, &ct)) return false;
+  if (!contact_test_circle_aabb(vadd(c, mv), r, bb, &ct, cz)) return false;
   if (ct.dist < -PENETRATION_LIMIT) {
     // moved_distance_after_collision(p, n1, mv) = p / (n1 . mv / |mv|)   (:351-358)
     const float x = std::fabs(ct.dist) / (vdot(ct.normal1, mv) / vlen(mv));
     const float portion = 1.0f - x / vlen(mv);
     Contact ct2;
-    const bool hit2 = contact_test_circle_aabb(vadd(c, vmul(mv, portion)), r, bb, &ct2);
-    if (!hit2) { *out = binary_search_first_contact(c, r, mv, portion, 1.0f, bb, 0, fault); return true; }
-    if (ct2.dist < -PENETRATION_LIMIT) { *out = binary_search_first_contact(c, r, mv, 0.0f, portion, bb, 0, fault); return true; }
+    const bool hit2 = contact_test_circle_aabb(vadd(c, vmul(mv, portion)), r, bb, &ct2, cz);
+    if (!hit2) {
+      if (cz) cz->bisect_upper += 1;
+      *out = binary_search_first_contact(c, r, mv, portion, 1.0f, bb, 0, fault, cz);
+      return true;
+    }
+    if (ct2.dist < -PENETRATION_LIMIT) {
+      if (cz) cz->bisect_lower += 1;
+      *out = binary_search_first_contact(c, r, mv, 0.0f, portion, bb, 0, fault, cz);
+      return true;
+    }
     *out = {vlen(mv) * portion, ct2.dist, ct2.normal2};
     return true;
   }
@@ -203,26 +222,36 @@ static bool find_non_penetrating_collision(V2 c, float r, V2 mv, const AABB& bb,
   return true;
 }
 
-// mechanics.rs:317-335
+// mechanics.rs:317-335.  An exhausted bisection raises F_RECURSION in the caller's fault word: the reference's
+// recursion does not return there, and the product flags the same tick.
+static bool rect_check_in(V2 center, float radius, V2 mv, const AABB& rect, ContactSurface* out, int* fault, Census* cz) {
+  ContactSurface cs;
+  if (!find_non_penetrating_collision(center, radius, mv, rect, &cs, fault, cz)) return false;
+  if (std::fabs(vector_angle(mv, cs.normal)) > FRAC_PI_2_F) { *out = cs; return true; }
+  if (cz) cz->angle_reject += 1;
+  return false;
+}
+// KAT entry point (no state to fault)
 bool rect_check(V2 center, float radius, V2 mv, AABB rect, ContactSurface* out) {
   int fault = 0;
-  ContactSurface cs;
-  if (!find_non_penetrating_collision(center, radius, mv, rect, &cs, &fault)) return false;
-  if (std::fabs(vector_angle(mv, cs.normal)) > FRAC_PI_2_F) { *out = cs; return true; }
-  return false;
+  return rect_check_in(center, radius, mv, rect, out, &fault, nullptr);
 }
 
 // ---- mechanics.rs:485-539 ContactCandidates -------------------------------------------
-struct Candidate { ContactSurface s; int brick_idx; };   // brick_idx = index into bricks vector, -1 = none
+struct Candidate { ContactSurface s; int brick_idx; };   // brick_idx = index into bricks vector; -1 panel, -2 a wall
 
-static void candidates_consider(std::vector<Candidate>& v, const Candidate& c, int* fault) {
-  if (!(c.s.approximation >= -PENETRATION_LIMIT && c.s.approximation <= CONTACT_PREDICTION)) *fault |= F_CANDIDATE_ASSERT;
+static void candidates_consider(std::vector<Candidate>& v, const Candidate& c, int* fault, Census* cz) {
+  if (!(c.s.approximation >= -PENETRATION_LIMIT && c.s.approximation <= CONTACT_PREDICTION)) {
+    *fault |= F_CANDIDATE_ASSERT;
+    if (cz) cz->candidate_assert += 1;
+  }
   v.push_back(c);
   if (v.size() > 1) {
     float shortest = INFINITY;
     for (const auto& e : v) { const float len = e.s.way + e.s.approximation; if (len < shortest) shortest = len; }
     std::vector<Candidate> kept;
     for (const auto& e : v) if (e.s.way + e.s.approximation <= shortest + SPACE_GRANULARITY) kept.push_back(e);
+    if (cz && kept.size() < v.size()) cz->filter_dropped += 1;
     v.swap(kept);
   }
 }
@@ -246,24 +275,43 @@ static bool effective_collision_surface(const std::vector<Candidate>& v, Contact
 static std::vector<Candidate> check_collisions(const Mechanics& m, V2 mv, int* fault) {
   std::vector<Candidate> cands;
   ContactSurface cs;
-  if (wall_left(m.ball_center, m.ball_radius, mv, &cs, fault)) candidates_consider(cands, {cs, -1}, fault);
-  if (wall_right(m.ball_center, m.ball_radius, mv, &cs, fault)) candidates_consider(cands, {cs, -1}, fault);
-  if (wall_top(m.ball_center, m.ball_radius, mv, &cs, fault)) candidates_consider(cands, {cs, -1}, fault);
-  if (rect_check(m.ball_center, m.ball_radius, mv, m.panel, &cs)) candidates_consider(cands, {cs, -1}, fault);
+  Census* cz = m.census;
+  int wf = 0;   // this move's wall assertions
+  if (wall_left(m.ball_center, m.ball_radius, mv, &cs, &wf)) { if (cz) cz->wall_left += 1; candidates_consider(cands, {cs, -2}, fault, cz); }
+  if (wall_right(m.ball_center, m.ball_radius, mv, &cs, &wf)) { if (cz) cz->wall_right += 1; candidates_consider(cands, {cs, -2}, fault, cz); }
+  if (wall_top(m.ball_center, m.ball_radius, mv, &cs, &wf)) { if (cz) cz->wall_top += 1; candidates_consider(cands, {cs, -2}, fault, cz); }
+  if (cz && wf) cz->wall_assert += 1;
+  *fault |= wf;
+  if (rect_check_in(m.ball_center, m.ball_radius, mv, m.panel, &cs, fault, cz)) {
+    if (cz) cz->panel_contact += 1;
+    candidates_consider(cands, {cs, -1}, fault, cz);
+  }
   for (size_t i = 0; i < m.bricks.size(); ++i)
-    if (rect_check(m.ball_center, m.ball_radius, mv, m.bricks[i].shape, &cs)) candidates_consider(cands, {cs, (int)i}, fault);
+    if (rect_check_in(m.ball_center, m.ball_radius, mv, m.bricks[i].shape, &cs, fault, cz))
+      candidates_consider(cands, {cs, (int)i}, fault, cz);
+  if (cz) {
+    int walls = 0, panel = 0, bricks = 0;
+    for (const auto& c : cands) { if (c.brick_idx == -2) ++walls; else if (c.brick_idx == -1) ++panel; else ++bricks; }
+    if (bricks && (walls || panel)) cz->mixed_set += 1;
+    if (walls >= 2) cz->two_walls += 1;
+    if (walls && panel) cz->wall_and_panel += 1;
+    if (cands.size() > 2) cz->set_gt2 += 1;
+  }
   return cands;
 }
 
 // ---- mechanics.rs:137-184 proceed_ball_with (recursion -> loop) --------------------------
 static void proceed_ball_with(Mechanics& m, V2 mv) {
+  Census* cz = m.census;
   for (int depth = 0;; ++depth) {
     if (vlen(mv) < SPACE_GRANULARITY) return;
-    if (depth > MAX_RECURSION) { m.fault |= F_RECURSION; return; }
+    if (depth > MAX_RECURSION) { m.fault |= F_RECURSION; if (cz) cz->moves_exhausted += 1; return; }
+    if (cz && depth == 2) cz->moves3 += 1;
     std::vector<Candidate> cands = check_collisions(m, mv, &m.fault);
     std::vector<int> hit;
     for (const auto& c : cands) if (c.brick_idx >= 0) hit.push_back(c.brick_idx);
     std::sort(hit.begin(), hit.end());
+    if (cz && hit.size() > 1) cz->multi_brick += 1;
     for (auto it = hit.rbegin(); it != hit.rend(); ++it) {
       m.bricks.erase(m.bricks.begin() + *it);
       m.score += 1;
@@ -300,7 +348,7 @@ static inline float accelerate(float s, float a, float limit) {
 }
 
 // ---- mechanics.rs:56-116 construction ----------------------------------------------------
-void mechanics_init(Mechanics& m, uint64_t seed, uint32_t env_id, uint32_t reset_count) {
+void mechanics_set_bricks(Mechanics& m, uint64_t mask) {
   m.bricks.clear();
   int id = 0;
   for (int row = 0; row < BRICK_ROWS; ++row) {
@@ -310,9 +358,14 @@ void mechanics_init(Mechanics& m, uint64_t seed, uint32_t env_id, uint32_t reset
       const AABB b = {{left_x, upper_y - BRICK_EDGE}, {left_x + BRICK_EDGE, upper_y}};
       if (b.max.x >= GRID_X - BRICKS_RIGHT_MIN) break;
       left_x = b.max.x + BRICK_SPACING;
-      m.bricks.push_back({b, id++});
+      if ((mask >> id) & 1ull) m.bricks.push_back({b, id});
+      ++id;
     }
   }
+}
+
+void mechanics_init(Mechanics& m, uint64_t seed, uint32_t env_id, uint32_t reset_count) {
+  mechanics_set_bricks(m, (1ull << kNumBricks) - 1ull);
   Stream s(seed, env_id, reset_count, P_BALL);
   m.ball_center = {GRID_X * 0.5f, GRID_Y * 0.5f};
   m.ball_radius = BALL_RADIUS;
@@ -331,11 +384,14 @@ void mechanics_time_step(Mechanics& m, int action) {
   // Panel::proceed
   const float dx = m.panel_speed * TIME_GRANULARITY;
   AABB pot = {{m.panel.min.x + dx, m.panel.min.y + 0.0f}, {m.panel.max.x + dx, m.panel.max.y + 0.0f}};
+  Census* cz = m.census;
   if (pot.min.x <= 0.0f) {
+    if (cz) cz->clamp_left += 1;
     const float t = -pot.min.x;
     m.panel = {{pot.min.x + t, pot.min.y + 0.0f}, {pot.max.x + t, pot.max.y + 0.0f}};
     m.panel_speed = 0.0f;
   } else if (pot.max.x >= GRID_X) {
+    if (cz) cz->clamp_right += 1;
     const float t = GRID_X - pot.max.x;
     m.panel = {{pot.min.x + t, pot.min.y + 0.0f}, {pot.max.x + t, pot.max.y + 0.0f}};
     m.panel_speed = 0.0f;
@@ -347,6 +403,14 @@ void mechanics_time_step(Mechanics& m, int action) {
   proceed_ball_with(m, mv);
   // check_game_end_situation (:131-135)
   if (m.ball_center.y >= m.panel.max.y || m.bricks.empty()) m.finished = true;
+  if (cz) {
+    cz->ticks += 1;
+    if (m.bricks.empty()) cz->cleared += 1;
+    if (m.score > cz->max_score) cz->max_score = m.score;
+    if (!std::isfinite(m.ball_center.x) || !std::isfinite(m.ball_center.y) || !std::isfinite(m.ball_dir.x) ||
+        !std::isfinite(m.ball_dir.y))
+      cz->nonfinite += 1;
+  }
   if (!m.finished) {
     if (action == 0) m.panel_speed = decrease_speed(m.panel_speed, PANEL_SLOWDOWN);
     else if (action == 1) m.panel_speed = accelerate(m.panel_speed, -PANEL_ACCEL, PANEL_MAX_SPEED);

@@ -28,6 +28,37 @@ struct ContactSurface {   // algebra_2d.rs:37-43
 
 struct Brick { AABB shape; int id; };   // id = creation order 0..59 (rows top→bottom, left→right)
 
+// Per-env branch census of the physics: which sites of the restatement a run has reached.  Filled only where
+// Mechanics::census points at one (a null pointer costs one untaken branch per site).  One struct per env, and
+// the batched drivers give every env to exactly one OpenMP thread, so no counter is shared between threads.
+// All fields are u32 so that tests/oracle.py can read the struct as an array (CENSUS_FIELDS, same order).
+struct Census {
+  uint32_t wall_left, wall_right, wall_top;   // wall tests that returned a candidate
+  uint32_t panel_contact;                     // rect_check accepted the panel
+  uint32_t clamp_left, clamp_right;           // Panel::proceed stopped the panel at a border
+  uint32_t inside;                            // contact(): ball centre strictly inside the box
+  uint32_t degenerate;                        // contact(): centre on the boundary (sq <= eps^2)
+  uint32_t degenerate_vertex;                 //   ... of which on a corner (diagonal normal)
+  uint32_t bisect_lower, bisect_upper;        // bisection started on [0, portion] (hit2 penetrates) / [portion, 1] (!hit2)
+  uint32_t bisect_exhausted;                  // bisection ran out of its probes (F_RECURSION)
+  uint32_t bisect_max_depth;                  // deepest probe index reached by a bisection (a maximum, not a count)
+  uint32_t angle_reject;                      // rect_check dropped a contact at the angle test
+  uint32_t filter_dropped;                    // ContactCandidates::consider dropped at least one candidate
+  uint32_t multi_brick;                       // moves that removed more than one brick
+  uint32_t mixed_set;                         // final candidate sets holding a brick and a non-brick
+  uint32_t two_walls;                         // final candidate sets holding two walls
+  uint32_t wall_and_panel;                    // final candidate sets holding a wall and the panel
+  uint32_t set_gt2;                           // final candidate sets of more than two
+  uint32_t moves3;                            // ticks with three or more moves
+  uint32_t moves_exhausted;                   // move loop ran out (F_RECURSION)
+  uint32_t wall_assert;                       // wall tests that raised F_WALL_ASSERT
+  uint32_t candidate_assert;                  // inserted candidates that raised F_CANDIDATE_ASSERT
+  uint32_t cleared;                           // ticks that ended with no brick left
+  uint32_t max_score;                         // highest score seen (a maximum, not a count)
+  uint32_t nonfinite;                         // ticks that ended with a non-finite ball centre or direction
+  uint32_t ticks;
+};
+
 struct Mechanics {   // mechanics.rs:46-54
   std::vector<Brick> bricks;
   V2 ball_center;
@@ -39,6 +70,7 @@ struct Mechanics {   // mechanics.rs:46-54
   bool finished;
   uint32_t score;
   int fault;          // non-zero where the reference would panic (assert!) — see fault codes
+  Census* census = nullptr;   // optional branch counters (not part of the state; mechanics_init leaves it)
 };
 
 enum Fault : int {
@@ -61,6 +93,9 @@ constexpr uint8_t kLumaBrick = 96, kLumaBall = 236, kLumaPanel = 255;
 
 void mechanics_init(Mechanics& m, uint64_t seed, uint32_t env_id, uint32_t reset_count);
 void mechanics_time_step(Mechanics& m, int action);   // action 0 None, 1 Left, 2 Right
+// The brick vector of a 60-bit mask (bit id = brick id), in creation order: what mechanics_init builds with the
+// bricks of the cleared bits erased.
+void mechanics_set_bricks(Mechanics& m, uint64_t mask);
 float acos_gt_half_pi_threshold();                    // see breakout_ref.cpp
 
 // KAT entry points (mechanics.rs:659-752)

@@ -96,6 +96,30 @@ void orc_env_state(void* h, OrcState* out) { fill_state(*(Env*)h, out); }
 void orc_env_tensor(void* h, uint8_t* out) { env_state_tensor(*(Env*)h, out); }
 void orc_env_frame(void* h, int slot, uint8_t* out_yx) { std::memcpy(out_yx, ((Env*)h)->frames[slot], kFramePix); }
 
+// Every field of the state from an OrcState: the brick vector rebuilt from the 60-bit mask in creation order, the
+// rest copied as given (floats included, finite or not).  Frames are left as they are.
+static void apply_state(Env& e, const OrcState& s) {
+  Mechanics& m = e.mech;
+  mechanics_set_bricks(m, s.bricks);
+  m.ball_center = {s.ball_x, s.ball_y};
+  m.ball_dir = {s.dir_x, s.dir_y};
+  m.panel = {{s.panel_min_x, s.panel_min_y}, {s.panel_max_x, s.panel_max_y}};
+  m.panel_speed = s.panel_speed;
+  m.score = s.score;
+  m.finished = s.finished != 0;
+  m.fault = (int)s.fault;
+  e.next_slot = (int)(s.next_slot & 3u);
+  e.reset_count = s.reset_count;
+}
+void orc_env_set_state(void* h, const OrcState* in) { apply_state(*(Env*)h, *in); }
+// Census of one env: orc_env_set_census zeroes and attaches one (the caller's buffer of
+// orc_census_size() bytes, which must outlive the env or be detached with a null pointer).
+uint32_t orc_census_size() { return (uint32_t)sizeof(Census); }
+void orc_env_set_census(void* h, Census* cz) {
+  if (cz) std::memset(cz, 0, sizeof(Census));
+  ((Env*)h)->mech.census = cz;
+}
+
 // ---------------- batched env run (parity driver) ----------------
 // Linear per-step hash (definition shared with the product's on-device checksum):
 //   hf = sum_i img[i] * (i+1) * K1      over the new frame, i = y*84 + x
@@ -119,13 +143,14 @@ static uint64_t frame_hash(const uint8_t* img) {
 
 // Runs n_envs envs for n_steps with actions from Stream(action_seed, env, step, P_SYNTH) (gen_range_u8(3)),
 // resetting an env after done or max_steps_per_episode steps (as the learner does).
-void orc_envs_run(uint64_t env_seed, uint32_t n_envs, uint32_t n_steps, uint64_t action_seed, uint64_t max_steps,
-                  OrcState* final_states, uint64_t* hashes, float* total_reward, uint32_t* episodes,
-                  uint8_t* final_tensors) {
+static void envs_run(uint64_t env_seed, uint32_t n_envs, uint32_t n_steps, uint64_t action_seed, uint64_t max_steps,
+                     OrcState* final_states, uint64_t* hashes, float* total_reward, uint32_t* episodes,
+                     uint8_t* final_tensors, Census* census) {
 #pragma omp parallel for schedule(dynamic, 4)
   for (uint32_t e = 0; e < n_envs; ++e) {
     Env env;
     env_init(env, env_seed, e);
+    if (census) { std::memset(&census[e], 0, sizeof(Census)); env.mech.census = &census[e]; }
     uint64_t H = 0, ep_steps = 0;
     float tot = 0.0f;
     uint32_t eps = 0;
@@ -147,6 +172,84 @@ void orc_envs_run(uint64_t env_seed, uint32_t n_envs, uint32_t n_steps, uint64_t
     episodes[e] = eps;
     if (final_tensors) env_state_tensor(env, final_tensors + (size_t)e * kStateBytes);
   }
+}
+void orc_envs_run(uint64_t env_seed, uint32_t n_envs, uint32_t n_steps, uint64_t action_seed, uint64_t max_steps,
+                  OrcState* final_states, uint64_t* hashes, float* total_reward, uint32_t* episodes,
+                  uint8_t* final_tensors) {
+  envs_run(env_seed, n_envs, n_steps, action_seed, max_steps, final_states, hashes, total_reward, episodes, final_tensors,
+           nullptr);
+}
+// the same run with the census of every env [n_envs]
+void orc_envs_run_census(uint64_t env_seed, uint32_t n_envs, uint32_t n_steps, uint64_t action_seed, uint64_t max_steps,
+                         OrcState* final_states, uint64_t* hashes, float* total_reward, uint32_t* episodes,
+                         uint8_t* final_tensors, Census* census) {
+  envs_run(env_seed, n_envs, n_steps, action_seed, max_steps, final_states, hashes, total_reward, episodes, final_tensors,
+           census);
+}
+
+// The tracking policy: move the panel towards the ball, with a dead band of +-10 around the panel's centre.
+static inline uint8_t tracker_action(const Mechanics& m) {
+  const float pc = (m.panel.min.x + m.panel.max.x) / 2.0f;
+  if (m.ball_center.x < pc - 10.0f) return 1;
+  if (m.ball_center.x > pc + 10.0f) return 2;
+  return 0;
+}
+
+// One driver behind both tape calls.  Env e starts from env_init(env_seed, e), then from start[e] if given; it is
+// reset on done only.  track = true writes tape[t][e] from the tracking policy before each step, otherwise the tape
+// is read.  Every output may be null.  Checkpoint c holds the state and the chained hash after step (c + 1) * K,
+// before the reset that a done step brings.
+static void run_tape(uint64_t env_seed, uint32_t n_envs, uint32_t T, uint8_t* tape, bool track, const OrcState* start,
+                     uint32_t K, float* rewards, uint8_t* dones, OrcState* ck_states, uint64_t* ck_hashes,
+                     OrcState* final_states, uint64_t* final_hashes, uint8_t* final_tensors, Census* census) {
+#pragma omp parallel for schedule(dynamic, 1)
+  for (uint32_t e = 0; e < n_envs; ++e) {
+    Env env;
+    env_init(env, env_seed, e);
+    if (start) apply_state(env, start[e]);
+    if (census) { std::memset(&census[e], 0, sizeof(Census)); env.mech.census = &census[e]; }
+    uint64_t H = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+      const size_t i = (size_t)t * n_envs + e;
+      if (track) {   // the policy reads the mechanics alone: no frame is drawn
+        tape[i] = tracker_action(env.mech);
+        mechanics_time_step(env.mech, tape[i]);
+        if (env.mech.finished) env_reset(env);
+        continue;
+      }
+      float r; bool d;
+      const int slot = env.next_slot;
+      env_step(env, tape[i], &r, &d);
+      if (rewards) rewards[i] = r;
+      if (dones) dones[i] = d ? 1 : 0;
+      OrcState st; fill_state(env, &st);
+      H = H * K3 + frame_hash(env.frames[slot]) + state_hash(st);
+      if (K && (t + 1) % K == 0) {
+        const size_t c = (size_t)((t + 1) / K - 1) * n_envs + e;
+        if (ck_states) ck_states[c] = st;
+        if (ck_hashes) ck_hashes[c] = H;
+      }
+      if (d) env_reset(env);
+    }
+    if (final_states) fill_state(env, &final_states[e]);
+    if (final_hashes) final_hashes[e] = H;
+    if (final_tensors) env_state_tensor(env, final_tensors + (size_t)e * kStateBytes);
+  }
+}
+
+// Runs a tape of actions [T][n_envs] (each 0..2): per-step rewards and dones [T][n_envs], the full state and the
+// chained hash of every env at every checkpoint [T / K][n_envs], the final states, hashes and tensors, and the
+// census per env.
+void orc_envs_run_tape(uint64_t env_seed, uint32_t n_envs, uint32_t T, const uint8_t* tape, const OrcState* start,
+                       uint32_t K, float* rewards, uint8_t* dones, OrcState* ck_states, uint64_t* ck_hashes,
+                       OrcState* final_states, uint64_t* final_hashes, uint8_t* final_tensors, Census* census) {
+  run_tape(env_seed, n_envs, T, const_cast<uint8_t*>(tape), false, start, K, rewards, dones, ck_states, ck_hashes,
+           final_states, final_hashes, final_tensors, census);
+}
+
+// Writes the tape [T][n_envs] that the tracking policy plays from the same start.
+void orc_envs_tracker_tape(uint64_t env_seed, uint32_t n_envs, uint32_t T, const OrcState* start, uint8_t* tape) {
+  run_tape(env_seed, n_envs, T, tape, true, start, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ---------------- Q-network ----------------

@@ -36,10 +36,12 @@ __device__ __forceinline__ F2 sub(F2 a, F2 b) { return {a.x - b.x, a.y - b.y}; }
 __device__ __forceinline__ F2 scale(F2 a, float s) { return {a.x * s, a.y * s}; }
 __device__ __forceinline__ F2 divs(F2 a, float s) { return {a.x / s, a.y / s}; }
 __device__ __forceinline__ float dotp(F2 a, F2 b) { return a.x * b.x + a.y * b.y; }
-// emath Vec2::length = f32::hypot -> glibc: (float) sqrt((double)x*x + (double)y*y)
+// emath Vec2::length = f32::hypot -> glibc: (float) sqrt((double)x*x + (double)y*y); an infinite component gives
+// +infinity even beside a NaN (IEEE hypot), where the sum of squares would give NaN
 __device__ __forceinline__ float length(F2 a) {
   const double x = a.x, y = a.y;
-  return (float)__builtin_sqrt(x * x + y * y);
+  const float l = (float)__builtin_sqrt(x * x + y * y);
+  return fabsf(a.x) == INFINITY || fabsf(a.y) == INFINITY ? INFINITY : l;
 }
 __device__ __forceinline__ F2 normalized(F2 a) {
   const float l = length(a);
@@ -179,10 +181,13 @@ __device__ bool candidate(const Ctx& x, int o, Surface* s, uint32_t* fault) {
   float b[4];
   if (o == 3) { b[0] = x.panel[0]; b[1] = x.panel[1]; b[2] = x.panel[2]; b[3] = x.panel[3]; }
   else brick_box(o - 4, b);
-  // conservative early-out: a contact needs the end position within r + 0.8 of the box
+  // conservative early-out: a contact needs the end position within r + 0.8 of the box.  Only for a finite end
+  // position: with a NaN or infinite coordinate the projection is NaN and the contact test lands on its boundary
+  // branch (distance -r), a contact with every box wherever the other coordinate is.
   const float ex = x.c.x + x.mv.x, ey = x.c.y + x.mv.y;
   const float reach = x.r + kPrediction + 1.0f;
-  if (ex < b[0] - reach || ex > b[2] + reach || ey < b[1] - reach || ey > b[3] + reach) return false;
+  const bool finite = fabsf(ex) < INFINITY && fabsf(ey) < INFINITY;
+  if (finite && (ex < b[0] - reach || ex > b[2] + reach || ey < b[1] - reach || ey > b[3] + reach)) return false;
   return rect_surface(x.c, x.r, x.mv, b[0], b[1], b[2], b[3], x.acos_thr, s, fault);
 }
 
@@ -262,6 +267,10 @@ __device__ void time_step(State& s, uint32_t action, float acos_thr, int lane) {
     if (count == 0) { x.c = add(x.c, x.mv); break; }
     // pass 2: ContactCandidates::consider keeps {path <= shortest + 0.001} (any single candidate if it is the
     // only one); sums run in insertion order (walls, panel, bricks ascending) = lane order, read lane by lane
+    // consider filters after every insertion, which differs from one filter over all only when every path is NaN:
+    // each second NaN empties the set, so of an odd number of them the last stands alone and is kept.
+    const bool nan_last = count > 2 && (count & 1) && __ballot(hit && pl != pl) == hitmask;
+    const int last = 63 - __builtin_clzll(hitmask);
     const float thr = shortest + kSpaceGranularity;
     F2 nsum = {0.0f, 0.0f};
     float asum = 0.0f, wsum = 0.0f;
@@ -272,7 +281,7 @@ __device__ void time_step(State& s, uint32_t action, float acos_thr, int lane) {
     for (uint64_t m = hitmask; m; m &= m - 1) {
       const int oh = __builtin_ctzll(m);
       const Surface c = {rl(su.way, oh), rl(su.approx, oh), F2{rl(su.n.x, oh), rl(su.n.y, oh)}};
-      if (count > 1 && !(c.way + c.approx <= thr)) continue;
+      if (count > 1 && !(c.way + c.approx <= thr) && !(nan_last && oh == last)) continue;
       if (kept == 0) first = c;
       nsum = add(nsum, c.n);
       asum = asum + c.approx;
@@ -596,6 +605,28 @@ int32_t qlx_env_states(qlx_env* e, qlx_breakout_state* out) {
     QLX_CHECK(e && out, QLX_E_INVALID, "null argument");
     QLX_HIP(hipSetDevice(e->device));
     QLX_HIP(hipMemcpyAsync(out, e->d_state, sizeof(State) * e->n, hipMemcpyDeviceToHost, e->stream));
+    QLX_HIP(hipStreamSynchronize(e->stream));
+  });
+}
+
+int32_t qlx_env_set_states(qlx_env* e, const qlx_breakout_state* in) {
+  return guard([&] {
+    QLX_CHECK(e && in, QLX_E_INVALID, "null argument");
+    for (uint32_t i = 0; i < e->n; ++i)
+      QLX_CHECK(in[i].finished <= 1 && in[i].next_slot <= 3 && (in[i].bricks >> kNumBricks) == 0, QLX_E_INVALID,
+                "state field out of range");
+    QLX_HIP(hipSetDevice(e->device));
+    QLX_HIP(hipMemcpyAsync(e->d_state, in, sizeof(State) * e->n, hipMemcpyHostToDevice, e->stream));
+    QLX_HIP(hipMemsetAsync(e->d_ep_steps, 0, sizeof(uint32_t) * e->n, e->stream));
+    QLX_HIP(hipStreamSynchronize(e->stream));
+  });
+}
+
+int32_t qlx_env_episode_steps(qlx_env* e, uint32_t* out) {
+  return guard([&] {
+    QLX_CHECK(e && out, QLX_E_INVALID, "null argument");
+    QLX_HIP(hipSetDevice(e->device));
+    QLX_HIP(hipMemcpyAsync(out, e->d_ep_steps, sizeof(uint32_t) * e->n, hipMemcpyDeviceToHost, e->stream));
     QLX_HIP(hipStreamSynchronize(e->stream));
   });
 }

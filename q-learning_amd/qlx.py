@@ -232,6 +232,7 @@ def lib():
         "qlx_env_count": ([vp], u32), "qlx_env_reset": ([vp, u8p], i32), "qlx_env_step": ([vp, u8p, vp, u8p], i32),
         "qlx_env_step_dev": ([vp, vp, vp, vp], i32), "qlx_env_obs": ([vp, u8p], i32),
         "qlx_env_states": ([vp, vp], i32), "qlx_env_hashes": ([vp, vp], i32), "qlx_env_sync": ([vp], i32),
+        "qlx_env_set_states": ([vp, vp], i32), "qlx_env_episode_steps": ([vp, vp], i32),
         "qlx_replay_create": ([u64, u32, i32, C.POINTER(vp)], i32), "qlx_replay_destroy": ([vp], i32),
         "qlx_replay_len": ([vp], u64), "qlx_replay_push_dev": ([vp, vp, vp, vp, vp], i32),
         "qlx_replay_push": ([vp, vp, vp, vp, vp], i32),
@@ -481,6 +482,18 @@ class BreakoutEnvironment:
     def mechanics(self):
         out = np.zeros(self.n, STATE_DTYPE)
         _check(lib().qlx_env_states(self.h, _p(out)))
+        return out
+
+    def set_mechanics(self, st):
+        """Directed start states: STATE_DTYPE[n] over the mechanics (floats as given); episode steps are zeroed,
+        ring frames and checksums stay.  finished > 1, next_slot > 3 or bricks >= 2**60 is an error, nothing written."""
+        a = np.ascontiguousarray(st, dtype=STATE_DTYPE)
+        assert a.shape == (self.n,)
+        _check(lib().qlx_env_set_states(self.h, _p(a)))
+
+    def episode_steps(self):
+        out = np.zeros(self.n, np.uint32)
+        _check(lib().qlx_env_episode_steps(self.h, _p(out)))
         return out
 
     def hashes(self):

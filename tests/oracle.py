@@ -121,6 +121,13 @@ def lib():
         L.orc_env_tensor.argtypes = [vp, vp]
         L.orc_env_frame.argtypes = [vp, i32, vp]
         L.orc_envs_run.argtypes = [u64, u32, u32, u64, u64, vp, vp, vp, vp, vp]
+        L.orc_envs_run_census.argtypes = [u64, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp]
+        L.orc_env_set_state.argtypes = [vp, vp]
+        L.orc_env_set_census.argtypes = [vp, vp]
+        L.orc_census_size.restype = u32
+        L.orc_envs_run_tape.argtypes = [u64, u32, u32, vp, vp, u32] + [vp] * 8
+        L.orc_envs_tracker_tape.argtypes = [u64, u32, u32, vp, vp]
+        assert L.orc_census_size() == CENSUS_DTYPE.itemsize
         L.orc_qnet_new.argtypes = [u64]
         L.orc_qnet_new.restype = vp
         L.orc_qnet_free.argtypes = [vp]
@@ -242,11 +249,40 @@ def rect_check(center, radius, mv, lo, hi):
     return _surface(lib().orc_rect_check, center[0], center[1], radius, mv[0], mv[1], lo[0], lo[1], hi[0], hi[1])
 
 
+# struct Census of oracle/breakout_ref.h, field for field (max_* are maxima, the others counts)
+CENSUS_FIELDS = ("wall_left", "wall_right", "wall_top", "panel_contact", "clamp_left", "clamp_right", "inside",
+                 "degenerate", "degenerate_vertex", "bisect_lower", "bisect_upper", "bisect_exhausted",
+                 "bisect_max_depth", "angle_reject", "filter_dropped", "multi_brick", "mixed_set", "two_walls",
+                 "wall_and_panel", "set_gt2", "moves3", "moves_exhausted", "wall_assert", "candidate_assert",
+                 "cleared", "max_score", "nonfinite", "ticks")
+CENSUS_DTYPE = np.dtype([(k, "<u4") for k in CENSUS_FIELDS])
+CENSUS_MAXIMA = ("bisect_max_depth", "max_score")
+
+
+def census_total(cz):
+    """One dict over all envs of a census array: sums of the counts, maxima of the maxima."""
+    return {k: int(cz[k].max() if k in CENSUS_MAXIMA else cz[k].sum(dtype=np.uint64)) for k in CENSUS_FIELDS}
+
+
 class Env:
     """Single Breakout env (BreakoutEnvironment restatement)."""
 
     def __init__(self, seed, env_id=0):
         self.h = lib().orc_env_new(seed, env_id)
+        self._census = None
+
+    def set_state(self, st):
+        """Every field from one STATE_DTYPE record (bricks rebuilt from the mask in creation order); frames stay."""
+        a = np.ascontiguousarray(np.asarray(st, dtype=STATE_DTYPE).reshape(1))
+        lib().orc_env_set_state(self.h, _p(a))
+        return self
+
+    def census(self):
+        """The env's branch counters (one CENSUS_DTYPE record, live); the first call zeroes and attaches them."""
+        if self._census is None:
+            self._census = np.zeros(1, dtype=CENSUS_DTYPE)
+            lib().orc_env_set_census(self.h, _p(self._census))
+        return self._census[0]
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -287,6 +323,49 @@ def envs_run(env_seed, n_envs, n_steps, action_seed, max_steps=10_000, want_tens
     tens = np.zeros((n_envs, 84, 84, 4), dtype=np.uint8) if want_tensors else None
     lib().orc_envs_run(env_seed, n_envs, n_steps, action_seed, max_steps, _p(st), _p(h), _p(tr), _p(ep), _p(tens))
     return st, h, tr, ep, tens
+
+
+def envs_run_census(env_seed, n_envs, n_steps, action_seed, max_steps=10_000):
+    """envs_run with the per-env census: (final states, hashes, census[n_envs])."""
+    st = np.zeros(n_envs, dtype=STATE_DTYPE)
+    h = np.zeros(n_envs, dtype=np.uint64)
+    tr = np.zeros(n_envs, dtype=np.float32)
+    ep = np.zeros(n_envs, dtype=np.uint32)
+    cz = np.zeros(n_envs, dtype=CENSUS_DTYPE)
+    lib().orc_envs_run_census(env_seed, n_envs, n_steps, action_seed, max_steps, _p(st), _p(h), _p(tr), _p(ep), None, _p(cz))
+    return st, h, cz
+
+
+def _start_states(start, n_envs):
+    if start is None:
+        return None
+    a = np.ascontiguousarray(start, dtype=STATE_DTYPE)
+    assert a.shape == (n_envs,)
+    return a
+
+
+def envs_tracker_tape(env_seed, n_envs, T, start=None):
+    """The actions [T][n_envs] of the tracking policy (panel towards the ball, dead band +-10), reset on done only."""
+    tape = np.zeros((T, n_envs), dtype=np.uint8)
+    lib().orc_envs_tracker_tape(env_seed, n_envs, T, _p(_start_states(start, n_envs)), _p(tape))
+    return tape
+
+
+def envs_run_tape(env_seed, tape, K, start=None):
+    """Plays tape[T][n_envs] (reset on done only).  Returns a dict: rewards / dones [T][n], ck_states / ck_hashes
+    [T // K][n] (after step (c + 1) * K, before a reset), states / hashes / tensors at the end, census [n]."""
+    tape = np.ascontiguousarray(tape, dtype=np.uint8)
+    T, n = tape.shape
+    assert tape.max(initial=0) < 3
+    out = dict(rewards=np.zeros((T, n), np.float32), dones=np.zeros((T, n), np.uint8),
+               ck_states=np.zeros((T // K, n), STATE_DTYPE), ck_hashes=np.zeros((T // K, n), np.uint64),
+               states=np.zeros(n, STATE_DTYPE), hashes=np.zeros(n, np.uint64),
+               tensors=np.zeros((n, 84, 84, 4), np.uint8), census=np.zeros(n, CENSUS_DTYPE))
+    lib().orc_envs_run_tape(env_seed, n, T, _p(tape), _p(_start_states(start, n)), K, _p(out["rewards"]), _p(out["dones"]),
+                            _p(out["ck_states"]), _p(out["ck_hashes"]), _p(out["states"]), _p(out["hashes"]),
+                            _p(out["tensors"]), _p(out["census"]))
+    out["dones"] = out["dones"].astype(bool)
+    return out
 
 
 class QNet:

@@ -61,6 +61,18 @@ def test_host_queries_without_device(lib):
     assert lib.qlx_env_reward_goal_mean(ballgame) == 9.5
 
 
+def test_env_set_states_argument_errors(lib):
+    """qlx_env_set_states / qlx_env_episode_steps refuse a null env or a null array before any device is needed
+    (the range checks of the state fields need an env, so they are in the -m gpu tests)."""
+    lib.qlx_last_error.restype = ctypes.c_char_p
+    for fn in (lib.qlx_env_set_states, lib.qlx_env_episode_steps):
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int32
+        buf = ctypes.create_string_buffer(64)
+        assert fn(None, buf) == -1 and b"null argument" in lib.qlx_last_error()   # QLX_E_INVALID
+        assert fn(None, None) == -1
+
+
 def test_device_calls_fail_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():
