@@ -637,6 +637,17 @@ struct TableK4Stream {
   }
 };
 
+// element at byte offset off of a global array: the base stays scalar and the offset one 32-bit register, so an epilogue
+// forms no 64-bit vector address (the arrays addressed this way are below 4 GB, as the operand streams' descriptors require).
+// In the conv2 / conv3 backward-data epilogues: pairs 69.9 / 62.8 -> 68.8 / 61.8 us (B = 1024, C3, profiled runs); in the
+// list forwards' epilogue and the weight-gradient slab stores it measured no gain and was not kept.
+__host__ __device__ inline float ld_off(const float* base, uint32_t off) {
+  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off);
+}
+__host__ __device__ inline void st_off(float* base, uint32_t off, float v) {
+  *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) = v;
+}
+
 // a policy's LDS beyond its operand images (EXTRA_LDS bytes, after them)
 template <class P, class = void>
 struct ExtraLdsOf : std::integral_constant<size_t, 0> {};
@@ -1465,21 +1476,23 @@ struct PConv3DgradPx {
   __device__ void epi(int z, int row, int col, f32x4 v) const { epi_post(z, row, col, v, epi_pre(z, row, col)); }
   __device__ Pre epi_pre(int z, int row, int col) const {
     const Px q = px(z);
+    const uint32_t po = (uint32_t)((q.ih * 9 + q.iw) * 64 + col) * 4u;   // byte offset of (pixel, channel) in a sample
     Pre pr;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pr.m[r] = a2[((size_t)((row + r < B ? row + r : 0) * 9 + q.ih) * 9 + q.iw) * 64 + col];
+    for (int r = 0; r < 4; ++r) pr.m[r] = ld_off(a2, (uint32_t)(row + r < B ? row + r : 0) * 20736u + po);
     // (row is a multiple of 4 and row + 3 < bg2_ld: the four samples' bytes are one aligned dword)
     pr.bg = pbg ? *reinterpret_cast<const uint32_t*>(bg2 + (size_t)(q.ih * 9 + q.iw) * bg2_ld + row) : 0u;
     return pr;
   }
   __device__ void epi_post(int z, int row, int col, f32x4 v, const Pre& pr) const {
     const Px q = px(z);
+    const uint32_t po = (uint32_t)((q.ih * 9 + q.iw) * 64 + col) * 4u;
     float d[4], e[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       d[r] = row + r < B && pr.m[r] > 0.0f ? v[r] : 0.0f;
       e[r] = ((pr.bg >> (8 * r)) & 0xFFu) != 0u ? d[r] : 0.0f;
-      if (row + r < B) dz2[((size_t)((row + r) * 9 + q.ih) * 9 + q.iw) * 64 + col] = d[r];
+      if (row + r < B) st_off(dz2, (uint32_t)(row + r) * 20736u + po, d[r]);
     }
     if (pbg) {   // (uniform: every lane of the wave takes part in the exchanges)
       const float s = pb_sum16(e);
@@ -1565,9 +1578,10 @@ struct PConv2DgradPx {
   __device__ Pre epi_pre(int z, int row, int col) const {
     const Px q = px(z);
     const int cls = col >> 5, ih = 2 * q.i + (cls >> 1), iw = 2 * q.j + (cls & 1);
+    const uint32_t po = (uint32_t)((ih * 20 + iw) * 32 + (col & 31)) * 4u;   // byte offset of (pixel, channel) in a sample
     Pre pr;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pr.m[r] = a1[((size_t)((row + r < B ? row + r : 0) * 20 + ih) * 20 + iw) * 32 + (col & 31)];
+    for (int r = 0; r < 4; ++r) pr.m[r] = ld_off(a1, (uint32_t)(row + r < B ? row + r : 0) * 51200u + po);
     // (row is a multiple of 4 and row + 3 < need_ld: the four samples' bytes are one aligned dword)
     pr.nb = need ? *reinterpret_cast<const uint32_t*>(need + (size_t)((ih * 20 + iw) >> 2) * need_ld + row) : ~0u;
     return pr;
@@ -1575,11 +1589,12 @@ struct PConv2DgradPx {
   __device__ void epi_post(int z, int row, int col, f32x4 v, const Pre& pr) const {
     const Px q = px(z);
     const int cls = col >> 5, ih = 2 * q.i + (cls >> 1), iw = 2 * q.j + (cls & 1);
+    const uint32_t po = (uint32_t)((ih * 20 + iw) * 32 + (col & 31)) * 4u;
     float d[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       d[r] = row + r < B && pr.m[r] > 0.0f ? v[r] : 0.0f;
-      if (row + r < B && ((pr.nb >> (8 * r)) & 0xFFu) != 0u) dz1[((size_t)((row + r) * 20 + ih) * 20 + iw) * 32 + (col & 31)] = d[r];
+      if (row + r < B && ((pr.nb >> (8 * r)) & 0xFFu) != 0u) st_off(dz1, (uint32_t)(row + r) * 51200u + po, d[r]);
     }
     if (pb) {   // (uniform: every lane of the wave takes part in the exchanges)
       const float s = pb_sum16(d);
@@ -1652,6 +1667,17 @@ struct PConvWgrad {
                 "compacted weight gradient: packed table entries");
   __host__ __device__ int kept_in(int z) const {   // CMP: the chunk's non-background rows
     int n = 0;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(QLX_Q32_POLICIES_ONLY)
+    // (device: the chunk's SC x 4 row words in one load, one per lane, counted from the lanes - see StreamsCmp::prepare)
+    if constexpr (CMP) {
+      static_assert(SC * 4 == 64, "compacted weight gradient: a chunk's row words are one wave's lanes");
+      const int wl = threadIdx.x & 63;
+      const uint32_t wv = z * SC + (wl >> 2) < B && (wl & 3) != 3 ? rows[(size_t)z * SC * 4 + wl] : 0u;
+      for (int l = 0; l < 64; ++l)
+        if ((l & 3) != 3) n += __builtin_popcount(__builtin_amdgcn_readlane(wv, l));
+      return n;
+    }
+#endif
     for (int bl = 0; bl < SC; ++bl) {
       const int b = z * SC + bl;
       if (b < B) n += __builtin_popcount(rows[(size_t)b * 4]) + __builtin_popcount(rows[(size_t)b * 4 + 1]) +
@@ -1716,10 +1742,24 @@ struct PConvWgrad {
     __device__ void prepare(float* lds, int ns) {
       uint32_t* t = reinterpret_cast<uint32_t*>(lds);
       int run = 0;   // kept rows of the samples before bl (uniform)
+      // The chunk's row words are SC x 4 = one per lane: one load, sample bl's words read from lanes 4 bl .. 4 bl + 2 (a
+      // sample past B has none: nothing kept).  A load per sample was a chain of 16 memory round trips, each waited out
+      // before the next, ahead of every tile's first slab (and a second such chain in kept_in): with both as one load each,
+      // conv2 / conv3 pairs 68.8 / 61.8 -> 67.0 / 60.4 us (B = 1024, C3, profiled runs).
+#ifndef QLX_Q32_POLICIES_ONLY
+      static_assert(SC * 4 == 64, "compacted weight gradient: a chunk's row words are one wave's lanes");
+      const int wl = a.tid & 63;
+      const uint32_t wv = z * SC + (wl >> 2) < B ? rows[(size_t)z * SC * 4 + wl] : 0u;
+#endif
       for (int bl = 0; bl < SC; ++bl) {
-        const int b = z * SC + bl;
-        if (b >= B) break;
-        const uint32_t w0 = rows[(size_t)b * 4], w1 = rows[(size_t)b * 4 + 1], w2 = rows[(size_t)b * 4 + 2];
+#ifdef QLX_Q32_POLICIES_ONLY
+        const int b = z * SC + bl;   // (host address replay: from memory)
+        const uint32_t w0 = b < B ? rows[(size_t)b * 4] : 0u, w1 = b < B ? rows[(size_t)b * 4 + 1] : 0u,
+                       w2 = b < B ? rows[(size_t)b * 4 + 2] : 0u;
+#else
+        const uint32_t w0 = __builtin_amdgcn_readlane(wv, 4 * bl), w1 = __builtin_amdgcn_readlane(wv, 4 * bl + 1),
+                       w2 = __builtin_amdgcn_readlane(wv, 4 * bl + 2);
+#endif
         for (int pp = a.tid; pp < P; pp += T) {
           const uint32_t w = pp < 32 ? w0 : (pp < 64 ? w1 : w2), bit = 1u << (pp & 31);
           if (w & bit) {
@@ -2024,7 +2064,16 @@ __device__ __forceinline__ void c1_steps(const uint32_t* rm, uint32_t* out, uint
 __device__ __forceinline__ bool c1_step_set(unsigned long long lo, unsigned long long hi, int st) {
   return ((st < 64 ? lo >> st : hi >> (st - 64)) & 1ull) != 0ull;
 }
-
+// A sample's live conv1 forward tiles (k_conv1_fwd32: tile t = output rows 4 (t / 5) .. + 3, columns 4 (t % 5) .. + 3, whose
+// 8 x 8 patches at stride 4 cover the 5 x 5 blocks from (4 (t / 5), 4 (t % 5))): bit t is set when one of those blocks is
+// marked.  A clear bit means all 16 step ballots of the tile are zero in every wave.  One ballot, the same in every wave.
+__device__ __forceinline__ uint32_t c1_tiles(const uint32_t* rm, int lane) {
+  const int t = lane < 25 ? lane : 0, bx = 4 * (t / 5), by = 4 * (t % 5);
+  uint32_t mm = 0;
+#pragma unroll
+  for (int r = 0; r < 5; ++r) mm |= rm[bx + r];
+  return (uint32_t)__builtin_amdgcn_ballot_w64(lane < 25 && ((mm >> by) & 0x1Fu) != 0u);
+}
 // a sample's row flags, one wave's share (waves 0, 1: conv2 rows p = tid; wave 2: conv3 rows p = tid - 128), as two
 // ballots (non-background / background rows) stored in LDS at the end of the sample's iteration; the list entries are
 // claimed and written once per wave after the block's last sample (c1_lists_flush), so no atomic's round trip is waited
@@ -2121,39 +2170,56 @@ __device__ __forceinline__ void c1_lists_flush(const unsigned long long* cl, int
 // tile's 16 frame dwords are read while this tile multiplies (against the kq-outer loop over all 13 accumulators: 49.1 ->
 // 47.9 us at B = 1024, 320 -> 309 us per 8,192-sample chunk, 256 -> 218 VGPRs; gpurun_out/w4).  One branch per (kq, tile)
 // with its four kw steps back to back (a branch per MFMA: 60 vs 46 us at C3)
-__device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t (&ob2)[7], int nt, int rp, int g, int col,
-                                              const float (&wf)[64], float bias, int skip, float* a1, int b) {
+__device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, uint32_t lb, int nt, int rp, int g, int col,
+                                              const float (&wf)[64], float bias, int skip, uint32_t live, float* a1, int b) {
   {
-    uint32_t dn[16];
+    const unsigned long long every = skip == 0 ? ~0ull : 0ull;   // or-ed into the step ballots: every step issued
+    auto tile_live = [&](int j) { return ((live >> (rp + 2 * j)) & 1u) != 0u; };   // wave-uniform (c1_tiles)
+    // tile t's dwords at the lane's base lb (its ring slot and tile row) plus a wave-uniform offset: one add per tile
     auto tile_dwords = [&](int j, uint32_t (&d)[16]) {
-      const uint32_t base = (ob2[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+      const int t = rp + 2 * j;
+      const uint32_t base = lb + (uint32_t)((t / 5) * (16 * 21) + (t % 5) * 4);
 #pragma unroll
       for (int kq = 0; kq < 16; ++kq) d[kq] = fr[base + (kq >> 1) * 21 + (kq & 1)];   // (kh, kw half): pixels (4 oh + kh, 4 ow + 4 hw ..)
     };
-    tile_dwords(0, dn);
-#pragma unroll
-    for (int j = 0; j < 13; ++j)
-      if (j < nt) {
-        uint32_t d[16];
-#pragma unroll
-        for (int kq = 0; kq < 16; ++kq) d[kq] = dn[kq];
+    // the lane's share of a store address (row g of the patch, its channel); the tile's share is wave-uniform, so a store
+    // is a scalar base, this offset and an immediate
+    const uint32_t so = (uint32_t)(g * 20 * 32 + col);
+    const float zb = relu(0.0f + bias);
+    // tile j from d, the next tile's dwords into dn
+    auto tile = [&](int j, const uint32_t (&d)[16], uint32_t (&dn)[16]) {
+      // A tile whose 20 x 20 pixel field is all 0 (live bit clear) has 16 zero ballots: its LDS reads, ballots and
+      // branches are passed over with one scalar test, and its rows are zb = relu(0 + bias), what the empty chain gives.
+      const bool lv = tile_live(j), nx = j + 1 < nt && tile_live(j + 1);
+      const int t = rp + 2 * j;   // rows (oh, ow .. ow + 3) of the patch, oh = 4 (t / 5) + g, ow = 4 (t % 5)
+      float* at = a1 + ((size_t)b * 400 + 80 * (t / 5) + 4 * (t % 5)) * 32;
+      if (lv) {
         // the tile's 16 step masks are taken before the next tile's LDS reads are issued, so no branch merge of the MFMA
         // chain waits for those reads (masks interleaved with the chain: the compiler put lgkmcnt(0) at the merges, 48.2 vs
         // 46.7 us at B = 1024; with the short-circuit form of the mask, a branch per mask: 46.7 vs 42.7 us)
         bool nz[16];
 #pragma unroll
-        for (int kq = 0; kq < 16; ++kq) nz[kq] = (__builtin_amdgcn_ballot_w64(d[kq] != 0u) != 0) | (skip == 0);   // wave-uniform, no branch
-        if (j + 1 < nt) tile_dwords(j + 1, dn);
+        for (int kq = 0; kq < 16; ++kq) nz[kq] = (__builtin_amdgcn_ballot_w64(d[kq] != 0u) | every) != 0ull;   // wave-uniform, no branch
+        if (nx) tile_dwords(j + 1, dn);
         f32x4 acc = zero4();
 #pragma unroll
         for (int kq = 0; kq < 16; ++kq)
           if (nz[kq])
 #pragma unroll
             for (int kw = 0; kw < 4; ++kw) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ubyte(d[kq], kw), wf[kq * 4 + kw], acc, 0, 0, 0);
-        const int t = rp + 2 * j, r0 = (4 * (t / 5) + g) * 20 + 4 * (t % 5);   // rows (oh, ow .. ow + 3) of the patch
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a1[((size_t)b * 400 + r0 + i) * 32 + col] = relu(acc[i] + bias);
+        for (int i = 0; i < 4; ++i) at[so + 32u * i] = relu(acc[i] + bias);
+      } else {
+        if (nx) tile_dwords(j + 1, dn);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) at[so + 32u * i] = zb;
       }
+    };
+    uint32_t dd[14][16];   // (a buffer per tile, read only when it was loaded: no tile copies or keeps another's dwords)
+    if (tile_live(0)) tile_dwords(0, dd[0]);
+#pragma unroll
+    for (int j = 0; j < 13; ++j)
+      if (j < nt) tile(j, dd[j], dd[j + 1]);
   }
 }
 
@@ -2165,6 +2231,11 @@ __device__ __forceinline__ void c1_fwd_sample(const uint32_t* fr, const uint32_t
 // every chain as it is (a chain from +0 never holds -0: x + (-x) and +0 + -0 round to +0), so it is not issued.  The
 // frames are mostly background (0), and a patch tile's receptive field (20 x 20 pixels per frame) is often all of it
 // (~70 % of the steps at C3), where a tile of 16 consecutive positions crosses the side walls.  Exact for finite W0.
+// Zero tiles: a tile none of whose 5 x 5 blocks is marked (c1_tiles, from the row masks the staging already builds; about
+// two thirds of the tiles at C3) skips its 16 LDS reads, ballots and branches as a whole and stores relu(0 + b0).  With
+// it, each tile's LDS base and store base are a lane part plus a wave-uniform part (one add, no per-store 64-bit
+// arithmetic), and a tile's dwords live in a buffer of their own instead of being copied out of the read-ahead buffer:
+// 37.4 -> 33.5 us at B = 1024, 270 -> 232 us per 8,192-sample chunk (profiled runs, C3); the MFMAs are the same.
 // ROLE only names the instantiation (0: training batches, 1: chunk-size target / acting passes), so a kernel trace
 // tells the two launch shapes apart.
 // ONE (round 6, the training batch): one sample per block, grid = B.  The persistent form (two blocks per CU, each block's
@@ -2196,16 +2267,8 @@ __global__ __launch_bounds__(256, ONE ? kC1OneMinW : 2) void k_conv1_fwd32(const
 #pragma unroll
   for (int kk = 0; kk < 64; ++kk) wf[kk] = w0[(kk * 4 + g) * 32 + col];
   const float bias = b0[col];
-  // dword offsets of the lane's 13 tile rows (lane group g reads ring slot g), two 16-bit offsets per register
-  uint32_t ob2[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) ob2[j] = 0;
-#pragma unroll
-  for (int j = 0; j < 13; ++j) {
-    const int t = rp + 2 * j < 25 ? rp + 2 * j : 0, l = lane & 15;
-    const int oh = 4 * (t / 5) + (l >> 2), ow = 4 * (t % 5) + (l & 3);
-    ob2[j >> 1] |= (uint32_t)(g * kC1SlotDw + 4 * oh * 21 + ow) << (16 * (j & 1));
-  }
+  // dword offset of the lane's row (l >> 2, l & 3) of tile 0 (lane group g reads ring slot g)
+  const uint32_t lb = (uint32_t)(g * kC1SlotDw + 4 * ((lane & 15) >> 2) * 21 + (lane & 3));
   const int nt = rp == 0 ? 13 : 12;
   int b = blockIdx.x;
   if (b >= B) return;
@@ -2217,7 +2280,7 @@ __global__ __launch_bounds__(256, ONE ? kC1OneMinW : 2) void k_conv1_fwd32(const
       if (marks) c1_mark(rm, pf);
     }
     __syncthreads();
-    c1_fwd_sample(c1w, ob2, nt, rp, g, col, wf, bias, skip, a1, b);
+    c1_fwd_sample(c1w, lb, nt, rp, g, col, wf, bias, skip, marks && skip != 0 ? c1_tiles(rm, lane) : ~0u, a1, b);
     if (marks) {
       if (wave < 3) c1_flags(rm, cl + wave * 2, wave, L, b);
       else if (L.steps) c1_steps(rm, L.steps + (size_t)b * 4, L.need, L.need_ld, b, lane);
@@ -2246,7 +2309,8 @@ __global__ __launch_bounds__(256, ONE ? kC1OneMinW : 2) void k_conv1_fwd32(const
     // iteration); (it + 1) % 3 gets the next sample's at the end of this iteration; (it + 2) % 3, read at the end of
     // it - 1, is cleared for it + 1
     if (marks && wave == 3 && tid - 192 < kC1RmDw) rm[((it + 2) % 3) * kC1RmDw + tid - 192] = 0u;
-    c1_fwd_sample(fr, ob2, nt, rp, g, col, wf, bias, skip, a1, b);
+    c1_fwd_sample(fr, lb, nt, rp, g, col, wf, bias, skip, marks && skip != 0 ? c1_tiles(rm + (it % 3) * kC1RmDw, lane) : ~0u, a1,
+                  b);
     if (marks && wave < 3) c1_flags(rm + (it % 3) * kC1RmDw, cl + it * 6 + wave * 2, wave, L, b);
     if (marks && wave == 3 && L.steps) c1_steps(rm + (it % 3) * kC1RmDw, L.steps + (size_t)b * 4, L.need, L.need_ld, b, lane);
     if (nb < B) {
@@ -2293,6 +2357,8 @@ __global__ __launch_bounds__(kC1WgradThreads, 2) void k_conv1_wgrad32(const uint
   // this lane's A row rho = l15: kh = 2 wq + rho / 8, h = (rho / 4) % 2, c = rho % 4; dword of (x = 4 oh + kh, y / 4 = ow + h)
   const int ao = (l15 & 3) * kC1WgSlotDw + (2 * wq + (l15 >> 3)) * 21 + ((l15 >> 2) & 1);
   const int bo = hh * 16 + l15;   // the lane's dz1 column
+  const int pxo = ao + g, dzo = hh * 6400 + g * 16 + l15;   // the lane's frame dword / dz1 value of position r = g (rd below)
+  const unsigned long long every = skip == 0 ? ~0ull : 0ull;   // or-ed into the step ballots: every step issued
   // dz1 in LDS as two [400][16] channel halves: a step's reads (rows r, r + 1 on lane groups g, g + 1; 16 channels each) are
   // 32 consecutive dwords - conflict-free (a [400][32] image puts both rows on the same 16 banks: 2-way)
 
@@ -2373,20 +2439,22 @@ __global__ __launch_bounds__(kC1WgradThreads, 2) void k_conv1_wgrad32(const uint
     // masks: 36.4 us.)  Same MFMAs on the same operands in the same order: bit-identical slabs.
     constexpr int GS = 5, NG = 100 / GS;
     static_assert(NG % 2 == 0 && NG * GS == 100, "conv1 weight gradient: operand groups");
+    static_assert(GS == 5, "conv1 weight gradient: a group is one output row");
     float bA[GS], bB[GS];
     uint32_t xA[GS], xB[GS];
+    // A group of 5 steps is one output row: step 5 grp + j, lane group g is position r = 20 grp + 4 j + g, i.e. oh = grp,
+    // ow = 4 j + g, so both LDS addresses are a lane base (pxo, dzo) plus compile-time offsets.
     auto rd = [&](int grp, float (&bv)[GS], uint32_t (&px)[GS]) {
 #pragma unroll
       for (int j = 0; j < GS; ++j) {
-        const int r = 4 * (grp * GS + j) + g, oh = r / 20, ow = r - oh * 20;
-        bv[j] = dzs[hh * 6400 + r * 16 + l15];
-        px[j] = c1w[ao + 84 * oh + ow];
+        bv[j] = dzs[dzo + grp * 320 + j * 64];
+        px[j] = c1w[pxo + grp * 84 + j * 4];
       }
     };
     auto run = [&](const float (&bv)[GS], const uint32_t (&px)[GS]) {
       bool nz[GS];
 #pragma unroll
-      for (int j = 0; j < GS; ++j) nz[j] = (__builtin_amdgcn_ballot_w64(px[j] != 0u) != 0) | (skip == 0);   // wave-uniform, no branch
+      for (int j = 0; j < GS; ++j) nz[j] = (__builtin_amdgcn_ballot_w64(px[j] != 0u) | every) != 0ull;   // wave-uniform, no branch
 #pragma unroll
       for (int j = 0; j < GS; ++j) {
         // all 64 x 4 frame values 0: the step adds +-0 (see the forward)
@@ -2395,7 +2463,11 @@ __global__ __launch_bounds__(kC1WgradThreads, 2) void k_conv1_wgrad32(const uint
           for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ubyte(px[j], t), bv[j], acc[t], 0, 0, 0);
       }
     };
+    // (Passing over a group whose five bits of the sample's step mask are clear with one scalar test - its ballots and
+    // branches only, or its LDS reads too - is exact but no faster: 26.5 us without, 26.6 / 27.2 us with, B = 1024 at C3,
+    // against 27.7 us before the addresses took this form.  A guarded read also makes the next merge wait for every read.)
     rd(0, bA, xA);
+#pragma unroll
     for (int grp = 0; grp < NG; grp += 2) {
       rd(grp + 1, bB, xB);
       run(bA, xA);
