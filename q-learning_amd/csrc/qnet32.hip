@@ -625,6 +625,8 @@ void f32_destroy(qlx_model* m) {
 void f32_workspace(qlx_model* m, int B) {
   F32Net& w = *m->fp32;
   const int C = std::min(B, kF32FwdChunk);   // conv activations are held per forward chunk
+  // (the operand streams' lane offsets are 32-bit and kOob = 2^31 has to lie past every descriptor: a1 is the largest)
+  static_assert((uint64_t)kF32FwdChunk * 12800 * 4 < 0x80000000ull, "a forward chunk's a1 stays below 2^31 bytes");
   int nseg = 0;
   for (int v = 0; v < kNumVars; ++v) nseg += segs_of(v);
   // row lists: kListSlots regions of ceil(G / kListSlots) blocks x ceil(n / G) samples each (G = c1_blocks(n) for a chunk of
@@ -814,15 +816,12 @@ void f32_forward(qlx_model* m, const uint8_t* const* table, int B, hipStream_t s
         using P2 = decltype(t2);
         using P3 = decltype(t3);
         // the constant rows' chains in the conv2 launch's first block
-        using PC2 = PConv2FwdL<16, 64, 1, 4>;
-        using PC3 = PConv3FwdL<16, 64, 1, 4>;
-        const ConstRows<PC2, PC3> cr{PC2{Grid{1, 1, 1}, w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, c2},
-                                     PC3{Grid{1, 1, 1}, w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, c3}};
-        // (the list tiles start at row tile 1; row tile 0, the constant row, is ConstRows' work: its blocks return)
-        P2 p2{lgrid(cap2, P2::BM, P2::BN), w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, w.frl2, cap2, cnt, w.fbgc, nullptr};
+        const ConstRows cr{{w.fbgc, p + var_offset(2), p + var_offset(3), c2}, {c2, p + var_offset(4), p + var_offset(5), c3}};
+        // (the list tiles start at row tile 1; row tile 0 is reserved: its blocks return)
+        P2 p2{lgrid(cap2, P2::BM, P2::BN), w.fa1, p + var_offset(2), p + var_offset(3), w.fa2, w.frl2, cap2, cnt, w.fbgc};
         p2.pre_batched = big;
         launch_list(m, p2, cr, sc2, 2.0 * n * 81 * 64 * 512, s);
-        launch_list(m, P3{lgrid(cap3, P3::BM, P3::BN), w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2, nullptr},
+        launch_list(m, P3{lgrid(cap3, P3::BM, P3::BN), w.fa2, p + var_offset(4), p + var_offset(5), w.fa3, w.frl3, cap3, cnt + kCntStride, c2},
                     s23, sc3, 2.0 * n * 49 * 64 * 576, s);
       };
       if (big) {

@@ -1,8 +1,8 @@
 // fp32 Nature-DQN kernels for gfx950: the reference's arithmetic (Keras float32 graph,
 // create_ql_model_breakout_84x84x4_3_32.py:20-33,37-61) on v_mfma_f32_16x16x4_f32.
 //
-// Every GEMM-shaped op is one LDS-tiled implicit-GEMM kernel driven by a per-layer operand policy, which describes its
-// operand addresses once: as streams (gemm_body_s), or as ldA / ldB (gemm_body: the dense-frame forward, the constant rows).
+// Every GEMM-shaped op is one LDS-tiled implicit-GEMM kernel (gemm_body) driven by a per-layer operand policy, which
+// describes its operand addresses once, as operand streams.
 // v_mfma_f32_16x16x4_f32 is bit-for-bit a k-ordered fmaf chain over its four k (lane group 0 first; measured on
 // MI355X, scripts/mfma_f32_probe.hip), and each output element keeps ONE accumulator over the whole reduction,
 // consumed in ascending k.  So every output is exactly
@@ -89,7 +89,7 @@ struct Opnd {
 // ds_read_b128, KMAJ operands one ds_read_b32 per k step).  bsum (DB): the B fragments' running column sums (bias chains).
 template <class OA, class OB, int TM, int TN, bool DB, class Acc>
 __device__ __forceinline__ void slab_mfma16(const float* a, const float* b, int wm, int wn, int lane, Acc (&acc)[TM][TN],
-                                            float (&bsum)[TN], bool do_bias = true) {
+                                            float (&bsum)[TN]) {
   constexpr int MF = 16;
 #pragma unroll
   for (int h = 0; h < BK / 16; ++h) {
@@ -114,11 +114,9 @@ __device__ __forceinline__ void slab_mfma16(const float* a, const float* b, int 
         if constexpr (OB::P8) bf[j] = b4[j][q];
         else bf[j] = OB::frag(b, (wn * TN + j) * MF, kk, lane);
       }
-      if constexpr (DB) {
-        if (do_bias)
+      if constexpr (DB)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) bsum[j] = __fadd_rn(bsum[j], bf[j]);
-      }
+        for (int j = 0; j < TN; ++j) bsum[j] = __fadd_rn(bsum[j], bf[j]);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -142,11 +140,10 @@ struct KSeqOf<P, std::void_t<decltype(P::KSEQ)>> : std::integral_constant<int, P
 
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-// Masked operand load for the policies: masked lanes load 16 zero bytes from q32_zero4, so the load is issued on every
-// path and nothing waits on its value before it is stored.  A branch around a load makes the compiler's vmcnt
-// bookkeeping path-dependent (it then waits for every outstanding load - including the next slab's - before storing
-// the current one), and a select on the loaded value pulls the wait up to the select; either collapses gemm_body's
-// two-slabs-in-flight register pipeline.
+// 16 zero bytes for a masked load (conv1's null frames, ldg_frame): the masked lanes load them, so the load is issued on
+// every path and nothing waits on its value before it is stored.  A branch around a load makes the compiler's vmcnt
+// bookkeeping path-dependent (it then waits for every outstanding load before storing the current one), and a select on
+// the loaded value pulls the wait up to the select.
 #ifdef QLX_Q32_POLICIES_ONLY
 static const float q32_zero4[4] __attribute__((aligned(16))) = {0.0f, 0.0f, 0.0f, 0.0f};
 #else
@@ -154,7 +151,6 @@ static const float q32_zero4[4] __attribute__((aligned(16))) = {0.0f, 0.0f, 0.0f
 // flat load, which also counts on lgkmcnt and so joins every LDS wait)
 static __attribute__((device)) float q32_zero4[4] __attribute__((aligned(16))) = {0.0f, 0.0f, 0.0f, 0.0f};
 #endif
-__device__ __forceinline__ f32x4 ld4m(const float* p, bool ok) { return ld4(ok ? p : q32_zero4); }
 // a value the caller knows to be equal on every lane, as a wave-uniform (scalar) value; the identity in the host replay of
 // the policies (scripts/q32_host_check.hip, QLX_Q32_POLICIES_ONLY)
 __device__ __forceinline__ int q32_uniform(int x) {
@@ -207,20 +203,6 @@ template <class P>
 struct LoadFenceOf<P, std::void_t<decltype(P::LOAD_FENCE)>> : std::integral_constant<bool, P::LOAD_FENCE> {};
 
 
-// Optional per-tile A-operand context: a policy with a member type ACtx provides
-//   ACtx a_ctx(int z, int row0, int tid) const                       once per tile, per thread (e.g. the frame pointers of its rows)
-//   f32x4 ldA_c(const ACtx&, int i, int z, int s, int row, int k) const    instead of ldA (i = the thread's load index)
-// so loop-invariant pointer loads (frame tables) leave the slab loop: one memory latency per slab, not two.
-template <class P, class = void>
-struct HasACtx : std::false_type {};
-template <class P>
-struct HasACtx<P, std::void_t<typename P::ACtx>> : std::true_type {};
-struct NoCtx {};
-template <class P, bool = HasACtx<P>::value>
-struct ACtxOf { using type = NoCtx; };
-template <class P>
-struct ACtxOf<P, true> { using type = typename P::ACtx; };
-
 // Optional early epilogue operands: a policy with epi_pre(z, row, col) -> f32x4 (e.g. the ReLU mask
 // values of its four rows) and epi_post(z, row, col, acc, pre) has epi_pre's loads issued before the slab loop, so the
 // epilogue waits on nothing (a load issued after the loop would wait behind every slab load still in flight).
@@ -239,209 +221,6 @@ template <class P, class = void>
 struct HasActive : std::false_type {};
 template <class P>
 struct HasActive<P, std::void_t<decltype(std::declval<const P&>().active(0, 0))>> : std::true_type {};
-
-// One output tile of a policy P (see the policies below for the members it provides):
-//   acc[row][col] = sum over the slabs s = 0 .. nslabs(z) - 1 and k = 0 .. 31 of A(z, s, row, k) * B(z, s, col, k),
-// one fmaf chain per output in (s, k) order; then P::epi stores it.  With P::BIAS the tiles of row-tile 0 also
-// sum B's columns (bias gradient): four chains over the reduction index mod 4, combined ((C0 + C1) + C2) + C3.
-// With P::KSPLIT = G > 1 the block runs G wave groups, group g chaining the slabs [g ns / G, (g + 1) ns / G) into its
-// own accumulators (own LDS buffers, the same barriers); the tile is then ((C0 + C1) + ..) + C(G-1), summed by group 0
-// through LDS before its epilogue (ns must be a multiple of G).
-template <class P>
-__device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
-  constexpr int MF = 16;
-  using OA = Opnd<P::BM, P::A_KMAJ>;
-  using OB = Opnd<P::BN, P::B_KMAJ>;
-  using Acc = f32x4;
-  constexpr int G = KSplitOf<P>::value;
-  static_assert(G == 1 || !P::BIAS, "K-split groups: no bias chains");
-  constexpr int T = P::WM * P::WN * 64;   // threads of one K group
-  constexpr int TM = P::BM / (P::WM * MF), TN = P::BN / (P::WN * MF);
-  static_assert(TM >= 1 && TN >= 1 && TM * P::WM * MF == P::BM && TN * P::WN * MF == P::BN, "tile shape");
-  constexpr int NA = (OA::F4 + T - 1) / T, NB = (OB::F4 + T - 1) / T;
-  constexpr int GROUP_LDS = 2 * (OA::FLOATS + OB::FLOATS);
-  static_assert(G == 1 || TM * TN * 4 * T <= GROUP_LDS, "K-split hand-off fits the group's LDS");
-  const int kg = G > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6) / (P::WM * P::WN)) : 0;
-  const int tid = threadIdx.x - kg * T, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave % P::WM, wn = wave / P::WM;
-  int tm, tn, z;
-  p.decode(lb, tm, tn, z);
-  const int row0 = tm * P::BM, col0 = tn * P::BN;
-  if constexpr (HasActive<P>::value) {
-    if (!p.active(z, row0)) return;
-  }
-  const int ns = p.nslabs(z) / G, s_base = kg * ns;   // this group's slabs: s_base + [0, ns)
-  constexpr int Q = KSeqOf<P>::value;   // (KSEQ: see gemm_body_s)
-  static_assert(Q == 1 || (Q == 2 && G == 1 && !P::BIAS), "sequential K split: two chains, no bias");
-  const int s_half = Q > 1 ? ns / 2 : -1;
-  typename ACtxOf<P>::type actx{};
-  if constexpr (HasACtx<P>::value) actx = p.a_ctx(z, row0, tid);
-  lds += kg * GROUP_LDS;
-  float* As0 = lds;
-  float* As1 = lds + OA::FLOATS;
-  float* Bs0 = lds + 2 * OA::FLOATS;
-  float* Bs1 = Bs0 + OB::FLOATS;
-  // two register sets: slab s + 2 is in flight from global memory while slab s is multiplied from LDS and slab
-  // s + 1 waits in registers for its LDS buffer (two slabs of MFMA work cover a load's latency)
-  f32x4 ra0[NA], rb0[NB], ra1[NA], rb1[NB];
-  auto load = [&](int s, f32x4(&ra)[NA], f32x4(&rb)[NB]) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int idx = tid + i * T;
-      if (OA::F4 % T == 0 || idx < OA::F4) {
-        int r, k;
-        OA::coord(idx, r, k);
-        if constexpr (HasACtx<P>::value) ra[i] = p.ldA_c(actx, i, z, s_base + s, row0 + r, k);
-        else ra[i] = p.ldA(z, s_base + s, row0 + r, k);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int idx = tid + i * T;
-      if (OB::F4 % T == 0 || idx < OB::F4) {
-        int r, k;
-        OB::coord(idx, r, k);
-        rb[i] = p.ldB(z, s_base + s, col0 + r, k);
-      }
-    }
-  };
-  auto store = [&](int s, const f32x4(&ra)[NA], const f32x4(&rb)[NB]) {
-    float* as = (s & 1) ? As1 : As0;
-    float* bs = (s & 1) ? Bs1 : Bs0;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int idx = tid + i * T;
-      if (OA::F4 % T == 0 || idx < OA::F4) {
-        int r, k;
-        OA::coord(idx, r, k);
-        OA::put(as, r, k, ra[i]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int idx = tid + i * T;
-      if (OB::F4 % T == 0 || idx < OB::F4) {
-        int r, k;
-        OB::coord(idx, r, k);
-        OB::put(bs, r, k, rb[i]);
-      }
-    }
-  };
-  Acc acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
-  Acc first[Q > 1 ? TM : 1][Q > 1 ? TN : 1];   // KSEQ: the finished first chain
-  // bias (BIAS policies, row-tile 0): column sums of B as four interleaved chains - lane group q of the wave's B fragments
-  // chains the k = q mod 4 rows - combined in group order at the end
-  float bsum[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) bsum[j] = 0.0f;
-  const bool do_bias = P::BIAS && tm == 0 && wm == 0;
-  auto compute = [&](int s) {
-    const float* a = (s & 1) ? As1 : As0;
-    const float* b = (s & 1) ? Bs1 : Bs0;
-    if constexpr (Q > 1) {
-      if (s == s_half) {   // (wave-uniform) the first chain is done: keep it, start the second from zero
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            first[i][j] = acc[i][j];
-            acc[i][j] = zero4();
-          }
-      }
-    }
-    if constexpr (IglpOf<P>::value >= 0) __builtin_amdgcn_iglp_opt(IglpOf<P>::value);
-    slab_mfma16<OA, OB, TM, TN, P::BIAS>(a, b, wm, wn, lane, acc, bsum, do_bias);
-  };
-  // iteration s: x holds slab s + 1, y is free.  Every iteration issues its loads unconditionally (the last slab again
-  // past the end), so the number of loads in flight is the same on every path and the store of slab s + 1 waits only
-  // for slab s + 1's loads (vmcnt = this iteration's NA + NB), never for slab s + 2's (see ld4m)
-  auto iter = [&](int s, f32x4(&xa)[NA], f32x4(&xb)[NB], f32x4(&ya)[NA], f32x4(&yb)[NB]) {
-    load(s + 2 < ns ? s + 2 : ns - 1, ya, yb);
-    if constexpr (LoadFenceOf<P>::value) __builtin_amdgcn_sched_barrier(0);   // the loads stay ahead of the slab's MFMAs
-    compute(s);
-    store(s + 1, xa, xb);   // unconditional, as in gemm_body_s (past the last slab: the idle buffer, never read)
-    lds_barrier();
-  };
-  constexpr bool PRE = HasEpiPre<P>::value;
-  typename PreOf<P>::type pre[TM][TN];
-  if constexpr (PRE) {
-    if (kg == 0) {   // (K groups: group 0 runs the epilogue)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          pre[i][j] = p.epi_pre(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15));
-    }
-  }
-  if (ns > 0) {
-    load(0, ra1, rb1);
-    store(0, ra1, rb1);
-    load(ns > 1 ? 1 : 0, ra0, rb0);
-    lds_barrier();
-    int s = 0;
-    for (; s + 1 < ns; s += 2) {
-      iter(s, ra0, rb0, ra1, rb1);
-      iter(s + 1, ra1, rb1, ra0, rb0);
-    }
-    if (s < ns) iter(s, ra0, rb0, ra1, rb1);
-  }
-  if constexpr (Q > 1) {   // C0 + C1
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = __fadd_rn(ns > s_half ? first[i][j][e] : acc[i][j][e], ns > s_half ? acc[i][j][e] : 0.0f);
-  }
-  if constexpr (G > 1) {   // groups 1 .. G - 1 hand their accumulators to group 0 through their own LDS (free now)
-    constexpr int E = 4;
-    if (kg > 0) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < E; ++e) lds[((i * TN + j) * E + e) * T + tid] = acc[i][j][e];
-    }
-    __syncthreads();
-    if (kg > 0) return;
-#pragma unroll
-    for (int g = 1; g < G; ++g)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < E; ++e) acc[i][j][e] = __fadd_rn(acc[i][j][e], lds[g * GROUP_LDS + ((i * TN + j) * E + e) * T + tid]);
-  }
-  // accumulator layout: lane l holds rows 4 (l / 16) .. + 3 of column l % 16
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      if constexpr (PRE) {
-        p.epi_post(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), acc[i][j], pre[i][j]);
-      } else {
-        p.epi(z, row0 + (wm * TM + i) * 16 + (lane >> 4) * 4, col0 + (wn * TN + j) * 16 + (lane & 15), acc[i][j]);
-      }
-    }
-  if constexpr (P::BIAS) {
-    if (do_bias) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const float c1 = __shfl(bsum[j], lane + 16), c2 = __shfl(bsum[j], lane + 32), c3 = __shfl(bsum[j], lane + 48);
-        if (lane < 16) p.epi_bias(z, col0 + (wn * TN + j) * 16 + lane, __fadd_rn(__fadd_rn(__fadd_rn(bsum[j], c1), c2), c3));
-      }
-    }
-  }
-}
 
 // a policy with RAW_ORDER = true takes its blocks in hardware order (no XCD grouping)
 template <class P, class = void>
@@ -469,12 +248,12 @@ struct Grid {
 // Operand streams: slab staging with no per-slab vector address arithmetic.
 //
 // On gfx950 the fp32 MFMA and the VALU do not overlap: an MFMA loop and a VALU loop on one SIMD take the sum of their
-// times (scripts/coexec_probe.hip), so every vector instruction of a slab loop is MFMA time lost.  The ldA / ldB form
-// (gemm_body: the dense-frame forward and the constant-row tiles) recomputes each load's 64-bit address per slab (divisions,
-// masks, selects: 40 to 100 VALU instructions per slab of 32 MFMAs).  A stream computes its per-lane byte offsets once per
-// tile; per slab it adds a wave-uniform offset (SALU) and issues raw buffer loads, whose range check returns zeros for a
-// lane offset past the buffer (rows past the batch, gather rows past a chunk).  A streamed policy has no other description
-// of its operand addresses: the host address replay (scripts/q32_host_check.hip) runs these streams.
+// times (scripts/coexec_probe.hip), so every vector instruction of a slab loop is MFMA time lost.  (Recomputing each load's
+// 64-bit address per slab - divisions, masks, selects - cost 40 to 100 VALU instructions per slab of 32 MFMAs.)  A stream
+// computes its per-lane byte offsets once per tile; per slab it adds a wave-uniform offset (SALU) and issues raw buffer
+// loads, whose range check returns zeros for a lane offset past the buffer (rows past the batch, gather rows past a chunk).
+// The streams are a policy's only description of its operand addresses: the host address replay
+// (scripts/q32_host_check.hip) runs them.
 //   load(s, regs)  - issue the slab's loads (s wave-uniform)
 //   store(t, regs) - write them into the operand's LDS image t (the Opnd layout the fragment reads use)
 constexpr uint32_t kOob = 0x80000000u;   // lane offset past any buffer: the load returns zeros
@@ -667,21 +446,22 @@ constexpr size_t gemm_lds_bytes() {
          ExtraLdsOf<P>::value;
 }
 
-// Stream form of gemm_body (policies with a member type Streams): the same pipeline, fragments, MFMA chains, bias chains
-// and epilogue, with the slab staging done by the policy's streams:
+// One output tile of a policy P (see the policies below for the members it provides):
+//   acc[row][col] = sum over the slabs s = 0 .. nslabs(z) - 1 and k = 0 .. 31 of A(z, s, row, k) * B(z, s, col, k),
+// one fmaf chain per output in (s, k) order; then P::epi (or epi_pre / epi_post) stores it.  The slab staging is the
+// policy's streams':
 //   typename P::Streams st = p.streams(z, row0, col0, tid);   per tile
-//   st.load(s, x) / st.store(s, x, As, Bs)                    x: a P::Streams::Regs register set
-template <class P, class = void>
-struct HasStreams : std::false_type {};
-template <class P>
-struct HasStreams<P, std::void_t<typename P::Streams>> : std::true_type {};
-
+//   st.load(s, x) / st.store(As, Bs, x)                       x: a P::Streams::Regs register set
+// Pipeline: two LDS buffers and two register sets - slab s + 2 is in flight from global memory while slab s is multiplied
+// from LDS and slab s + 1 waits in registers for its LDS buffer (two slabs of MFMA work cover a load's latency).
+// With P::BIAS the tiles of row-tile 0 also sum B's columns (bias gradient): four chains over the reduction index mod 4 -
+// lane group q of the wave's B fragments chains the k = q mod 4 rows - combined ((C0 + C1) + C2) + C3.
 // K split (round 6, policies with KSPLIT = G > 1 or KSEQ = Q > 1): the reduction is G (Q) chains over consecutive equal
 // slab ranges, combined ((C0 + C1) + ..) before the epilogue - the same value either way: KSPLIT runs the chains in G
-// wave groups of the block at once (group 0 sums them through LDS), KSEQ one after another in the same waves (the
-// finished chains wait in registers).  ns must be a multiple of G (Q).
+// wave groups of the block at once (each with its own LDS buffers, the same barriers; group 0 sums them through LDS),
+// KSEQ one after another in the same waves (the finished chains wait in registers).  ns must be a multiple of G (Q).
 template <class P>
-__device__ __forceinline__ void gemm_body_s(const P& p, int lb, float* lds) {
+__device__ __forceinline__ void gemm_body(const P& p, int lb, float* lds) {
   constexpr int MF = 16;
   using OA = Opnd<P::BM, P::A_KMAJ>;
   using OB = Opnd<P::BN, P::B_KMAJ>;
@@ -749,10 +529,12 @@ __device__ __forceinline__ void gemm_body_s(const P& p, int lb, float* lds) {
       if constexpr (IglpOf<P>::value >= 0) __builtin_amdgcn_iglp_opt(IglpOf<P>::value);
       slab_mfma16<OA, OB, TM, TN, DB>(a, b, wm, wn, lane, acc, bsum);
     };
-    // (the store of slab s + 1 is unconditional: past the last slab it writes the idle buffer with the reloaded last slab,
-    // which nothing reads.  Skipped there, its registers' loads stayed pending on that path, and the compiler - which does
-    // not see that the path leaves the loop - waited for them at the top of every other slab step: the two register sets
-    // degenerated to one.)
+    // Slab step s: xs holds slab s + 1, ys is free.  Every step issues its loads (the last slab again past the end) and the
+    // store of slab s + 1 unconditionally: past the last slab the store writes the idle buffer with the reloaded last slab,
+    // which nothing reads.  So the number of loads in flight is the same on every path and the store waits only for slab
+    // s + 1's loads, never for slab s + 2's.  (With the store skipped there, its registers' loads stayed pending on that
+    // path, and the compiler - which does not see that the path leaves the loop - waited for them at the top of every other
+    // slab step: the two register sets degenerated to one.)
     auto iter = [&](int s, Regs& xs, Regs& ys) {
       st.load(s_base + (s + 2 < ns ? s + 2 : ns - 1), ys);
       if constexpr (LoadFenceOf<P>::value) __builtin_amdgcn_sched_barrier(0);
@@ -839,11 +621,10 @@ __device__ __forceinline__ void gemm_body_s(const P& p, int lb, float* lds) {
   }
 }
 
+// (the launches call through this level: calling gemm_body directly changes the inlining order, and with it the code of
+// every kernel)
 template <class P>
-__device__ __forceinline__ void body(const P& p, int lb, float* lds) {
-  if constexpr (HasStreams<P>::value) gemm_body_s(p, lb, lds);
-  else gemm_body(p, lb, lds);
-}
+__device__ __forceinline__ void body(const P& p, int lb, float* lds) { gemm_body(p, lb, lds); }
 
 template <class P>
 __global__ __launch_bounds__(threads_of<P>()) void k_gemm32(const P p) {
@@ -942,7 +723,46 @@ struct NoSide {
 #define QLX_CONV_FWD_CHAINS 1
 constexpr int kConvFwdChains = QLX_CONV_FWD_CHAINS;
 static_assert(kConvFwdChains == 1, "conv forward policies: one chain per output");
-// conv2 / conv3 forward on fp32 NHWC input: out = relu(conv + bias); slab s: tap = 32 s / C, c0 = 32 s % C
+// Streams of a conv forward tile on fp32 NHWC input [..][W][C]: A = the rows' im2col windows - a row's lane offset is its
+// window's first element (kOob: no row), a slab's tap and channel offset (tap = 32 s / C, c0 = 32 s % C) wave-uniform; SEL
+// (the list forward's conv3): the taps in a row's mask msk read the constant row at cxo instead, a per-lane select per
+// slab.  B = the weight rows [KS][KS][C][OC], affine.  The policy fills a.rs, a.vo (SEL: cxo, msk) and b.
+template <int W, int C, int KS, int OC, int BM, int BN, int T, bool SEL = false>
+struct ConvFwdStreams {
+  using SA = AffineStream<BM, false, T>;
+  using SB = AffineStream<BN, true, T>;
+  SA a;
+  SB b;
+  uint32_t cxo[SA::N], msk[SA::N];   // (SEL)
+  struct Regs {
+    typename SA::Regs a;
+    typename SB::Regs b;
+  };
+  __device__ void load(int s, Regs& x) const {
+    const int tap = (s * BK) / C, c0 = (s * BK) % C, kh = tap / KS, kw = tap - kh * KS;
+    const uint32_t so = (uint32_t)((kh * W + kw) * C + c0) * 4u;
+    if constexpr (SEL) {
+#pragma unroll
+      for (int i = 0; i < SA::N; ++i)
+        if (SA::O::F4 % T == 0 || a.tid + i * T < SA::O::F4) {
+          const bool cst = (msk[i] >> tap) & 1u;
+          x.a[i] = buf_ld4(a.rs, cst ? cxo[i] + (uint32_t)c0 * 4u : a.vo[i] + so, 0u);
+        }
+    } else {
+      a.load(so, 0, x.a);
+    }
+    b.load((uint32_t)s * BK * OC * 4u, 0, x.b);
+  }
+  __device__ void store(float* as, float* bs, const Regs& x) const {
+    a.store(as, x.a);
+    b.store(bs, x.b);
+  }
+  __device__ void init_b(const float* w, int col0, int tid) {
+    b.init(w, (uint32_t)KS * KS * C * OC * 4u, tid, [col0](int r, int k) { return (uint32_t)(k * OC + col0 + r) * 4u; });
+  }
+};
+
+// conv2 / conv3 forward on fp32 NHWC input: out = relu(conv + bias)
 template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2>
 struct PConvFwd {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
@@ -957,14 +777,19 @@ struct PConvFwd {
   int M;             // B * OH * OW
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return KS * KS * C / BK; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const {
-    const bool ok = row < M;
-    const int rr = ok ? row : 0;
-    const int tap = (s * BK) / C, c0 = (s * BK) % C, kh = tap / KS, kw = tap % KS;
-    const int b = rr / (OH * OW), p = rr - b * (OH * OW), oh = p / OW, ow = p - oh * OW;
-    return ld4m(in + ((size_t)(b * H + oh * S + kh) * W + ow * S + kw) * C + c0 + k, ok);
+  // streams: one descriptor over the chunk's input activations, exactly (the last row's last tap ends at its end); rows past
+  // M read zeros.  kOob has to lie past it: the largest input, a1 of a forward chunk, stays below 2^31 bytes (f32_workspace)
+  using Streams = ConvFwdStreams<W, C, KS, OC, BM_, BN_, WM_ * WN_ * 64>;
+  __device__ Streams streams(int, int row0, int col0, int tid) const {
+    Streams st;
+    const int m = M;
+    st.a.init(in, (uint32_t)(M / (OH * OW)) * (uint32_t)(H * W * C * 4), tid, [row0, m](int r, int k) {
+      const int row = row0 + r, b = row / (OH * OW), p = row - b * (OH * OW), oh = p / OW, ow = p - oh * OW;
+      return row < m ? (uint32_t)(((b * H + oh * S) * W + ow * S) * C + k) * 4u : kOob;
+    });
+    st.init_b(w, col0, tid);
+    return st;
   }
-  __device__ f32x4 ldB(int, int s, int col, int k) const { return ld4(w + (size_t)(s * BK + k) * OC + col); }
   __device__ void epi(int, int row, int col, f32x4 v) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1000,14 +825,13 @@ struct RowShift : Base {
 using PConv2FwdR = RowShift<PConvFwd<20, 20, 32, 4, 2, 9, 9, 64, 16, 64, 1, 4>>;
 using PConv3FwdR = RowShift<PConvFwd<9, 9, 64, 3, 1, 7, 7, 64, 16, 64, 1, 4>>;
 
-// conv2 / conv3 forward over the non-background rows (see C1Lists).  Row tile 0 holds one row, the constant row: its input
-// is the constant vector cx at every tap (conv2: relu(0 + b0); conv3: c2) and its output goes to cbuf (c2; c3) - the
-// background rows' value, computed by the GEMM's own chain (ConstRows runs these as the first block of the conv2 launch).
-// Row tile 1 + t * kListSlots + x is tile t of list region x, whose row lr is output row list[x][lr] (chunk-local
-// b * OH * OW + p, bits 0..19) for lr < the region's count (device memory); tiles past it return at once.  Tiles run in
-// hardware block order (the live ones first, spread over the XCDs).  SEL (conv3): the taps whose input position is
-// background in the layer below (list entry bits 20..28, written by conv1) read cx = that layer's constant row instead of
-// `in` (those rows are written by this launch's side blocks).
+// conv2 / conv3 forward over the non-background rows (see C1Lists).  Row tile 0 is reserved (the constant row's place, which
+// PConstRow computes in ConstRows, the first block of the conv2 launch): its blocks return at once, and the list tiles keep
+// their hardware blocks.  Row tile 1 + t * kListSlots + x is tile t of list region x, whose row lr is output row
+// list[x][lr] (chunk-local b * OH * OW + p, bits 0..19) for lr < the region's count (device memory); tiles past it return
+// at once.  Tiles run in hardware block order (the live ones first, spread over the XCDs).  SEL (conv3): the taps whose
+// input position is background in the layer below (list entry bits 20..28, written by conv1) read cx = that layer's
+// constant row instead of `in` (those rows are written by this launch's side blocks).
 template <int H, int W, int C, int KS, int S, int OH, int OW, int OC, int BM_ = 64, int BN_ = 64, int WM_ = 2, int WN_ = 2,
           bool SEL = false>
 struct PConvFwdL {
@@ -1026,31 +850,24 @@ struct PConvFwdL {
   const int* list;   // [kListSlots][cap]
   int cap;
   const unsigned long long* cnt;   // this layer's counter of region 0 (region x at x * 2 * kCntStride)
-  const float* cx;   // constant input row [C]
-  float* cbuf;       // constant output row [OC]
+  const float* cx;   // (SEL) the layer below's constant row [C]
   // the epilogue rows' entries batched per call (entries()) or row by row, per launch: measured at C3, batched: conv3
   // 28.0 -> 27.5 us, the 8,192-sample conv2 / conv3 passes 137 / 180 -> 128 / 171 us, but the B = 1024 conv2 23.9 -> 25.6 us
   // (that launch sets it false)
   bool pre_batched = true;
-  struct ACtx { int off[NA]; uint32_t m[NA]; };   // input offset (-1: no row), taps read from cx
   struct Pre { float b; int o[4]; };   // o: the rows' raw list entries
 
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return KS * KS * C / BK; }
   __device__ int count(int x) const { return (int)(cnt[x * 2 * kCntStride] >> 32); }
-  // list entry of a GEMM row: >= 0 a row (SEL: with its constant-tap mask << 20), -1 none, -2 the constant row
-  // List entries of N rows of one row tile (the callers' rows all lie in one tile, so the tile index is read as
-  // wave-uniform): one scalar branch for the constant-row tile, the region counter as a scalar load, and the N entry loads -
-  // unconditional, at clamped addresses - all in flight at once.  (Row by row with a per-lane tile index the compiler put
-  // each row's loads behind an exec-masked branch and a vmcnt(0): one memory round trip per row in the tile prologue.)
+  // list entry of a GEMM row: >= 0 a row (SEL: with its constant-tap mask << 20), -1 none
+  // List entries of N rows of one row tile >= 1 (the callers' rows all lie in one tile, so the tile index is read as
+  // wave-uniform): the region counter as a scalar load, and the N entry loads - unconditional, at clamped addresses - all
+  // in flight at once.  (Row by row with a per-lane tile index the compiler put each row's loads behind an exec-masked
+  // branch and a vmcnt(0): one memory round trip per row in the tile prologue.)
   template <int N>
   __device__ void entries(const int (&row)[N], int (&out)[N]) const {
     const int tm = q32_uniform(row[0] / BM);
-    if (tm == 0) {
-#pragma unroll
-      for (int i = 0; i < N; ++i) out[i] = row[i] == 0 ? -2 : -1;
-      return;
-    }
     const int x = (tm - 1) % kListSlots, base = ((tm - 1) / kListSlots) * BM;
     const int n = count(x);
     int v[N];
@@ -1059,37 +876,10 @@ struct PConvFwdL {
 #pragma unroll
     for (int i = 0; i < N; ++i) out[i] = base + row[i] % BM < n ? v[i] : -1;
   }
-  __device__ bool active(int, int row0) const {   // (row tile 0 only where the constant row has somewhere to go)
+  __device__ bool active(int, int row0) const {   // (row tile 0: reserved)
     const int tm = row0 / BM;
-    return tm == 0 ? cbuf != nullptr : ((tm - 1) / kListSlots) * BM < count((tm - 1) % kListSlots);
+    return tm != 0 && ((tm - 1) / kListSlots) * BM < count((tm - 1) % kListSlots);
   }
-  __device__ ACtx a_ctx(int, int row0, int tid) const {
-    ACtx c;
-    int rows[NA], raws[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      int r, k;
-      OA::coord(tid + i * T, r, k);
-      rows[i] = row0 + r;
-    }
-    entries(rows, raws);
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int raw = raws[i], e = raw >= 0 ? raw & 0xFFFFF : raw;
-      const int b = e / R, p = e - b * R, oh = p / OW, ow = p - oh * OW;
-      c.off[i] = e >= 0 ? ((b * H + oh * S) * W + ow * S) * C : -1;
-      c.m[i] = e == -2 ? 0xFFFFFFFFu : (SEL && raw >= 0 ? (uint32_t)raw >> 20 : 0u);
-    }
-    return c;
-  }
-  __device__ f32x4 ldA_c(const ACtx& c, int i, int, int s, int, int k) const {
-    const int tap = (s * BK) / C, c0 = (s * BK) % C, kh = tap / KS, kw = tap % KS;
-    const int o = c.off[i];
-    const bool cst = (c.m[i] >> tap) & 1u;
-    const float* src = cst ? cx + c0 + k : in + (size_t)(o < 0 ? 0 : o) + (kh * W + kw) * C + c0 + k;
-    return ld4m(src, cst || o >= 0);
-  }
-  __device__ f32x4 ldB(int, int s, int col, int k) const { return ld4(w + (size_t)(s * BK + k) * OC + col); }
   __device__ Pre epi_pre(int, int row, int col) const {
     Pre q;
     q.b = bias[col];
@@ -1097,7 +887,6 @@ struct PConvFwdL {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int tm = (row + r) / BM;
-      if (tm == 0) { q.o[r] = row + r == 0 ? -2 : -1; continue; }
       const int x = (tm - 1) % kListSlots, lr = ((tm - 1) / kListSlots) * BM + (row + r) % BM;
       q.o[r] = lr < count(x) ? list[x * cap + lr] : -1;
     }
@@ -1109,62 +898,20 @@ struct PConvFwdL {
   }
   __device__ void epi_post(int, int, int col, f32x4 v, const Pre& q) const {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
+    for (int r = 0; r < 4; ++r)
       if (q.o[r] >= 0) out[(size_t)(q.o[r] & 0xFFFFF) * OC + col] = relu(v[r] + q.b);
-      else if (q.o[r] == -2) cbuf[col] = relu(v[r] + q.b);
-    }
   }
-  // streams (gemm_body_s; the list tiles, row tile >= 1 - the constant-row tile runs in ConstRows on the ldA core): A =
-  // the listed rows' im2col windows (rows past the list read zeros), a slab's tap and channel offset wave-uniform; SEL:
-  // a row's background taps read the constant row cx instead (one buffer spans `in` and cx: both live in the model's
-  // workspace), a per-lane select per slab.  B = the weight rows, affine.
-  struct StreamsImpl {
-    Rsrc ra;
-    uint32_t vo[NA], cxo[NA], msk[NA];
-    int tid;
-    AffineStream<BN_, true, T> b;
-    struct Regs {
-      f32x4 a[NA];
-      typename AffineStream<BN_, true, T>::Regs b;
-    };
-    __device__ void load(int s, Regs& x) const {
-      const int tap = (s * BK) / C, c0 = (s * BK) % C, kh = tap / KS, kw = tap - kh * KS;
-      const uint32_t so = (uint32_t)((kh * W + kw) * C + c0) * 4u;
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        if (OA::F4 % T == 0 || tid + i * T < OA::F4) {
-          if constexpr (SEL) {
-            const bool cst = (msk[i] >> tap) & 1u;
-            x.a[i] = buf_ld4(ra, cst ? cxo[i] + (uint32_t)c0 * 4u : vo[i] + so, 0u);
-          } else {
-            x.a[i] = buf_ld4(ra, vo[i], so);
-          }
-        }
-      }
-      b.load((uint32_t)s * BK * OC * 4u, 0, x.b);
-    }
-    __device__ void store(float* as, float* bs, const Regs& x) const {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int idx = tid + i * T;
-        if (OA::F4 % T == 0 || idx < OA::F4) {
-          int r, k;
-          OA::coord(idx, r, k);
-          OA::put(as, r, k, x.a[i]);
-        }
-      }
-      b.store(bs, x.b);
-    }
-  };
-  using Streams = StreamsImpl;
+  // streams: A = the listed rows' im2col windows (rows past the list read zeros); SEL: a row's background taps read the
+  // constant row cx instead (one buffer spans `in` and cx: both live in the model's workspace)
+  using Streams = ConvFwdStreams<W, C, KS, OC, BM_, BN_, T, SEL>;
   __device__ Streams streams(int, int row0, int col0, int tid) const {
     Streams st;
-    st.tid = tid;
+    st.a.tid = tid;
     // one descriptor over [min(in, cx), max end): both in the model's workspace (f32_forward)
     const char* lo = (const char*)in;
     const char* base = SEL && (const char*)cx < lo ? (const char*)cx : lo;
     const uint32_t in_off = (uint32_t)(lo - base), cx_off = SEL ? (uint32_t)((const char*)cx - base) : 0u;
-    st.ra = buf_rsrc(base, kNoEnd);   // (row offsets are bounded by the list entries: b * R + p of this chunk)
+    st.a.rs = buf_rsrc(base, kNoEnd);   // (row offsets are bounded by the list entries: b * R + p of this chunk)
     int rows[NA], raws[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
@@ -1179,11 +926,11 @@ struct PConvFwdL {
       OA::coord(tid + i * T, r, k);
       const int raw = raws[i], e = raw >= 0 ? raw & 0xFFFFF : -1;
       const int bb = e / R, pp = e - bb * R, oh = pp / OW, ow = pp - oh * OW;
-      st.vo[i] = e >= 0 ? in_off + (uint32_t)(((bb * H + oh * S) * W + ow * S) * C + k) * 4u : kOob;
+      st.a.vo[i] = e >= 0 ? in_off + (uint32_t)(((bb * H + oh * S) * W + ow * S) * C + k) * 4u : kOob;
       st.cxo[i] = cx_off + (uint32_t)k * 4u;
       st.msk[i] = SEL && raw >= 0 ? (uint32_t)raw >> 20 : 0u;
     }
-    st.b.init(w, (uint32_t)KS * KS * C * OC * 4u, tid, [col0](int r, int k) { return (uint32_t)(k * OC + col0 + r) * 4u; });
+    st.init_b(w, col0, tid);
     return st;
   }
 };
@@ -1192,13 +939,56 @@ using PConv2FwdL = PConvFwdL<20, 20, 32, 4, 2, 9, 9, 64, BM, BN, WM, WN, false>;
 template <int BM, int BN, int WM, int WN>
 using PConv3FwdL = PConvFwdL<9, 9, 64, 3, 1, 7, 7, 64, BM, BN, WM, WN, true>;
 
+// A conv layer's constant row, the value of its background rows: the output row whose input is the constant vector cx [C]
+// at every tap (conv2: relu(0 + b0); conv3: c2), cbuf [OC] = relu(that row + bias), by the GEMM's own chain k = (kh, kw, c)
+// ascending: row 0 of one 16 x 64 tile (4 waves x 16 channels), rows 1..15 reading zeros.
+template <int C, int KS, int OC>
+struct PConstRow {
+  static constexpr int BM = 16, BN = OC, WM = 1, WN = 4, T = 256;
+  static constexpr bool A_KMAJ = false, B_KMAJ = true, BIAS = false;
+  static constexpr Grid g{1, 1, 1};   // (one tile: what the host address replay walks)
+  const float* cx;
+  const float* w;    // [KS][KS][C][OC]
+  const float* bias;
+  float* cbuf;
+  __host__ __device__ void decode(int, int& tm, int& tn, int& z) const { tm = tn = z = 0; }
+  __host__ __device__ int nslabs(int) const { return KS * KS * C / BK; }
+  __device__ float epi_pre(int, int, int col) const { return bias[col]; }
+  __device__ void epi_post(int, int row, int col, f32x4 v, float b) const {
+    if (row == 0) cbuf[col] = relu(v[0] + b);
+  }
+  // streams: A = cx at every tap, the slab's channel offset wave-uniform; B = the weight rows
+  struct Streams {
+    AffineStream<BM, false, T> a;
+    AffineStream<BN, true, T> b;
+    struct Regs {
+      typename AffineStream<BM, false, T>::Regs a;
+      typename AffineStream<BN, true, T>::Regs b;
+    };
+    __device__ void load(int s, Regs& x) const {
+      a.load((uint32_t)((s * BK) % C) * 4u, 0, x.a);
+      b.load((uint32_t)s * BK * OC * 4u, 0, x.b);
+    }
+    __device__ void store(float* as, float* bs, const Regs& x) const {
+      a.store(as, x.a);
+      b.store(bs, x.b);
+    }
+  };
+  __device__ Streams streams(int, int, int, int tid) const {
+    Streams st;
+    st.a.init(cx, (uint32_t)C * 4u, tid, [](int r, int k) { return r == 0 ? (uint32_t)k * 4u : kOob; });
+    st.b.init(w, (uint32_t)KS * KS * C * OC * 4u, tid, [](int r, int k) { return (uint32_t)(k * OC + r) * 4u; });
+    return st;
+  }
+};
+
 // The constant rows as the first block of the conv2 launch: the conv2 constant row (input relu(0 + b0) -> c2), then, from
-// c2, the conv3 constant row (-> c3), each as the constant-row tile of a 16 x 64 list policy (4 waves x 16 channels, the
-// GEMM's chains).  Both are ready when the conv3 launch starts, so its side blocks can write the background rows of a2
-// and a3 and the fc1 forward reads a complete a3.
-template <class PA, class PB>
+// c2, the conv3 constant row (-> c3).  Both are ready when the conv3 launch starts, so its side blocks can write the
+// background rows of a2 and a3 and the fc1 forward reads a complete a3.
 struct ConstRows {
-  static constexpr size_t LDS = gemm_lds_bytes<PA>() > gemm_lds_bytes<PB>() ? gemm_lds_bytes<PA>() : gemm_lds_bytes<PB>();
+  using PA = PConstRow<32, 4, 64>;
+  using PB = PConstRow<64, 3, 64>;
+  static constexpr size_t LDS = gemm_lds_bytes<PA>();   // (both 16 x 64 tiles)
   PA pa;
   PB pb;
   __host__ __device__ int blocks() const { return 1; }
@@ -1286,7 +1076,7 @@ struct PFc1FwdT {
     for (int r = 0; r < 4; ++r)
       if (row + r < M) a4[(size_t)(row + r) * 512 + col] = relu(v[r] + b[r]);
   }
-  // streams (gemm_body_s): a3 rows (rows past M read zeros), W3 k rows
+  // streams: a3 rows (rows past M read zeros), W3 k rows
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, false, T>;
   using SB = AffineStream<BN_, true, T>;
@@ -1368,7 +1158,7 @@ struct PFc1DgradT {
       if ((row & 15) == 0 && row < M) pbg[(size_t)(row >> 4) * 3136 + col] = s;
     }
   }
-  // streams (gemm_body_s): dz4 rows (rows past M read zeros), W3 rows (k = n contiguous)
+  // streams: dz4 rows (rows past M read zeros), W3 rows (k = n contiguous)
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, false, T>;
   using SB = AffineStream<BN_, false, T>;
@@ -1407,7 +1197,7 @@ struct PFc1WgradT {
       if (row + r < 3136) dw3[(size_t)(row + r) * 512 + col] = v[r];
   }
   __device__ void epi_bias(int, int col, float v) const { db3[col] = v; }
-  // streams (gemm_body_s): a3 and dz4 rows of the slab's samples (k = b; samples past B read zeros)
+  // streams: a3 and dz4 rows of the slab's samples (k = b; samples past B read zeros)
   static constexpr int T = WM_ * WN_ * 64;
   using SA = AffineStream<BM_, true, T, true>;
   using SB = AffineStream<BN_, true, T, true>;
@@ -1499,7 +1289,7 @@ struct PConv3DgradPx {
       if ((row & 15) == 0 && row < B) pbg[((size_t)(row >> 4) * 81 + q.ih * 9 + q.iw) * 64 + col] = s;
     }
   }
-  // streams (gemm_body_s): dz3 rows of the tile's samples (rows past B read zeros), W2 rows of the tile's channels; a
+  // streams: dz3 rows of the tile's samples (rows past B read zeros), W2 rows of the tile's channels; a
   // slab's pixel tap (kh, kw) and oc half are wave-uniform offsets
   static constexpr int T = WM_ * WN_ * 64;
   struct Streams {
@@ -1601,7 +1391,7 @@ struct PConv2DgradPx {
       if ((row & 15) == 0 && row < B) pb[((size_t)(row >> 4) * 400 + ih * 20 + iw) * 32 + (col & 31)] = s;
     }
   }
-  // streams (gemm_body_s): A = dz2 rows of the tile's samples (rows past B read zeros), B = W1 rows of the tile's class
+  // streams: A = dz2 rows of the tile's samples (rows past B read zeros), B = W1 rows of the tile's class
   // channels; a slab's tap (th, tw) and oc half are wave-uniform offsets
   static constexpr int T = WM_ * WN_ * 64;
   struct Streams {
@@ -1691,7 +1481,7 @@ struct PConvWgrad {
     for (int r = 0; r < 4; ++r) slab[((size_t)z * (MROWS + 1) + row + r) * OC + col] = v[r];
   }
   __device__ void epi_bias(int z, int col, float v) const { slab[((size_t)z * (MROWS + 1) + MROWS) * OC + col] = v; }
-  // streams (gemm_body_s): A = the im2col rows gathered through the tile's offset table (TableK4Stream: one entry per
+  // streams: A = the im2col rows gathered through the tile's offset table (TableK4Stream: one entry per
   // reduction index r = (b, oh, ow) of the chunk), B = dz rows, affine in r; r past the chunk reads zeros
   static constexpr int T = WM_ * WN_ * 64;
   static constexpr int KMAX = (SC * P + BK - 1) / BK * BK;   // table entries: the chunk's r, padded to whole slabs
@@ -1785,7 +1575,7 @@ struct PConvWgrad {
       b.store(bs, x.b);
     }
   };
-  // (in place against an ldA / ldB core: 262.3K vs 263.0K env-steps/s, conv2 pair 102.0 vs 102.2 us - neutral; kept as the
+  // (in place against per-slab address arithmetic: 262.3K vs 263.0K env-steps/s, conv2 pair 102.0 vs 102.2 us - neutral; kept as the
   // one path: the weight-gradient tiles then issue no per-slab address arithmetic)
   static_assert(BM_ == 64 && WM_ * WN_ == 4, "weight gradient: the table stream stages 64-row tiles on four waves");
   using Streams = std::conditional_t<CMP, StreamsCmp, StreamsImpl>;

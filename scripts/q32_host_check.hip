@@ -1,8 +1,8 @@
 // Host-side address check of the fp32 GEMM policies (qnet32_kernels.h): every operand load and epilogue store a
 // launch of qnet32.hip would issue is replayed on the CPU against host buffers of exactly the device workspace
-// sizes, under AddressSanitizer, through the code the device runs: a policy with Streams builds its streams per
-// thread, writes their LDS tables and issues every slab's buffer loads (host stand-ins for the descriptor and the
-// loads, which also check the descriptor's byte count); the others go through ldA / ldB.  Dev tool (no GPU needed):
+// sizes, under AddressSanitizer, through the code the device runs: a policy builds its streams per thread, writes
+// their LDS tables and issues every slab's buffer loads (host stand-ins for the descriptor and the loads, which also
+// check the descriptor's byte count against the host buffer).  Dev tool (no GPU needed):
 //   hipcc --offload-host-only -x hip -I q-learning_amd/csrc -I include -fsanitize=address -g -O1 \
 //         scripts/q32_host_check.hip -o /tmp/q32_host_check && /tmp/q32_host_check 32 128
 #include <hip/hip_runtime.h>
@@ -40,17 +40,14 @@ void HostLoads::check_rsrc(const char* base, uint32_t bytes) const {
   exit(1);
 }
 
-// STREAMS = false for a policy with Streams: the tiles the device sends to gemm_body explicitly (ConstRows).
 // past: the smallest lane offset at which the launch's streams ask for zeros
-template <class P, bool STREAMS = HasStreams<P>::value>
+template <class P>
 static void replay(const P& p, const char* name, uint32_t past = kOob) {
   using OA = Opnd<P::BM, P::A_KMAJ>;
   using OB = Opnd<P::BN, P::B_KMAJ>;
   constexpr int T = P::WM * P::WN * 64;   // threads of one K group
   constexpr int TM = P::BM / (P::WM * 16), TN = P::BN / (P::WN * 16);
-  volatile float sink = 0.0f;
   host_loads = HostLoads{name, 0, 0, 0, past, 0, 0};
-  long ld = 0;
   float* lds = static_cast<float*>(std::malloc(gemm_lds_bytes<P>()));   // (the streams' tables: exact size)
   for (int lb = 0; lb < p.g.blocks(); ++lb) {
     int tm, tn, z;
@@ -60,45 +57,24 @@ static void replay(const P& p, const char* name, uint32_t past = kOob) {
       if (!p.active(z, row0)) continue;
     }
     host_loads.block = lb;
-    if constexpr (STREAMS) {   // gemm_body_s: per K group the streams of its T threads, their tables, then the slabs
-      using St = typename P::Streams;
-      constexpr int G = KSplitOf<P>::value, GROUP_LDS = 2 * (OA::FLOATS + OB::FLOATS);
-      const int ns = p.nslabs(z) / G;
-      static std::vector<St> st(T);
-      for (int tid = 0; tid < T; ++tid) {   // (the same in every group)
-        host_loads.tid = tid;
-        st[tid] = p.streams(z, row0, col0, tid);
-      }
-      for (int kg = 0; kg < G; ++kg) {
-        if constexpr (HasPrepare<St>::value)
-          for (int tid = 0; tid < T; ++tid) st[tid].prepare(lds + kg * GROUP_LDS, ns);
-        for (int s = 0; s < ns; ++s) {
-          host_loads.slab = kg * ns + s;
-          for (int tid = 0; tid < T; ++tid) {
-            host_loads.tid = tid;
-            typename St::Regs x;
-            st[tid].load(kg * ns + s, x);
-          }
-        }
-      }
-    } else {
-      const int ns = p.nslabs(z);
+    // gemm_body: per K group the streams of its T threads, their tables, then the slabs
+    using St = typename P::Streams;
+    constexpr int G = KSplitOf<P>::value, GROUP_LDS = 2 * (OA::FLOATS + OB::FLOATS);
+    const int ns = p.nslabs(z) / G;
+    static std::vector<St> st(T);
+    for (int tid = 0; tid < T; ++tid) {   // (the same in every group)
+      host_loads.tid = tid;
+      st[tid] = p.streams(z, row0, col0, tid);
+    }
+    for (int kg = 0; kg < G; ++kg) {
+      if constexpr (HasPrepare<St>::value)
+        for (int tid = 0; tid < T; ++tid) st[tid].prepare(lds + kg * GROUP_LDS, ns);
       for (int s = 0; s < ns; ++s) {
-        for (int idx = 0; idx < OA::F4; ++idx) {
-          int r, k;
-          OA::coord(idx, r, k);
-          f32x4 v;
-          if constexpr (HasACtx<P>::value) v = p.ldA_c(p.a_ctx(z, row0, idx % T), idx / T, z, s, row0 + r, k);
-          else v = p.ldA(z, s, row0 + r, k);
-          sink = sink + v[0];
-          ++ld;
-        }
-        for (int idx = 0; idx < OB::F4; ++idx) {
-          int r, k;
-          OB::coord(idx, r, k);
-          const f32x4 v = p.ldB(z, s, col0 + r, k);
-          sink = sink + v[0];
-          ++ld;
+        host_loads.slab = kg * ns + s;
+        for (int tid = 0; tid < T; ++tid) {
+          host_loads.tid = tid;
+          typename St::Regs x;
+          st[tid].load(kg * ns + s, x);
         }
       }
     }
@@ -122,9 +98,8 @@ static void replay(const P& p, const char* name, uint32_t past = kOob) {
     }
   }
   std::free(lds);
-  if (STREAMS) printf("%-24s blocks %6d buffer loads %10ld in range %9ld zero-filled ok\n", name, p.g.blocks(), host_loads.in_range, host_loads.zero_filled);
-  else printf("%-24s blocks %6d ldA / ldB loads %7ld ok\n", name, p.g.blocks(), ld);
-  checks += ld + host_loads.in_range + host_loads.zero_filled;
+  printf("%-24s blocks %6d buffer loads %10ld in range %9ld zero-filled ok\n", name, p.g.blocks(), host_loads.in_range, host_loads.zero_filled);
+  checks += host_loads.in_range + host_loads.zero_filled;
 }
 
 template <class T>
@@ -183,16 +158,16 @@ int main(int argc, char** argv) {
       }
       auto lg = [&](int cap, int BM, int BN) { return Grid{1 + kListSlots * ((cap + BM - 1) / BM), 64 / BN, 1}; };
       // conv2: one tile shape, the epilogue's list entries batched (chunk-size pass) or row by row (training batch)
-      PConv2FwdL<64, 64, 2, 2> p2{lg(cap2, 64, 64), a1, w1, b1, a2, rl2, cap2, cnt, cx, nullptr};
+      PConv2FwdL<64, 64, 2, 2> p2{lg(cap2, 64, 64), a1, w1, b1, a2, rl2, cap2, cnt, cx};
       replay(p2, "conv2_fwd L big");
       p2.pre_batched = false;
       replay(p2, "conv2_fwd L");
-      replay(PConv3FwdL<64, 64, 2, 2>{lg(cap3, 64, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L big");
-      replay(PConv3FwdL<32, 64, 2, 2>{lg(cap3, 32, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, nullptr}, "conv3_fwd L");
+      replay(PConv3FwdL<64, 64, 2, 2>{lg(cap3, 64, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2}, "conv3_fwd L big");
+      replay(PConv3FwdL<32, 64, 2, 2>{lg(cap3, 32, 64), a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2}, "conv3_fwd L");
     }
-    // (ConstRows runs these two on gemm_body: their ldA_c / ldB)
-    replay<PConv2FwdL<16, 64, 1, 4>, false>({Grid{1, 1, 1}, a1, w1, b1, a2, rl2, cap2, cnt, cx, c2}, "const row c2");
-    replay<PConv3FwdL<16, 64, 1, 4>, false>({Grid{1, 1, 1}, a2, w2, b2, a3, rl3, cap3, cnt + kCntStride, c2, c3}, "const row c3");
+    // (ConstRows' two tiles: a descriptor over the constant input row alone, inside the constant rows' own region)
+    replay(ConstRows::PA{cx, w1, b1, c2}, "const row c2");
+    replay(ConstRows::PB{c2, w2, b2, c3}, "const row c3");
   }
   replay(PFc1FwdB{grid(n, PFc1FwdB::BM, 512, PFc1FwdB::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd B");
   replay(PFc1FwdS{grid(n, PFc1FwdS::BM, 512, PFc1FwdS::BN, 1), a3, w3, b3, a4, n}, "fc1_fwd S");

@@ -229,8 +229,33 @@ struct PGen {
   int M, N, K;
   __host__ __device__ void decode(int lb, int& tm, int& tn, int& z) const { g.decode(lb, tm, tn, z); }
   __host__ __device__ int nslabs(int) const { return K / BK; }
-  __device__ f32x4 ldA(int, int s, int row, int k) const { return row < M ? ld4(A + (size_t)row * K + s * BK + k) : zero4(); }
-  __device__ f32x4 ldB(int, int s, int col, int k) const { return ld4(Bm + (size_t)(s * BK + k) * N + col); }
+  // streams: A rows (rows past M read zeros), B k rows; the row strides are run-time values (A and B below 2^31 bytes)
+  static constexpr int T = WM_ * WN_ * 64;
+  struct Streams {
+    AffineStream<BM_, false, T> a;
+    AffineStream<BN_, true, T> b;
+    uint32_t db;   // B bytes per slab
+    struct Regs {
+      typename AffineStream<BM_, false, T>::Regs a;
+      typename AffineStream<BN_, true, T>::Regs b;
+    };
+    __device__ void load(int s, Regs& x) const {
+      a.load((uint32_t)s * BK * 4u, 0, x.a);
+      b.load((uint32_t)s * db, 0, x.b);
+    }
+    __device__ void store(float* as, float* bs, const Regs& x) const {
+      a.store(as, x.a);
+      b.store(bs, x.b);
+    }
+  };
+  __device__ Streams streams(int, int row0, int col0, int tid) const {
+    Streams st;
+    const int m = M, n = N, kd = K;
+    st.a.init(A, (uint32_t)M * K * 4u, tid, [=](int r, int k) { return row0 + r < m ? (uint32_t)((row0 + r) * kd + k) * 4u : kOob; });
+    st.b.init(Bm, (uint32_t)K * N * 4u, tid, [=](int r, int k) { return (uint32_t)(k * n + col0 + r) * 4u; });
+    st.db = (uint32_t)BK * N * 4u;
+    return st;
+  }
   __device__ void epi(int, int row, int col, f32x4 v) const {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -283,7 +308,7 @@ struct RowFast : Base {
   }
 };
 
-// K-split wave groups on any policy (KSPLIT: gemm_body, gemm_body_s)
+// K-split wave groups on any policy (KSPLIT: gemm_body)
 template <class Base, int K>
 struct KSplit : Base {
   static constexpr int KSPLIT = K;

@@ -15,7 +15,8 @@ file holds them to the oracle (oracle/qnet32_ref.cpp) bit for bit where those pa
 each as one training step (forward, backward, apply): a1..a4, the loss, the clip norms, all ten gradients and w / m / v.
 The same cases run in a child process under QLX_F32_BG=0 (no step masks: every group computed; the oracle's dense mode)
 and under QLX_F32_C1_SKIP=0 (every step issued: no group or tile may be passed over), since the switches are read when a
-model is created.  The chunk-size forward kernel (B = 2,049) gets one forward on env frames.
+model is created.  The chunk-size forward kernel (B = 2,049) gets one forward on env frames.  The dense conv2 / conv3
+forward's ragged remainder tiles get B = 7 and 11 under QLX_F32_BG=0 with QLX_NUM_CUS=8.
 """
 import ctypes
 import os
@@ -197,16 +198,23 @@ import sys
 import numpy as np
 sys.path[:0] = [sys.argv[3], sys.argv[3] + "/tests", sys.argv[3] + "/q-learning_amd"]
 import qlx
-from test_gpu_qnet32_issue import BATCHES, KINDS, _run_case
+from test_gpu_qnet32_issue import _run_case
 d = np.load(sys.argv[1])
 out = {}
-for B in BATCHES:
-    for kind in KINDS:
-        k = f"{B}_{kind}"
-        for name, v in _run_case(qlx, d, d[f"x_{k}"], d[f"a_{k}"], d[f"y_{k}"]).items():
-            out[f"{k}__{name}"] = v
+for k in [f[2:] for f in d.files if f.startswith("x_")]:   # every case of the input file
+    for name, v in _run_case(qlx, d, d[f"x_{k}"], d[f"a_{k}"], d[f"y_{k}"]).items():
+        out[f"{k}__{name}"] = v
 np.savez(sys.argv[2], **out)
 """
+
+
+def _child(path, out, env):
+    """the cases of the input file `path` in a child process under the switches `env` (they are read when a model is created)"""
+    cenv = {k: v for k, v in os.environ.items() if not k.startswith("QLX_F32_") and k != "QLX_NUM_CUS"}
+    cenv.update(env)
+    r = subprocess.run([sys.executable, "-c", CHILD, path, out, ROOT], env=cenv, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return np.load(out)
 
 
 @pytest.mark.parametrize("env", [{"QLX_F32_BG": "0"}, {"QLX_F32_C1_SKIP": "0"}],
@@ -214,16 +222,42 @@ np.savez(sys.argv[2], **out)
 def test_null_step_masks_bit_exact(cases, env):
     """every case again without the forward's step masks / with every step issued (one child process per switch)"""
     d, path, _, exp = cases
-    out = str(d / ("out_" + "_".join(f"{k}{v}" for k, v in env.items()) + ".npz"))
-    cenv = {k: v for k, v in os.environ.items() if not k.startswith("QLX_F32_") and k != "QLX_NUM_CUS"}
-    cenv.update(env)
-    r = subprocess.run([sys.executable, "-c", CHILD, path, out, ROOT], env=cenv, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stderr[-3000:]
-    got = np.load(out)
+    got = _child(path, str(d / ("out_" + "_".join(f"{k}{v}" for k, v in env.items()) + ".npz")), env)
     dense = env.get("QLX_F32_BG") == "0"
     for k, both in exp.items():
         want = both[dense]
         _check({n: got[f"{k}__{n}"] for n in want}, want, f"{env}: {k}")
+
+
+def _balanced_whole_tiles(M, ncu):
+    """f32_forward's split of a dense conv forward over M rows: whole 64-row tiles, or 0 for the plain grid"""
+    t = M // 64
+    whole = t - t % ncu
+    return 0 if whole < ncu or M - whole * 64 > 32 * ncu else whole
+
+
+def test_dense_remainder_tiles_bit_exact(tmp_path):
+    """The dense-frame conv2 / conv3 forward's balanced grid with a ragged last 16-row remainder tile (RowShift), which
+    256 CUs reach only from B = 203: under QLX_NUM_CUS=8, B = 7 gives conv2 (M = 567) 8 whole tiles plus 4 remainder tiles,
+    the last with 7 live rows, and conv3 (M = 343) the plain ragged grid; B = 11 gives conv3 (M = 539) 8 whole tiles plus 2
+    remainder tiles, the last with 11 rows, and conv2 (M = 891) the plain ragged grid.  One training step each on env frames,
+    QLX_F32_BG=0 and QLX_NUM_CUS=8 together in one child process, against the oracle's dense mode."""
+    assert _balanced_whole_tiles(7 * 81, 8) == 8 and (7 * 81 - 512) % 16 == 7 and _balanced_whole_tiles(7 * 49, 8) == 0
+    assert _balanced_whole_tiles(11 * 49, 8) == 8 and (11 * 49 - 512) % 16 == 11 and _balanced_whole_tiles(11 * 81, 8) == 0
+    ref, w = _fresh_ref()
+    inp, exp = {f"w{v}": w[v] for v in range(10)}, {}
+    for B in (7, 11):
+        x = env_states(B, seed=40 + B)
+        rng = np.random.default_rng(7 * B)
+        a = rng.integers(0, 3, B).astype(np.uint8)
+        y = (ref.forward(x)[np.arange(B), a] + rng.normal(0, 1.5, B)).astype(np.float32)
+        inp[f"x_{B}"], inp[f"a_{B}"], inp[f"y_{B}"] = x, a, y
+        exp[B] = _expect(x, a, y, True)
+    path = str(tmp_path / "in.npz")
+    np.savez(path, **inp)
+    got = _child(path, str(tmp_path / "out.npz"), {"QLX_F32_BG": "0", "QLX_NUM_CUS": "8"})
+    for B, want in exp.items():
+        _check({n: got[f"{B}__{n}"] for n in want}, want, f"dense, 8 CUs: B = {B}")
 
 
 def test_chunk_form_forward_bit_exact():

@@ -1,10 +1,10 @@
 """Every global load / store address of the fp32 GEMM policies (qnet32_kernels.h) stays inside its buffer: the
 launches qnet32.hip issues are replayed on the CPU (scripts/q32_host_check.hip, compiled host-only) against host
 buffers of exactly the device workspace sizes under AddressSanitizer, with null frame-table entries (ring slots before
-an episode's first frame) mixed in.  The operand loads go through the code the device runs: a streamed policy's own
-streams (per-thread lane offsets, LDS offset tables, descriptor byte counts; a buffer load must be inside its descriptor
-and its host buffer, or past the descriptor at an offset the stream chose for that), ldA / ldB for the policies and tiles
-that run on them.  No GPU needed."""
+an episode's first frame) mixed in.  The operand loads go through the code the device runs, every policy's own streams
+(per-thread lane offsets, LDS offset tables, descriptor byte counts; a buffer load must be inside its descriptor and its
+host buffer, or past the descriptor at an offset the stream chose for that) - the dense-frame forwards and the two
+constant-row tiles included.  No GPU needed."""
 import os
 import shutil
 import subprocess
