@@ -17,7 +17,7 @@ LDFLAGS := -shared -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 OBJS := $(OUT)/obj/common.o $(OUT)/obj/env_breakout.o $(OUT)/obj/replay.o $(OUT)/obj/model.o $(OUT)/obj/qnet_bf16.o $(OUT)/obj/qnet32.o $(OUT)/obj/learner.o \
         $(OUT)/obj/ballgame.o $(OUT)/obj/tf_bundle.o $(OUT)/obj/per.o $(OUT)/obj/stats.o $(OUT)/obj/evaluator.o \
         $(OUT)/obj/snapshot_format.o $(OUT)/obj/frame_codec.o $(OUT)/obj/learner_core.o $(OUT)/obj/learner_snapshot.o \
-        $(OUT)/obj/metrics.o $(OUT)/obj/batch_dev.o $(OUT)/obj/model_dev.o $(OUT)/obj/head_wide.o
+        $(OUT)/obj/metrics.o $(OUT)/obj/batch_dev.o $(OUT)/obj/model_dev.o $(OUT)/obj/head_wide.o $(OUT)/obj/dist_loss.o
 
 HDRS := include/qlx.h $(wildcard $(SRC)/*.h)
 
@@ -68,6 +68,11 @@ $(OUT)/obj/qnet32.o: $(SRC)/qnet32.hip $(HDRS) | $(OUT)/obj
 # the wide output head: fmaf chains pinned bit for bit to the fp32 head's, so qnet32.o's flags
 $(OUT)/obj/head_wide.o: $(SRC)/head_wide.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(Q32SCHED) $(Q32VFORM) -c $< -o $@
+
+# distributional losses on the wide head: the quantile loss is separately rounded fp32 operations the tests restate bit
+# for bit (metrics.o's flags)
+$(OUT)/obj/dist_loss.o: $(SRC)/dist_loss.hip $(HDRS) | $(OUT)/obj
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 
 $(OUT)/obj/learner.o: $(SRC)/learner.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@

@@ -710,6 +710,60 @@ int32_t qlx_head_grads_dev(qlx_head* h, float** d_grads_out, uint64_t* count_out
 /* weights only, between heads of equal width on one device; orders the streams as qlx_model_copy_weights_dev does */
 int32_t qlx_head_copy_weights_dev(qlx_head* dst, qlx_head* src);
 
+/* ---- distributional losses on the wide head: QR-DQN's quantile Huber loss, C51's projected cross-entropy ----
+ * A head of width 3 N read as Z[b][a N + i], action a in 0..2, atom i in 0..N-1 (z.view(-1, 3, N)).  The descriptor names
+ * the reading; 3 * atoms must be the head's width (otherwise QLX_E_INVALID naming atoms, after the argument checks).
+ * Values Q[b][a]: quantile - the mean of the N quantiles; categorical - sum_k p_k z_k, p = softmax(Z[b][a][:]) with the row
+ * maximum subtracted, z_k = v_min + k D, D = (v_max - v_min) / (N - 1).  actions = first argmax, max_q its value.
+ * Loss of a batch (live = terminals ? 0 : discounts; a* = a_star, or the first argmax of the values of z_next):
+ *   quantile     T_j = returns + live z_next[a*][j], u_ij = T_j - Z[b][actions][i], h = |u| <= 1 ? (0.5 u) u : |u| - 0.5,
+ *                w_ij = |tau_i - 1{u_ij < 0}|, tau_i = (i + 0.5) / N, L_b = sum_i (sum_j w_ij h_ij) / N,
+ *                dz[b][actions N + i] = weights_b (-(sum_j w_ij clamp(u_ij, -1, 1)) / N) / B
+ *   categorical  p' = softmax(z_next[a*][:]), Tz_k = clamp(returns + live z_k, v_min, v_max),
+ *                m_i = sum_k p'_k max(0, 1 - |Tz_k - z_i| / D), L_b = -sum_i m_i log p_i, p = softmax(Z[b][actions][:]),
+ *                dz[b][actions N + i] = weights_b (p_i sum(m) - m_i) / B
+ *   loss = (sum_b weights_b L_b) / B; every other column of dz is written as zero; sample_loss_b = L_b (no weight).
+ * The quantile arithmetic is separately rounded fp32 in a fixed order; no floating-point atomics anywhere,
+ * so both losses are bit-reproducible and a sample's result depends on the batch only through the final / B.
+ * Conventions of the `_dev` sections: arguments are checked on the host before any handle is read (QLX_E_INVALID, the field
+ * named), everything is enqueued on the model's stream, no call allocates, synchronises or copies to the host; n and batch
+ * are bounded by qlx_model_reserve (QLX_E_STATE above it).  An action or a_star >= 3 is treated as 0 and sets the model's
+ * sticky flag (qlx_model_sync reports it once); non-finite inputs propagate. */
+#define QLX_DIST_QUANTILE 0
+#define QLX_DIST_CATEGORICAL 1
+#define QLX_DIST_MAX_ATOMS 341
+typedef struct qlx_dist {
+  int32_t kind;            /* QLX_DIST_QUANTILE (atoms 1..341) or QLX_DIST_CATEGORICAL (atoms 2..341) */
+  uint32_t atoms;
+  float v_min, v_max;      /* categorical: finite, v_min < v_max; ignored for quantiles */
+} qlx_dist;
+typedef struct qlx_dist_batch {      /* device pointers; the first four are what qlx_replay_batch_dev writes */
+  const uint8_t* actions;            /* [B] */
+  const float* returns;              /* [B] */
+  const float* discounts;            /* [B] */
+  const uint8_t* terminals;          /* [B] */
+  const float* z_next;               /* [B][3 N]: the target net's head output on s' */
+  const uint8_t* a_star;             /* [B] or NULL: NULL = first argmax of the values of z_next; else the caller's (double DQN) */
+  const float* weights;              /* [B] or NULL */
+} qlx_dist_batch;
+#ifdef __cplusplus
+static_assert(sizeof(qlx_dist) == 16, "qlx_dist ABI size");
+static_assert(sizeof(qlx_dist_batch) == 56, "qlx_dist_batch ABI size");
+#endif
+/* values of n (1..8192) rows d_z [n][3 N]: d_q [n][3], d_actions [n], d_max_q [n]; any may be NULL, not all three */
+int32_t qlx_head_values_dev(qlx_head* h, const qlx_dist* dist, const float* d_z, uint32_t n, float* d_q, uint8_t* d_actions,
+                            float* d_max_q);
+/* one launch for a*, target, L_b and the whole dz row (zeros included), one tiny launch for the scalar loss (skipped when
+ * d_loss is NULL).  d_dz [batch][3 N]; d_loss one float; d_sample_loss [batch]; d_a_star_out [batch].  batch 1..4096 */
+int32_t qlx_head_dist_loss_dev(qlx_head* h, const qlx_dist* dist, const float* d_z, const qlx_dist_batch* batch_in, uint32_t batch,
+                               float* d_dz, float* d_loss_or_null, float* d_sample_loss_or_null, uint8_t* d_a_star_out_or_null);
+/* one update: by definition, and bit for bit, qlx_head_forward_dev(src, batch, d_z_work, NULL), qlx_head_dist_loss_dev,
+ * qlx_head_backward_dev with that forward's ticket and no dq, qlx_model_step_dev(0).  The two work buffers [batch][3 N] are
+ * the caller's and hold Z and dz afterwards. */
+int32_t qlx_head_dist_train_dev(qlx_head* h, const qlx_dist* dist, const qlx_states_dev* src, const qlx_dist_batch* batch_in,
+                                uint32_t batch, float* d_z_work, float* d_dz_work, float* d_loss_or_null,
+                                float* d_sample_loss_or_null);
+
 /* ---------------- Prioritized replay on device tensors (beyond the reference) ----------------
  * The learner's proportional prioritized replay (the sum tree above: same heap, same draws, same weights, same priority
  * write) kept inside a qlx_replay and driven one batch per call from device memory.  Conventions of "Device-tensor env and

@@ -1,0 +1,20 @@
+// Distributional losses on the wide head: the kernels' launchers.  Entry points are in dist_loss.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "qlx_internal.h"
+
+namespace qlx {
+
+constexpr uint32_t kDistMaxAtoms = QLX_DIST_MAX_ATOMS;   // 3 * 341 = 1023 <= QLX_HEAD_MAX_WIDTH
+
+// Q [n][3], first argmax and max-Q of n rows z [n][3 N]; any output may be null
+void dist_values(const qlx_dist& d, const float* z, uint32_t n, float* q, uint8_t* actions, float* max_q, hipStream_t s);
+// a*, target, L_b (sample_loss [B], never null: the head's scratch when the caller wants none) and the whole dz row in one
+// launch; the scalar loss, unless null, in a second one-wave launch.  flag: the model's sticky flag word
+void dist_loss(const qlx_dist& d, const float* z, const qlx_dist_batch& b, uint32_t B, float* dz, float* loss, float* sample_loss,
+               uint8_t* a_star_out, uint32_t* flag, hipStream_t s);
+
+}  // namespace qlx

@@ -21,6 +21,7 @@ struct qlx_head {
   qlx::DeviceBuffer<float> d_w, d_m, d_v, d_grads;
   qlx::DeviceBuffer<float> d_part;   // clip-norm scratch: Wh's segment partials, then bh's one, then the two norms
   qlx::DeviceBuffer<float> d_zero;   // [4096][3] zeros: the fc1 backward's dq when the caller gives none
+  qlx::DeviceBuffer<float> d_dist;   // [4096] per-sample losses of a distributional loss whose caller wants none (§20)
   int64_t iterations = 0;
   hipEvent_t event = nullptr;        // orders qlx_head_copy_weights_dev across two streams (created at its first use)
   int64_t count() const { return (int64_t)(qlx::kHeadIn + 1) * width; }

@@ -368,6 +368,7 @@ int32_t qlx_head_create(qlx_model* m, uint32_t width, uint64_t seed, qlx_head** 
       h->d_grads.alloc(count);
       h->d_part.alloc((size_t)head_segs_w(h->width) + 3);
       h->d_zero.alloc((size_t)kHwMaxTrain * 3);
+      h->d_dist.alloc((size_t)kHwMaxTrain);
       // Wh: GlorotUniform(fan_in 512, fan_out width) from stream (seed, 10, 0, P_INIT), element i = word order; bh = 0
       std::vector<float> w(count, 0.0f);
       const float limit = std::sqrt(6.0f / (float)(kHeadIn + h->width));

@@ -145,6 +145,21 @@ class StatesDev(C.Structure):
                 ("layout", C.c_int32), ("which", C.c_int32)]
 
 
+class Dist(C.Structure):
+    """qlx_dist: how a head of width 3 * atoms is read: kind DIST_QUANTILE (atoms 1..341) or
+    DIST_CATEGORICAL (atoms 2..341, finite v_min < v_max)"""
+    _fields_ = [("kind", C.c_int32), ("atoms", C.c_uint32), ("v_min", C.c_float), ("v_max", C.c_float)]
+
+
+class DistBatch(C.Structure):
+    """qlx_dist_batch: device pointers [B] of a distributional loss's batch; the first four are what qlx_replay_batch_dev
+    writes, z_next is [B][3 atoms], a_star and weights may be None"""
+    _fields_ = [(k, C.c_void_p) for k in ("actions", "returns", "discounts", "terminals", "z_next", "a_star", "weights")]
+
+
+DIST_QUANTILE = 0       # QLX_DIST_QUANTILE
+DIST_CATEGORICAL = 1    # QLX_DIST_CATEGORICAL
+DIST_MAX_ATOMS = 341    # QLX_DIST_MAX_ATOMS
 OBS_NHWC_SLOT = 0   # QLX_OBS_NHWC_SLOT: [n][84][84][4] (x, y, ring slot)
 OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 oldest
 STEP_GRADS_WRITTEN = 1   # QLX_STEP_GRADS_WRITTEN: qlx_model_step_dev after the caller wrote the gradient buffer
@@ -278,6 +293,10 @@ def lib():
         "qlx_head_backward_dev": ([vp, C.POINTER(StatesDev), vp, vp, u32, u64], i32),
         "qlx_head_grads_dev": ([vp, C.POINTER(vp), C.POINTER(C.c_uint64)], i32),
         "qlx_head_copy_weights_dev": ([vp, vp], i32),
+        # distributional losses on the wide head (qlx_torch.TorchQNet.head_values / dist_loss / train_dist)
+        "qlx_head_values_dev": ([vp, C.POINTER(Dist), vp, u32, vp, vp, vp], i32),
+        "qlx_head_dist_loss_dev": ([vp, C.POINTER(Dist), vp, C.POINTER(DistBatch), u32, vp, vp, vp, vp], i32),
+        "qlx_head_dist_train_dev": ([vp, C.POINTER(Dist), C.POINTER(StatesDev), C.POINTER(DistBatch), u32, vp, vp, vp, vp], i32),
         "qlx_params_default": ([vp], None),
         "qlx_learner_create": ([C.POINTER(Params), i32, C.POINTER(vp)], i32), "qlx_learner_destroy": ([vp], i32),
         "qlx_learner_vector_step": ([vp], i32), "qlx_learner_run": ([vp, u64], i32), "qlx_learner_sync": ([vp], i32),
@@ -755,6 +774,17 @@ class WideHead:
 
     def copy_weights_dev(self, other):
         _check(lib().qlx_head_copy_weights_dev(self.h, other.h))
+
+    def values_dev(self, dist, d_z, n, d_q=None, d_actions=None, d_max_q=None):
+        _check(lib().qlx_head_values_dev(self.h, C.byref(dist), d_z, n, d_q, d_actions, d_max_q))
+
+    def dist_loss_dev(self, dist, d_z, batch_in, batch, d_dz, d_loss=None, d_sample_loss=None, d_a_star_out=None):
+        _check(lib().qlx_head_dist_loss_dev(self.h, C.byref(dist), d_z, C.byref(batch_in), batch, d_dz, d_loss, d_sample_loss,
+                                            d_a_star_out))
+
+    def dist_train_dev(self, dist, src, batch_in, batch, d_z_work, d_dz_work, d_loss=None, d_sample_loss=None):
+        _check(lib().qlx_head_dist_train_dev(self.h, C.byref(dist), C.byref(src), C.byref(batch_in), batch, d_z_work, d_dz_work,
+                                             d_loss, d_sample_loss))
 
 
 class Evaluator:

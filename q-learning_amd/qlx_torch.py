@@ -24,6 +24,7 @@ last_indices are int64 holding the ABI's uint64 (a negative value reads as an in
 import collections
 import contextlib
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -382,6 +383,53 @@ class _QZFunction(torch.autograd.Function):
         return None, None, None
 
 
+class _Dist:
+    """how a head of width 3 * atoms is read by the distributional calls (qlx_dist)"""
+
+    def __init__(self, kind, atoms, v_min=0.0, v_max=0.0):
+        self.atoms, self.width = int(atoms), 3 * int(atoms)
+        self.c = qlx.Dist(kind, self.atoms, v_min, v_max)
+
+
+class Quantile(_Dist):
+    """Z[b][a * atoms + i] is quantile i of action a (QR-DQN): Q is the mean of the quantiles, the loss the quantile Huber
+    loss with kappa = 1 and tau_i = (i + 0.5) / atoms"""
+
+    def __init__(self, atoms):
+        if not 1 <= int(atoms) <= qlx.DIST_MAX_ATOMS:
+            raise ValueError(f"atoms must be in 1..{qlx.DIST_MAX_ATOMS}")
+        super().__init__(qlx.DIST_QUANTILE, atoms)
+
+
+class Categorical(_Dist):
+    """Z[b][a * atoms + i] is the logit of atom z_i = v_min + i (v_max - v_min) / (atoms - 1) of action a (C51): Q is the
+    expectation under the softmax, the loss the cross-entropy against the projected target distribution"""
+
+    def __init__(self, atoms, v_min, v_max):
+        if not 2 <= int(atoms) <= qlx.DIST_MAX_ATOMS:
+            raise ValueError(f"atoms must be in 2..{qlx.DIST_MAX_ATOMS}")
+        if not (math.isfinite(v_min) and math.isfinite(v_max) and v_min < v_max):
+            raise ValueError("v_min and v_max must be finite with v_min < v_max")
+        super().__init__(qlx.DIST_CATEGORICAL, atoms, v_min, v_max)
+        self.v_min, self.v_max = float(v_min), float(v_max)
+
+
+class _DistLossFunction(torch.autograd.Function):
+    """loss = the distributional loss of z (TorchQNet.dist_loss); its backward hands dz * grad_loss on to z's grad_fn"""
+
+    @staticmethod
+    def forward(ctx, z, net, dist, args):
+        loss, dz, sample_loss, a_star = net._dist_loss(z, dist, *args)
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(dz, sample_loss, a_star)
+        return loss, dz, sample_loss, a_star
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        (dz,) = ctx.saved_tensors
+        return dz * grad_loss, None, None, None
+
+
 class _DeviceFloats:
     """a device float32 array of libqlx as torch.as_tensor reads it (zero copy); keeps its owner alive"""
 
@@ -431,6 +479,7 @@ class TorchQNet(_Streamed):
         self._grads = None
         self._head = None         # the attached qlx.WideHead (attach_head)
         self._head_grads = None
+        self._dist_work = {}      # width -> the two work tensors of train_dist
 
     def close(self):
         head = getattr(self, "_head", None)
@@ -510,6 +559,101 @@ class TorchQNet(_Streamed):
             k = qlx.HEAD_IN * head.width
             self._head_grads = (flat[:k].view(qlx.HEAD_IN, head.width), flat[k:])
         return self._head_grads
+
+    # ---- distributional losses on the head: QR-DQN and C51 without a torch op on the update path ----
+
+    def _dist(self, dist):
+        head = self._need_head()
+        if not isinstance(dist, _Dist):
+            raise ValueError("dist must be a qlx_torch.Quantile or qlx_torch.Categorical")
+        if dist.width != head.width:
+            raise ValueError(f"3 * atoms = {dist.width} is not the head's width {head.width}")
+        return head
+
+    def _dist_batch(self, B, dist, actions, returns, discounts, terminals, z_next, a_star, weights):
+        """(qlx.DistBatch, the tensors it points at) or ValueError before anything is launched"""
+        ts = (_arg("actions", actions, self.device, torch.uint8, (B,)),
+              _arg("returns", returns, self.device, torch.float32, (B,)),
+              _arg("discounts", discounts, self.device, torch.float32, (B,)),
+              _arg("terminals", terminals, self.device, torch.uint8, (B,)),
+              _arg("z_next", z_next, self.device, torch.float32, (B, dist.width)),
+              None if a_star is None else _arg("a_star", a_star, self.device, torch.uint8, (B,)),
+              None if weights is None else _arg("weights", weights, self.device, torch.float32, (B,)))
+        return qlx.DistBatch(*(None if t is None else t.data_ptr() for t in ts)), ts
+
+    def head_values(self, z, dist, want=_WANT, out=None):
+        """Q-values of head outputs z float32 [n, 3 * atoms] read as `dist` (Quantile or Categorical), in the shape of q():
+        the tensors named in `want` - 'q' float32 [n, 3], 'actions' uint8 [n] (first argmax), 'max_q' float32 [n]."""
+        head = self._dist(dist)
+        if not isinstance(z, torch.Tensor) or z.dim() != 2:
+            raise ValueError("z must be a 2-d tensor")
+        n = z.shape[0]
+        if not 0 < n <= self.reserved:
+            raise ValueError(f"n must be in 1..{self.reserved} (the reserve)")
+        zt = _arg("z", z.detach(), self.device, torch.float32, (n, dist.width))
+        names = (want,) if isinstance(want, str) else tuple(want)
+        out = dict(out or {})
+        if not names or set(names) - set(_WANT) or set(out) - set(names):
+            raise ValueError(f"want must name some of {_WANT}, and out only what want names")
+        spec = dict(q=(torch.float32, (n, 3)), actions=(torch.uint8, (n,)), max_q=(torch.float32, (n,)))
+        res = {k: (_arg(f"out[{k!r}]", out[k], self.device, *spec[k]) if k in out else
+                   torch.empty(spec[k][1], dtype=spec[k][0], device=self.device)) for k in names}
+        ptr = [res[k].data_ptr() if k in res else None for k in _WANT]
+        self._run(None, None, (zt,) + tuple(res.values()),
+                  lambda: _L.qlx_head_values_dev(head.h, C.byref(dist.c), zt.data_ptr(), n, *ptr))
+        return res[want] if isinstance(want, str) else tuple(res[k] for k in names)
+
+    def _dist_loss(self, z, dist, actions, returns, discounts, terminals, z_next, a_star, weights):
+        head = self._dist(dist)
+        if not isinstance(z, torch.Tensor) or z.dim() != 2:
+            raise ValueError("z must be a 2-d tensor")
+        B = z.shape[0]
+        if not 0 < B <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"batch must be in 1..{min(MAX_BATCH, self.reserved)}")
+        zt = _arg("z", z.detach(), self.device, torch.float32, (B, dist.width))
+        batch, ts = self._dist_batch(B, dist, actions, returns, discounts, terminals, z_next, a_star, weights)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        dz = torch.empty((B, dist.width), dtype=torch.float32, device=self.device)
+        sample_loss = torch.empty(B, dtype=torch.float32, device=self.device)
+        a_out = torch.empty(B, dtype=torch.uint8, device=self.device)
+        self._run(None, None, (zt,) + ts + (loss, dz, sample_loss, a_out),
+                  lambda: _L.qlx_head_dist_loss_dev(head.h, C.byref(dist.c), zt.data_ptr(), C.byref(batch), B, dz.data_ptr(),
+                                                    loss.data_ptr(), sample_loss.data_ptr(), a_out.data_ptr()))
+        return loss, dz, sample_loss, a_out
+
+    def dist_loss(self, z, dist, actions, returns, discounts, terminals, z_next, a_star=None, weights=None):
+        """The distributional loss of head outputs z float32 [B, 3 * atoms] against the target net's z_next [B, 3 * atoms]:
+        (loss, dz, sample_loss, a_star) - loss 0-d = mean of weights * sample_loss, dz = dloss/dz [B, 3 * atoms] (pass it to
+        backward_dz), sample_loss float32 [B] (no weights: what update_priorities takes), a_star uint8 [B] (the one given,
+        or the first argmax of the values of z_next).  actions, returns, discounts, terminals as TorchReplay.batch gives
+        them.  When z carries a grad_fn (forward(head=True)), loss does too: loss.backward() hands dz * grad on to it."""
+        args = (actions, returns, discounts, terminals, z_next, a_star, weights)
+        if torch.is_grad_enabled() and isinstance(z, torch.Tensor) and z.requires_grad:
+            return _DistLossFunction.apply(z, self, dist, args)
+        return self._dist_loss(z, dist, *args)
+
+    def train_dist(self, dist, actions, returns, discounts, terminals, z_next, a_star=None, weights=None, *, obs=None,
+                   env=None, replay=None, indices=None, which="s", layout="nchw_time", want_sample_loss=False):
+        """One whole update of the net and its head on B states in one call (qlx_head_dist_train_dev: the head's forward,
+        the distributional loss, the backward, clip_by_norm and Adam): (loss, sample_loss), loss a 0-d float32 device
+        tensor, sample_loss float32 [B] or None.  The two [B, 3 * atoms] work tensors are allocated once per net and width."""
+        head = self._dist(dist)
+        s, B, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < B <= min(MAX_BATCH, self.reserved):
+            raise ValueError(f"batch must be in 1..{min(MAX_BATCH, self.reserved)}")
+        batch, ts = self._dist_batch(B, dist, actions, returns, discounts, terminals, z_next, a_star, weights)
+        work = self._dist_work.get(dist.width)
+        if work is None:
+            rows = min(MAX_BATCH, self.reserved)
+            work = self._dist_work[dist.width] = tuple(torch.empty((rows, dist.width), dtype=torch.float32, device=self.device)
+                                                       for _ in range(2))
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        sl = torch.empty(B, dtype=torch.float32, device=self.device) if want_sample_loss else None
+        self._pending = False   # (the update overwrites the gradient buffers)
+        self._run(env, replay, ins + ts + work + (loss, sl),
+                  lambda: _L.qlx_head_dist_train_dev(head.h, C.byref(dist.c), C.byref(s), C.byref(batch), B, work[0].data_ptr(),
+                                                     work[1].data_ptr(), loss.data_ptr(), None if sl is None else sl.data_ptr()))
+        return loss, sl
 
     @property
     def model(self):

@@ -9,6 +9,10 @@
   python scripts/torch_qnet_bench.py head   [--batch 1024] [--widths 4,153,600]   the wide output head:
       net(replay=, head=True) + a loss in torch + backward() + step() per width, beside `grad`'s update without a head on
       the same states; `--kernels N` only runs N of each width for a kernel trace (k_headw_fwd / _dz / _wgrad)
+  python scripts/torch_qnet_bench.py dist   [--batch 1024]   distributional updates on the wide head, off
+      the replay ring: quantile N = 51 and 200, categorical N = 51; per case forward(head=True) + the loss in torch +
+      backward() + step() against train_dist(), alternated call by call, median [min..max] of 30 after 5 warm-ups, beside
+      `grad`'s update without a head; `--kernels N` only runs N of each for a kernel trace (k_dist_loss_* / k_dist_values)
   python scripts/torch_qnet_bench.py pack   [--n 1024]     the two staging kernels, to be run under a kernel trace:
       rocprofv3 --kernel-trace --stats -d DIR -- python scripts/torch_qnet_bench.py pack --n 8192
       (k_pack_states: the dense source of q(); k_pack_obs: the host call qlx_model_predict on the same states)
@@ -214,6 +218,107 @@ def head(args):
     env.close()
 
 
+def time_alternated(fns, reps, warmup):
+    """time_device for several paths, one call of each in turn, so that a drift of the clocks meets all of them alike"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            out[k].append(a.elapsed_time(b) * 1e3)
+    return out
+
+
+def torch_dist_loss(kind, N, z, z_next, b, rows, atoms, v_min, v_max):
+    """the example's losses (scripts/torch_qrdqn_example.py): a*, the target and the loss of the taken action, in torch"""
+    live = b.discounts * (1.0 - b.terminals.float())
+    zn = z_next.view(-1, 3, N)
+    taken = z.view(-1, 3, N)[rows, b.actions.long()]
+    if kind == "quantile":
+        nxt = zn[rows, zn.mean(dim=2).argmax(dim=1)]
+        u = (b.returns[:, None] + live[:, None] * nxt)[:, None, :] - taken[:, :, None]
+        huber = torch.where(u.abs() <= 1, 0.5 * u * u, u.abs() - 0.5)
+        tau = (torch.arange(N, device=z.device, dtype=z.dtype) + 0.5) / N
+        return ((tau[None, :, None] - (u.detach() < 0).float()).abs() * huber).mean(dim=2).sum(dim=1).mean()
+    p = torch.softmax(zn, dim=2)
+    nxt = p[rows, (p * atoms).sum(dim=2).argmax(dim=1)]
+    delta = (v_max - v_min) / (N - 1)
+    tz = (b.returns[:, None] + live[:, None] * atoms[None, :]).clamp(v_min, v_max)
+    hat = (1.0 - (tz[:, None, :] - atoms[None, :, None]).abs() / delta).clamp(min=0.0)
+    m = (nxt[:, None, :] * hat).sum(dim=2)
+    return -(m * torch.log_softmax(taken, dim=1)).sum(dim=1).mean()
+
+
+def dist(args):
+    if not torch.cuda.is_available():
+        sys.exit("torch_qnet_bench.py dist: no GPU")
+    B = args.batch
+    env, rb = played_env(256, 40, rb=20_000)
+    lay = "nhwc_slot"
+    idx = rb.sample_indices(B, seed=3, update_idx=0)
+    b = rb.batch(idx, n_step=3, gamma=0.99, layout=lay, fields=("actions", "returns", "discounts", "terminals", "last_indices"))
+    rows = torch.arange(B, device=DEV)
+    a_idx = b.actions.long().unsqueeze(1)
+    y = torch.randn(B, device=DEV)
+    v_min, v_max = -10.0, 10.0
+    plain = QT.TorchQNet("f32", env=env, reserve=B)
+
+    def no_head():   # `grad`'s update
+        q = plain(replay=rb, indices=idx, layout=lay)
+        torch.nn.functional.huber_loss(q.gather(1, a_idx).squeeze(1), y, delta=1.0).backward()
+        plain.step()
+
+    cases, nets = [], [plain]
+    for kind, N in (("quantile", 51), ("quantile", 200), ("categorical", 51)):
+        d = QT.Quantile(N) if kind == "quantile" else QT.Categorical(N, v_min, v_max)
+        atoms = torch.linspace(v_min, v_max, N, device=DEV)
+        z_next = torch.randn(B, 3 * N, device=DEV)
+        by_torch, fused = QT.TorchQNet("f32", env=env, reserve=B), QT.TorchQNet("f32", env=env, reserve=B)
+        by_torch.attach_head(3 * N, seed=N)
+        fused.attach_head(3 * N, seed=N)
+        nets += [by_torch, fused]
+
+        def torch_path(net=by_torch, kind=kind, N=N, z_next=z_next, atoms=atoms):
+            _, z = net.forward(replay=rb, indices=idx, layout=lay, head=True)
+            torch_dist_loss(kind, N, z, z_next, b, rows, atoms, v_min, v_max).backward()
+            net.step()
+
+        def fused_path(net=fused, d=d, z_next=z_next):
+            net.train_dist(d, b.actions, b.returns, b.discounts, b.terminals, z_next, replay=rb, indices=idx, layout=lay)
+
+        def values_path(net=fused, d=d, z_next=z_next):
+            net.head_values(z_next, d, want="actions")
+
+        cases.append((f"{kind} N = {N}", torch_path, fused_path, values_path))
+
+    if args.kernels:   # for rocprofv3 --kernel-trace --stats: the same launches, untimed
+        for _ in range(args.kernels):
+            no_head()
+            for _, torch_path, fused_path, values_path in cases:
+                torch_path()
+                fused_path()
+                values_path()
+    else:
+        base = time_device(no_head, args.reps, args.warmup)
+        mb = statistics.median(base)
+        print(f"distributional update, B = {B}, f32, off the replay ring (median [min..max] of {args.reps} after {args.warmup}):")
+        print(f"  {'no head (grad)':38s} {fmt(base)}")
+        for name, torch_path, fused_path, values_path in cases:
+            t, f = time_alternated((torch_path, fused_path), args.reps, args.warmup)
+            print(f"  {name + ', loss in torch':38s} {fmt(t)}   + {statistics.median(t) - mb:.1f} us")
+            print(f"  {name + ', train_dist':38s} {fmt(f)}   + {statistics.median(f) - mb:.1f} us")
+    for net in nets:
+        net.sync()
+    env.close()
+
+
 def pack(args):
     n = args.n
     net = QT.TorchQNet("bf16", reserve=n)
@@ -231,17 +336,21 @@ def pack(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("act", "update", "grad", "head", "pack"))
+    ap.add_argument("what", choices=("act", "update", "grad", "head", "dist", "pack"))
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--arch", choices=("f32", "bf16"), default="f32")
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=None, help="default 20, dist: 30")
+    ap.add_argument("--warmup", type=int, default=None, help="default 3, dist: 5")
     ap.add_argument("--widths", default="4,153,600", help="head: the head widths, comma separated")
-    ap.add_argument("--kernels", type=int, default=0, help="grad, head: run this many of each path untimed (kernel trace)")
+    ap.add_argument("--kernels", type=int, default=0, help="grad, head, dist: run this many of each path untimed (kernel trace)")
     args = ap.parse_args()
-    {"act": act, "update": update, "grad": grad, "head": head, "pack": pack}[args.what](args)
+    if args.reps is None:
+        args.reps = 30 if args.what == "dist" else 20
+    if args.warmup is None:
+        args.warmup = 5 if args.what == "dist" else 3
+    {"act": act, "update": update, "grad": grad, "head": head, "dist": dist, "pack": pack}[args.what](args)
 
 
 if __name__ == "__main__":
