@@ -70,7 +70,7 @@ $(OUT)/obj/head_wide.o: $(SRC)/head_wide.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(Q32SCHED) $(Q32VFORM) -c $< -o $@
 
 # distributional losses on the wide head: the quantile loss is separately rounded fp32 operations the tests restate bit
-# for bit (metrics.o's flags)
+# for bit (metrics.o's flags); the fused select kernel shares the values' device functions and therefore this object
 $(OUT)/obj/dist_loss.o: $(SRC)/dist_loss.hip $(HDRS) | $(OUT)/obj
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 

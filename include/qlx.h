@@ -350,7 +350,8 @@ int32_t qlx_evaluator_destroy(qlx_evaluator* ev);
  * Every run starts from the same env and draw state: equal config and weights give equal results.  vector_steps = the
  * first multiple of poll_steps at which no env was playing; forward_samples = the rows the Q-net forward ran over. */
 int32_t qlx_evaluator_run(qlx_evaluator* ev, qlx_model* m, qlx_eval_summary* out);
-/* records of the last run, [n_envs][K] env-major, any may be NULL: return, length, ended by done, sum of max_a q */
+/* (the policy of a distributional wide head: qlx_evaluator_run_head, with the head's calls below) */
+/* records of the last run (of either kind), [n_envs][K] env-major, any may be NULL: return, length, ended by done, sum of max_a q */
 int32_t qlx_evaluator_episodes(qlx_evaluator* ev, float* returns, uint32_t* lengths, uint8_t* terminals, float* max_q_sums);
 qlx_env* qlx_evaluator_env(qlx_evaluator* ev);
 /* evaluates the learner's online model on the learner's stream with a temporary evaluator; the learner's own
@@ -676,7 +677,8 @@ int32_t qlx_model_grads_dev(qlx_model* m, float** d_grads_out, uint64_t* count_o
  * 512, fan_out width, from stream (seed, 10, 0, purpose 4) in element order) and bh [width] (zero), their Adam m and v, a
  * gradient buffer (Wh, then bh), its own iteration count and clip-norm scratch; it runs on the model's stream with the
  * model's hyperparameters (qlx_model_hparams).  The model's ten variables, its checkpoints, snapshots and learner do not
- * know the head: qlx_head_get_var / _set_var are its persistence.
+ * know the head: qlx_head_write_checkpoint / _read_checkpoint (below) are its persistence, weights, Adam slots and iterations;
+ * qlx_head_get_var / _set_var move one array.
  * A model has at most one head (a second create: QLX_E_STATE); a bf16 model has none (QLX_E_INVALID); qlx_model_destroy of
  * a model with a live head fails with QLX_E_STATE.  Conventions of the `_dev` section above: arguments are checked on the
  * host before any handle is read (QLX_E_INVALID, the field named), then everything is enqueued on the model's stream; no
@@ -763,6 +765,41 @@ int32_t qlx_head_dist_loss_dev(qlx_head* h, const qlx_dist* dist, const float* d
 int32_t qlx_head_dist_train_dev(qlx_head* h, const qlx_dist* dist, const qlx_states_dev* src, const qlx_dist_batch* batch_in,
                                 uint32_t batch, float* d_z_work, float* d_dz_work, float* d_loss_or_null,
                                 float* d_sample_loss_or_null);
+
+/* ---- acting with, evaluating and checkpointing a distributional head ----
+ * One kernel gives a row's values, first argmax and epsilon-greedy draw: the values are qlx_head_values_dev's bits (the same
+ * device functions), the draw is the evaluator's (random when epsilon > 0 and epsilon > the f64 from words 0-1 of the row's
+ * stream; the random action uniform over 3 from word 2).  Conventions of the sections above: argument errors (a null head,
+ * dist, d_z / d_z_work or d_actions, every qlx_dist error, the source's cases, n 0 or > 8192, an epsilon that is not finite
+ * or outside 0..1) are QLX_E_INVALID with the field named, found before any handle is read; then 3 * atoms against the
+ * width (QLX_E_INVALID naming atoms), the reserve (QLX_E_STATE) and the source's handles.  A failed call launches nothing.
+ * Both calls only enqueue on the model's stream. */
+/* epsilon-greedy on given rows d_z [n][3 N]: row r draws from stream (seed, r, step, purpose 9), f64 from word 0, action
+ * from word 2.  d_max_q [n] and d_q [n][3] are the greedy values, whatever action was drawn; with epsilon 0 nothing is drawn
+ * and d_actions is qlx_head_values_dev's. */
+int32_t qlx_head_select_dev(qlx_head* h, const qlx_dist* dist, const float* d_z, uint32_t n, double epsilon, uint64_t seed,
+                            uint32_t step, uint8_t* d_actions, float* d_max_q_or_null, float* d_q_or_null);
+/* by definition, and bit for bit: qlx_head_forward_dev(src, n, d_z_work, NULL), then qlx_head_select_dev on d_z_work
+ * [n][3 N], which holds Z afterwards; every check of both is made before the first launch */
+int32_t qlx_head_act_dev(qlx_head* h, const qlx_dist* dist, const qlx_states_dev* src, uint32_t n, double epsilon, uint64_t seed,
+                         uint32_t step, uint8_t* d_actions, float* d_max_q_or_null, float* d_q_or_null, float* d_z_work);
+/* qlx_evaluator_run (above) with the policy of h read as `dist`: q = the values of Z(obs_e) in place of the built-in Q, all
+ * else word for word - the env reset per run, the purpose-8 draws, the records, fp32 sums in step order, retirement,
+ * polling, vector_steps, forward_samples, compaction; it runs on the stream of the head's model and synchronises.  Per
+ * vector step: the trunk forward over the rows, the head's forward into a Z workspace the evaluator owns ([n_envs][width],
+ * allocated before the loop of the first run that needs it, grown only), one select launch; the built-in head is not
+ * launched.  qlx_evaluator_episodes serves the last run of either kind.  Argument errors (null ev, h, dist or out, every
+ * qlx_dist error) before any handle is read; then 3 * atoms against the width and the devices.  No weight, Adam slot,
+ * iteration count, gradient buffer or sticky flag of the model or the head changes; like any forward the run advances the
+ * model's forward ticket, so a ticket taken before it is no longer current and a backward given it runs its forward again.
+ * The model's workspace grows to n_envs rows if it is smaller: qlx_model_reserve does not bound an evaluation. */
+int32_t qlx_evaluator_run_head(qlx_evaluator* ev, qlx_head* h, const qlx_dist* dist, qlx_eval_summary* out);
+/* The head's persistence, as qlx_model_write_checkpoint / _read_checkpoint are the model's (host calls, synchronise): magic
+ * "QLXHEAD1", two int64 {width, iterations}, then Wh|bh weights, Adam m, Adam v, 513 * width floats each.  A file with
+ * another magic, another width or too few bytes is refused with QLX_E_IO and nothing of the head changes.  A read restores
+ * iterations too, so a model and a head restored from their two files continue an interrupted run bit for bit. */
+int32_t qlx_head_write_checkpoint(qlx_head* h, const char* path);
+int32_t qlx_head_read_checkpoint(qlx_head* h, const char* path);
 
 /* ---------------- Prioritized replay on device tensors (beyond the reference) ----------------
  * The learner's proportional prioritized replay (the sum tree above: same heap, same draws, same weights, same priority

@@ -9,6 +9,8 @@
 // i = t and t + blockDim (N <= 341: two at most) of the N x N pair terms and runs their sums over j ascending as one chain
 // each, T_j (quantile) or p'_k and Tz_k (categorical) read from LDS as broadcasts.  theta_i / the logit of row i stay in
 // the owning thread's registers: nothing else reads them.  Values: one wave per row triplet.
+// Select: the values kernel's wave per row, then lane 0 draws the row's epsilon-greedy action - what an
+// evaluator step and an acting step need from Z in one launch.
 //
 // The fixed orders (every quantile operation is a separately rounded fp32 operation; the file is built without contraction):
 //   S(x, n), the sum of n values used for every sum that is not a chain over j: lane l of one wave chains x[l], x[l + 64], ..
@@ -143,6 +145,66 @@ __global__ __launch_bounds__(256) void k_dist_values(const float* __restrict__ z
   }
   if (actions) actions[s] = (uint8_t)best;
   if (max_q) max_q[s] = best == 0 ? qv[0] : best == 1 ? qv[1] : qv[2];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Values, first argmax and the epsilon-greedy draw in one launch: k_dist_values' layout (wave w of a block
+// takes forward row 4 blockIdx + w; no LDS, no barrier) and its device functions, so q, the argmax and max-Q are its bits;
+// then lane 0 does for the row what evaluator.hip's k_eval_select does.  list: row r is env list[r], valid while
+// r < count[1] and kdone[e] < K (the evaluator); null: e = r and every row is valid (the acting call).  A row that is not
+// valid reads no Z and leaves nothing behind.  Action counts are integer atomics, one per valid row.
+struct SelectArgs {
+  const float* z;               // [rows][3 N]
+  uint32_t rows;
+  const uint32_t* list;         // [rows] or null
+  const uint32_t* count;        // with list
+  const uint32_t* kdone;        // with list
+  uint32_t K;
+  double epsilon;
+  uint64_t seed;
+  uint32_t t, purpose;
+  uint8_t* actions;             // [e]
+  float* qmax;                  // [e] greedy max-Q, or null
+  float* q;                     // [r][3] greedy values, or null
+  unsigned long long* counts;   // [3] with list, or null
+};
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_dist_select(SelectArgs S, Atoms A) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (r >= S.rows) return;   // (wave-uniform, as every exit below)
+  uint32_t e = r;
+  if (S.list) {
+    if (r >= S.count[1]) return;
+    e = S.list[r];
+    if (S.kdone[e] >= S.K) return;
+  }
+  const float* row = S.z + (size_t)r * 3 * A.N;
+  float qv[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    qv[a] = KIND == QLX_DIST_QUANTILE ? quantile_value(row + a * A.N, A.N, lane) : softmax_row(row + a * A.N, A, lane).value;
+  if (lane != 0) return;
+  const int best = first_argmax3(qv[0], qv[1], qv[2]);
+  bool random = false;
+  if (S.epsilon > 0.0) {
+    RngStreamRegs su(S.seed, e, S.t, S.purpose, 0);   // (no indexed array: no scratch)
+    random = S.epsilon > uniform_f64_01(su);
+  }
+  uint32_t a = (uint32_t)best;
+  if (random) {
+    RngStreamRegs sa(S.seed, e, S.t, S.purpose, 2);
+    a = uniform_u8(sa, kActions);
+  }
+  S.actions[e] = (uint8_t)a;
+  if (S.qmax) S.qmax[e] = best == 0 ? qv[0] : best == 1 ? qv[1] : qv[2];
+  if (S.q) {
+    S.q[(size_t)r * 3] = qv[0];
+    S.q[(size_t)r * 3 + 1] = qv[1];
+    S.q[(size_t)r * 3 + 2] = qv[2];
+  }
+  if (S.counts) atomicAdd(S.counts + a, 1ull);
 }
 
 struct LossArgs {
@@ -360,6 +422,13 @@ void check_batch(const qlx_dist_batch* b, uint32_t batch) {
   QLX_CHECK(batch > 0 && batch <= kDlMaxTrain, QLX_E_INVALID, "batch must be in 1..4096");
 }
 
+// what the two acting calls share beside the descriptor
+void check_select(uint32_t n, double epsilon, const uint8_t* d_actions) {
+  QLX_CHECK(n > 0 && n <= kDlMaxStates, QLX_E_INVALID, "n must be in 1..8192");
+  QLX_CHECK(std::isfinite(epsilon) && epsilon >= 0.0 && epsilon <= 1.0, QLX_E_INVALID, "epsilon must be finite and in 0..1");
+  QLX_CHECK(d_actions, QLX_E_INVALID, "null d_actions");
+}
+
 // the checks that read the head
 void check_head(const qlx_head* h, const qlx_dist& d, uint32_t n) {
   QLX_CHECK((int64_t)3 * d.atoms == (int64_t)h->width, QLX_E_INVALID, "3 * dist->atoms is not the head's width");
@@ -377,6 +446,24 @@ void dist_values(const qlx_dist& d, const float* z, uint32_t n, float* q, uint8_
   QLX_HIP(hipGetLastError());
   debug_sync(s, "k_dist_values");
 }
+
+void dist_select(const qlx_dist& d, const float* z, uint32_t rows, const DistSelectRows* active, double epsilon, uint64_t seed,
+                 uint32_t t, uint32_t purpose, uint8_t* actions, float* qmax, float* q, hipStream_t s) {
+  const Atoms A = atoms_of(d);
+  SelectArgs S{};
+  S.z = z; S.rows = rows;
+  if (active) { S.list = active->list; S.count = active->count; S.kdone = active->kdone; S.K = active->K; S.counts = active->counts; }
+  S.epsilon = epsilon; S.seed = seed; S.t = t; S.purpose = purpose;
+  S.actions = actions; S.qmax = qmax; S.q = q;
+  if (d.kind == QLX_DIST_QUANTILE)
+    hipLaunchKernelGGL(k_dist_select<QLX_DIST_QUANTILE>, dim3((rows + 3) / 4), dim3(256), 0, s, S, A);
+  else
+    hipLaunchKernelGGL(k_dist_select<QLX_DIST_CATEGORICAL>, dim3((rows + 3) / 4), dim3(256), 0, s, S, A);
+  QLX_HIP(hipGetLastError());
+  debug_sync(s, "k_dist_select");
+}
+
+void dist_check(const qlx_dist* d) { check_dist(d); }
 
 void dist_loss(const qlx_dist& d, const float* z, const qlx_dist_batch& b, uint32_t B, float* dz, float* loss, float* sample_loss,
                uint8_t* a_star_out, uint32_t* flag, hipStream_t s) {
@@ -454,6 +541,37 @@ int32_t qlx_head_dist_train_dev(qlx_head* h, const qlx_dist* dist, const qlx_sta
   if ((rc = qlx_head_dist_loss_dev(h, dist, d_z_work, batch_in, batch, d_dz_work, d_loss, d_sample_loss, nullptr)) != QLX_OK) return rc;
   if ((rc = qlx_head_backward_dev(h, src, d_dz_work, nullptr, batch, ticket)) != QLX_OK) return rc;
   return qlx_model_step_dev(h->model, 0);
+}
+
+int32_t qlx_head_select_dev(qlx_head* h, const qlx_dist* dist, const float* d_z, uint32_t n, double epsilon, uint64_t seed,
+                            uint32_t step, uint8_t* d_actions, float* d_max_q, float* d_q) {
+  return guard([&] {
+    QLX_CHECK(h, QLX_E_INVALID, "null head");
+    check_dist(dist);
+    QLX_CHECK(d_z, QLX_E_INVALID, "null d_z");
+    check_select(n, epsilon, d_actions);
+    const qlx_dist d = *dist;
+    check_head(h, d, n);
+    QLX_HIP(hipSetDevice(h->model->device));
+    dist_select(d, d_z, n, nullptr, epsilon, seed, step, P_ACT_DEV, d_actions, d_max_q, d_q, h->model->stream);
+  });
+}
+
+int32_t qlx_head_act_dev(qlx_head* h, const qlx_dist* dist, const qlx_states_dev* src, uint32_t n, double epsilon, uint64_t seed,
+                         uint32_t step, uint8_t* d_actions, float* d_max_q, float* d_q, float* d_z_work) {
+  // every check of the two calls first, so that a failure launches nothing
+  int32_t rc = guard([&] {
+    QLX_CHECK(h, QLX_E_INVALID, "null head");
+    check_dist(dist);
+    check_source(src);
+    check_select(n, epsilon, d_actions);
+    QLX_CHECK(d_z_work, QLX_E_INVALID, "null d_z_work");
+    check_head(h, *dist, n);
+    check_handles(h->model, *src, n);
+  });
+  if (rc != QLX_OK) return rc;
+  if ((rc = qlx_head_forward_dev(h, src, n, d_z_work, nullptr)) != QLX_OK) return rc;
+  return qlx_head_select_dev(h, dist, d_z_work, n, epsilon, seed, step, d_actions, d_max_q, d_q);
 }
 
 }  // extern "C"

@@ -7,6 +7,9 @@
 //                  pointer table [B][4] of the next forward
 // Episodes end at very different times, so the forward runs over B rows = the active count the host read at its last
 // poll (every poll_steps vector steps: one pinned 8-byte copy, an event and a wait); nothing else synchronises.
+// A run on a model's wide head (qlx_evaluator_run_head) is the same loop with the step "Q and select"
+// exchanged: the head's forward into the evaluator's Z rows, then dist_loss.hip's k_dist_select in place of the built-in
+// head and k_eval_select.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "dist_loss.h"
+#include "head_wide.h"
 #include "objects.h"
 #include "qnet.h"
 
@@ -187,6 +192,12 @@ struct qlx_evaluator {
   qlx::DeviceBuffer<uint8_t> d_rec_term;
   qlx::DeviceBuffer<unsigned long long> d_counts;   // [3] actions taken
   qlx::DeviceBuffer<uint32_t> d_count;              // [2] (k_eval_init)
+  // a run on a wide head: its outputs over the forward's rows [n][width], grown only, before the loop of the first run that
+  // needs it; fused_select = false (QLX_EVAL_HEAD_FUSED=0, the measurement's other arm): k_dist_values into d_hq [n][3],
+  // then k_eval_select
+  qlx::DeviceBuffer<float> d_z, d_hq;
+  size_t z_floats = 0;
+  bool fused_select = true;
   qlx::PinnedBuffer<uint32_t> h_count;              // pinned copy read at each poll
   hipEvent_t polled = nullptr;
   // host copies of the last run's records
@@ -214,11 +225,58 @@ struct EvalBorrow {
   }
 };
 
-static void evaluator_run(qlx_evaluator* ev, qlx_model* m, qlx_eval_summary* out) {
+static void launch_eval_select(qlx_evaluator* ev, uint32_t B, const float* q, uint32_t t, hipStream_t s) {
+  const qlx_eval_config& c = ev->cfg;
+  hipLaunchKernelGGL(k_eval_select, dim3((B + 255) / 256), dim3(256), 0, s, B, ev->d_count, ev->d_list, q, c.episodes_per_env,
+                     ev->d_kdone, c.epsilon, c.policy_seed, t, ev->d_actions, ev->d_qmax, ev->d_counts);
+  QLX_HIP(hipGetLastError());
+}
+
+// "Q and select" of the built-in head: after the trunk forward over B rows, row r's action into d_actions[list[r]], its
+// max-Q into d_qmax, the action counts
+struct SelectBuiltin {
+  void prepare(qlx_evaluator*, qlx_model*) const {}
+  void operator()(qlx_evaluator* ev, qlx_model* m, uint32_t B, uint32_t t, hipStream_t s) const {
+    Fc2Args a = fc2_args(m, (int)B);
+    model_head(m, 0, a, (int)B, s);
+    launch_eval_select(ev, B, m->w.q, t, s);
+  }
+};
+
+// ... of a wide head read as `d`: no built-in head launch
+struct SelectHead {
+  qlx_head* h;
+  qlx_dist d;
+  void prepare(qlx_evaluator* ev, qlx_model*) const {
+    const size_t need = (size_t)ev->cfg.n_envs * (size_t)h->width;
+    if (need > ev->z_floats) {
+      ev->d_z.release();
+      ev->z_floats = 0;
+      ev->d_z.alloc(need);
+      ev->z_floats = need;
+    }
+    if (!ev->fused_select && !ev->d_hq) ev->d_hq.alloc((size_t)ev->cfg.n_envs * kActions);
+  }
+  void operator()(qlx_evaluator* ev, qlx_model*, uint32_t B, uint32_t t, hipStream_t s) const {
+    const qlx_eval_config& c = ev->cfg;
+    head_forward_launch(h, B, ev->d_z, s);
+    if (ev->fused_select) {
+      const DistSelectRows rows{ev->d_list, ev->d_count, ev->d_kdone, c.episodes_per_env, ev->d_counts};
+      dist_select(d, ev->d_z, B, &rows, c.epsilon, c.policy_seed, t, P_EVAL, ev->d_actions, ev->d_qmax, nullptr, s);
+    } else {
+      dist_values(d, ev->d_z, B, ev->d_hq, nullptr, nullptr, s);
+      launch_eval_select(ev, B, ev->d_hq, t, s);
+    }
+  }
+};
+
+template <class Select>
+static void evaluator_run(qlx_evaluator* ev, qlx_model* m, const Select& select, qlx_eval_summary* out) {
   const qlx_eval_config& c = ev->cfg;
   const uint32_t n = c.n_envs, K = c.episodes_per_env, P = ev->poll;
   QLX_HIP(hipSetDevice(ev->device));
   model_workspace(m, (int)n);
+  select.prepare(ev, m);
   EvalBorrow borrow(ev, m);
   hipStream_t s = m->stream;
   qlx_env* env = ev->env;
@@ -234,11 +292,7 @@ static void evaluator_run(qlx_evaluator* ev, qlx_model* m, qlx_eval_summary* out
   for (;;) {
     for (uint32_t i = 0; i < P; ++i, ++t) {
       model_forward_trunk(m, ev->d_table, (int)B, s, false);
-      Fc2Args a = fc2_args(m, (int)B);
-      model_head(m, 0, a, (int)B, s);
-      hipLaunchKernelGGL(k_eval_select, dim3((B + 255) / 256), dim3(256), 0, s, B, ev->d_count, ev->d_list, m->w.q, K, ev->d_kdone,
-                         c.epsilon, c.policy_seed, (uint32_t)t, ev->d_actions, ev->d_qmax, ev->d_counts);
-      QLX_HIP(hipGetLastError());
+      select(ev, m, B, (uint32_t)t, s);
       debug_sync(s, "eval act + select");
       env_launch_step(env, ev->d_actions, ev->d_rewards, ev->d_dones);
       hipLaunchKernelGGL(k_eval_book, dim3(1), dim3(1024), 0, s, n, K, ev->d_rewards, ev->d_dones, env->d_ep_steps,
@@ -310,6 +364,8 @@ int32_t qlx_evaluator_create(const qlx_eval_config* cfg, int32_t device, qlx_eva
       ev->poll = cfg->poll_steps ? cfg->poll_steps : kEvalPollDefault;
       const char* sw = std::getenv("QLX_EVAL_COMPACT");
       ev->compact = !(sw && sw[0] == '0');
+      const char* fs = std::getenv("QLX_EVAL_HEAD_FUSED");
+      ev->fused_select = !(fs && fs[0] == '0');
       const uint32_t n = cfg->n_envs;
       const size_t R = (size_t)n * cfg->episodes_per_env;
       const int32_t st = qlx_env_create(QLX_ENV_BREAKOUT, n, cfg->env_seed, device, &ev->env);
@@ -360,7 +416,20 @@ int32_t qlx_evaluator_run(qlx_evaluator* ev, qlx_model* m, qlx_eval_summary* out
   return guard([&] {
     QLX_CHECK(ev && m && out, QLX_E_INVALID, "null argument");
     QLX_CHECK(m->device == ev->device, QLX_E_INVALID, "model and evaluator are on different devices");
-    evaluator_run(ev, m, out);
+    evaluator_run(ev, m, SelectBuiltin{}, out);
+  });
+}
+
+int32_t qlx_evaluator_run_head(qlx_evaluator* ev, qlx_head* h, const qlx_dist* dist, qlx_eval_summary* out) {
+  return guard([&] {
+    QLX_CHECK(ev, QLX_E_INVALID, "null evaluator");
+    QLX_CHECK(h, QLX_E_INVALID, "null head");
+    dist_check(dist);
+    QLX_CHECK(out, QLX_E_INVALID, "null out");
+    const qlx_dist d = *dist;
+    QLX_CHECK((int64_t)3 * d.atoms == (int64_t)h->width, QLX_E_INVALID, "3 * dist->atoms is not the head's width");
+    QLX_CHECK(h->model->device == ev->device, QLX_E_INVALID, "model and evaluator are on different devices");
+    evaluator_run(ev, h->model, SelectHead{h, d}, out);
   });
 }
 

@@ -27,3 +27,9 @@ struct qlx_head {
   int64_t count() const { return (int64_t)(qlx::kHeadIn + 1) * width; }
   int64_t bias_offset() const { return (int64_t)qlx::kHeadIn * width; }
 };
+
+namespace qlx {
+// Z [n][width] = a4 Wh + bh of the model's last trunk forward over n rows: the one k_headw_fwd launch, with the grid choice
+// every caller shares (qlx_head_forward_dev, the evaluator's head run), so the bits are the same whoever asks
+void head_forward_launch(qlx_head* h, uint32_t n, float* d_z, hipStream_t s);
+}  // namespace qlx

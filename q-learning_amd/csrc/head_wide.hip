@@ -24,6 +24,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "head_wide.h"
@@ -37,6 +40,7 @@ namespace qlx {
 using namespace q32;
 
 constexpr uint32_t kHwMaxStates = 8192, kHwMaxTrain = 4096;
+constexpr char kHeadMagic[8] = {'Q', 'L', 'X', 'H', 'E', 'A', 'D', '1'};
 
 // ---------------------------------------------------------------------------------------------------------------
 // Forward.  Block = 16 samples x the column tiles ct = blockIdx.y, + gridDim.y, ..; wave w chains the k quarter w
@@ -337,6 +341,17 @@ void head_step(qlx_head* h, hipStream_t s) {
   h->iterations += 1;
 }
 
+void head_forward_launch(qlx_head* h, uint32_t n, float* d_z, hipStream_t st) {
+  const int rows = ((int)n + 15) / 16, tiles = (h->width + 15) / 16;
+  // about a thousand blocks, else every tile its own (at B = 1024 and width 600 measured alike from 512 to 2,048 blocks,
+  // 18.3 to 19.0 us, and 25.0 us at 256)
+  const int gy = std::min(tiles, std::max(1, (1024 + rows - 1) / rows));
+  hipLaunchKernelGGL(k_headw_fwd, dim3(rows, gy), dim3(256), 0, st, f32_a4(h->model), (const float*)h->d_w,
+                     (const float*)(h->d_w + h->bias_offset()), (int)n, h->width, d_z);
+  QLX_HIP(hipGetLastError());
+  debug_sync(st, "k_headw_fwd");
+}
+
 static float* head_var(qlx_head* h, int32_t var, int32_t which) {
   float* base = which == 0 ? h->d_w.get() : which == 1 ? h->d_m.get() : h->d_v.get();
   return base + (var == 0 ? 0 : h->bias_offset());
@@ -433,6 +448,54 @@ int32_t qlx_head_set_var(qlx_head* h, int32_t var, int32_t which, const float* i
   });
 }
 
+// the head's file: magic, {width, iterations}, then the three buffers whole (Wh then bh in each) - the model's format
+// (model.hip qlx_model_write_checkpoint) with the head's width in place of the parameter count
+int32_t qlx_head_write_checkpoint(qlx_head* h, const char* path) {
+  return guard([&] {
+    QLX_CHECK(h, QLX_E_INVALID, "null head");
+    QLX_CHECK(path, QLX_E_INVALID, "null path");
+    const size_t count = (size_t)h->count();
+    QLX_HIP(hipSetDevice(h->model->device));
+    QLX_HIP(hipStreamSynchronize(h->model->stream));
+    std::vector<float> buf(count * 3);
+    QLX_HIP(hipMemcpy(buf.data(), h->d_w, count * 4, hipMemcpyDeviceToHost));
+    QLX_HIP(hipMemcpy(buf.data() + count, h->d_m, count * 4, hipMemcpyDeviceToHost));
+    QLX_HIP(hipMemcpy(buf.data() + 2 * count, h->d_v, count * 4, hipMemcpyDeviceToHost));
+    FILE* f = std::fopen(path, "wb");
+    QLX_CHECK(f, QLX_E_IO, std::string("cannot open ") + path);
+    const int64_t hdr[2] = {h->width, h->iterations};
+    bool ok = std::fwrite(kHeadMagic, 1, 8, f) == 8 && std::fwrite(hdr, 8, 2, f) == 2 &&
+              std::fwrite(buf.data(), 4, buf.size(), f) == buf.size();
+    ok = (std::fclose(f) == 0) && ok;
+    QLX_CHECK(ok, QLX_E_IO, "head checkpoint write failed");
+  });
+}
+
+// the whole file is in host memory and judged before the first device copy: a refused file changes nothing of the head
+int32_t qlx_head_read_checkpoint(qlx_head* h, const char* path) {
+  return guard([&] {
+    QLX_CHECK(h, QLX_E_INVALID, "null head");
+    QLX_CHECK(path, QLX_E_INVALID, "null path");
+    FILE* f = std::fopen(path, "rb");
+    QLX_CHECK(f, QLX_E_IO, std::string("cannot open ") + path);
+    const size_t count = (size_t)h->count();
+    char magic[8];
+    int64_t hdr[2];
+    std::vector<float> buf(count * 3);
+    const bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, kHeadMagic, 8) == 0 && std::fread(hdr, 8, 2, f) == 2 &&
+                    hdr[0] == h->width && std::fread(buf.data(), 4, buf.size(), f) == buf.size();
+    std::fclose(f);
+    QLX_CHECK(ok, QLX_E_IO, "not a qlx head checkpoint of this head's width");
+    QLX_HIP(hipSetDevice(h->model->device));
+    QLX_HIP(hipStreamSynchronize(h->model->stream));
+    QLX_HIP(hipMemcpy(h->d_w, buf.data(), count * 4, hipMemcpyHostToDevice));
+    QLX_HIP(hipMemcpy(h->d_m, buf.data() + count, count * 4, hipMemcpyHostToDevice));
+    QLX_HIP(hipMemcpy(h->d_v, buf.data() + 2 * count, count * 4, hipMemcpyHostToDevice));
+    h->iterations = hdr[1];
+    h->model->fwd_reusable = false;   // a kept forward belongs to the weights before this read
+  });
+}
+
 int32_t qlx_head_forward_dev(qlx_head* h, const qlx_states_dev* src, uint32_t n, float* d_z, float* d_q) {
   return guard([&] {
     QLX_CHECK(h, QLX_E_INVALID, "null head");
@@ -445,14 +508,7 @@ int32_t qlx_head_forward_dev(qlx_head* h, const qlx_states_dev* src, uint32_t n,
     QLX_HIP(hipSetDevice(m->device));
     hipStream_t st = m->stream;
     model_forward_trunk(m, states_table(m, s, n), (int)n, st);
-    const int rows = ((int)n + 15) / 16, tiles = (h->width + 15) / 16;
-    // about a thousand blocks, else every tile its own (at B = 1024 and width 600 measured alike from 512 to 2,048 blocks,
-    // 18.3 to 19.0 us, and 25.0 us at 256)
-    const int gy = std::min(tiles, std::max(1, (1024 + rows - 1) / rows));
-    hipLaunchKernelGGL(k_headw_fwd, dim3(rows, gy), dim3(256), 0, st, f32_a4(m), (const float*)h->d_w,
-                       (const float*)(h->d_w + h->bias_offset()), (int)n, h->width, d_z);
-    QLX_HIP(hipGetLastError());
-    debug_sync(st, "k_headw_fwd");
+    head_forward_launch(h, n, d_z, st);
     if (d_q) {
       Fc2Args a = fc2_args(m, (int)n);
       a.q = d_q;

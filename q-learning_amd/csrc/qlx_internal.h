@@ -63,7 +63,7 @@ constexpr int kNumBricks = 60;
 __host__ __device__ inline int s2d_offset(int x, int y) { return ((x >> 2) * kBlocks + (y >> 2)) * 16 + (x & 3) * 4 + (y & 3); }
 
 // ---- Philox4x32-10 counter-based RNG (build-defined stream) ------------
-enum Purpose : uint32_t { P_BALL = 1, P_ACT = 2, P_SAMPLE = 3, P_INIT = 4, P_SYNTH = 5, P_BALLGAME = 6, P_PER = 7, P_EVAL = 8 };
+enum Purpose : uint32_t { P_BALL = 1, P_ACT = 2, P_SAMPLE = 3, P_INIT = 4, P_SYNTH = 5, P_BALLGAME = 6, P_PER = 7, P_EVAL = 8, P_ACT_DEV = 9 };
 
 __host__ __device__ inline void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                        uint32_t out[4]) {
@@ -105,6 +105,35 @@ struct RngStream {
   }
 };
 
+// The same word stream with the block's four words selected by comparisons, never indexed: a kernel that draws with it keeps
+// them in registers (RngStream's buf[word & 3] is a dynamically indexed array: 64 bytes of scratch per lane).  The uniform_*
+// functions below take either.
+struct RngStreamRegs {
+  uint32_t k0, k1, c1, c2, purpose;
+  uint64_t word;
+  uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+  uint64_t blk;
+  __host__ __device__ RngStreamRegs(uint64_t seed, uint32_t c1_, uint32_t c2_, uint32_t purpose_, uint64_t start = 0)
+      : k0((uint32_t)seed), k1((uint32_t)(seed >> 32)), c1(c1_), c2(c2_), purpose(purpose_), word(start), blk(~0ull) {}
+  __host__ __device__ uint32_t u32() {
+    const uint64_t b = word >> 2;
+    if (b != blk) {
+      uint32_t out[4];
+      philox((uint32_t)b, c1, c2, purpose, k0, k1, out);
+      b0 = out[0]; b1 = out[1]; b2 = out[2]; b3 = out[3];
+      blk = b;
+    }
+    const uint32_t i = (uint32_t)word & 3u;
+    ++word;
+    return i == 0 ? b0 : i == 1 ? b1 : i == 2 ? b2 : b3;
+  }
+  __host__ __device__ uint64_t u64() {
+    const uint64_t lo = u32();
+    const uint64_t hi = u32();
+    return lo | (hi << 32);
+  }
+};
+
 __host__ __device__ inline float bits_f32(uint32_t b) { return __builtin_bit_cast(float, b); }
 __host__ __device__ inline uint32_t f32_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 
@@ -119,7 +148,8 @@ __host__ __device__ inline float uniform_f32(RngStream& s, float low, float high
   }
 }
 // rand 0.8.5 gen_range(0_f64..1_f64)
-__host__ __device__ inline double uniform_f64_01(RngStream& s) {
+template <class Stream>
+__host__ __device__ inline double uniform_f64_01(Stream& s) {
   for (;;) {
     const double v01 = __builtin_bit_cast(double, (s.u64() >> 12) | 0x3FF0000000000000ull) - 1.0;
     const double res = v01 * 1.0 + 0.0;
@@ -127,7 +157,8 @@ __host__ __device__ inline double uniform_f64_01(RngStream& s) {
   }
 }
 // rand 0.8.5 UniformInt<u8>::sample_single(0, n)
-__host__ __device__ inline uint32_t uniform_u8(RngStream& s, uint32_t n) {
+template <class Stream>
+__host__ __device__ inline uint32_t uniform_u8(Stream& s, uint32_t n) {
   const uint32_t zone = 0xFFFFFFFFu - (0xFFFFFFFFu - n + 1u) % n;
   for (;;) {
     const uint64_t m = (uint64_t)s.u32() * n;

@@ -165,6 +165,7 @@ OBS_NCHW_TIME = 1   # QLX_OBS_NCHW_TIME: [n][4][84][84] (age, x, y), channel 0 o
 STEP_GRADS_WRITTEN = 1   # QLX_STEP_GRADS_WRITTEN: qlx_model_step_dev after the caller wrote the gradient buffer
 HEAD_IN = 512            # the wide head's input: a4, the ReLU output of fc1
 HEAD_MAX_WIDTH = 1024    # QLX_HEAD_MAX_WIDTH
+P_ACT_DEV = 9            # the Philox purpose of qlx_head_select_dev / _act_dev's draws (P_EVAL = 8 is the evaluator's)
 
 _NP_OF_C = {C.c_uint64: "<u8", C.c_uint32: "<u4", C.c_float: "<f4"}
 # the same row as a numpy structured dtype (what metrics() returns an array of)
@@ -297,6 +298,11 @@ def lib():
         "qlx_head_values_dev": ([vp, C.POINTER(Dist), vp, u32, vp, vp, vp], i32),
         "qlx_head_dist_loss_dev": ([vp, C.POINTER(Dist), vp, C.POINTER(DistBatch), u32, vp, vp, vp, vp], i32),
         "qlx_head_dist_train_dev": ([vp, C.POINTER(Dist), C.POINTER(StatesDev), C.POINTER(DistBatch), u32, vp, vp, vp, vp], i32),
+        # acting with, evaluating and checkpointing a distributional head (TorchQNet.select / act / evaluate / save_head)
+        "qlx_head_select_dev": ([vp, C.POINTER(Dist), vp, u32, C.c_double, u64, u32, vp, vp, vp], i32),
+        "qlx_head_act_dev": ([vp, C.POINTER(Dist), C.POINTER(StatesDev), u32, C.c_double, u64, u32, vp, vp, vp, vp], i32),
+        "qlx_evaluator_run_head": ([vp, vp, C.POINTER(Dist), C.POINTER(EvalSummary)], i32),
+        "qlx_head_write_checkpoint": ([vp, C.c_char_p], i32), "qlx_head_read_checkpoint": ([vp, C.c_char_p], i32),
         "qlx_params_default": ([vp], None),
         "qlx_learner_create": ([C.POINTER(Params), i32, C.POINTER(vp)], i32), "qlx_learner_destroy": ([vp], i32),
         "qlx_learner_vector_step": ([vp], i32), "qlx_learner_run": ([vp, u64], i32), "qlx_learner_sync": ([vp], i32),
@@ -786,6 +792,23 @@ class WideHead:
         _check(lib().qlx_head_dist_train_dev(self.h, C.byref(dist), C.byref(src), C.byref(batch_in), batch, d_z_work, d_dz_work,
                                              d_loss, d_sample_loss))
 
+    def select_dev(self, dist, d_z, n, epsilon, seed, step, d_actions, d_max_q=None, d_q=None):
+        """epsilon-greedy actions of n rows d_z [n][3 atoms] in one launch; row r draws from stream (seed, r, step, P_ACT_DEV)"""
+        _check(lib().qlx_head_select_dev(self.h, C.byref(dist), d_z, n, epsilon, seed, step, d_actions, d_max_q, d_q))
+
+    def act_dev(self, dist, src, n, epsilon, seed, step, d_actions, d_z_work, d_max_q=None, d_q=None):
+        """forward_dev into d_z_work [n][3 atoms], then select_dev on it, in one call"""
+        _check(lib().qlx_head_act_dev(self.h, C.byref(dist), C.byref(src), n, epsilon, seed, step, d_actions, d_max_q, d_q,
+                                      d_z_work))
+
+    def write_checkpoint(self, path):
+        """Wh, bh, their Adam slots and the head's iterations in one file (the model's own file does not hold them)"""
+        _check(lib().qlx_head_write_checkpoint(self.h, path.encode()))
+        return path
+
+    def read_checkpoint(self, path):
+        _check(lib().qlx_head_read_checkpoint(self.h, path.encode()))
+
 
 class Evaluator:
     """Policy evaluation on the GPU (qlx_evaluator, beyond the reference): n_envs fresh Breakout envs play
@@ -813,6 +836,13 @@ class Evaluator:
         """K episodes per env with `model`'s current weights (not modified); the summary as a dict"""
         s = EvalSummary()
         _check(lib().qlx_evaluator_run(self.h, model.h, C.byref(s)))
+        return _eval_summary(s)
+
+    def run_head(self, head, dist):
+        """run() with the policy of a WideHead read as `dist` (a Dist): the argmax of the head's values in place of the
+        built-in Q; everything else, episodes() included, as run()"""
+        s = EvalSummary()
+        _check(lib().qlx_evaluator_run_head(self.h, head.h, C.byref(dist), C.byref(s)))
         return _eval_summary(s)
 
     def episodes(self):

@@ -480,6 +480,7 @@ class TorchQNet(_Streamed):
         self._head = None         # the attached qlx.WideHead (attach_head)
         self._head_grads = None
         self._dist_work = {}      # width -> the two work tensors of train_dist
+        self._act_work = {}       # width -> the Z work tensor of act
 
     def close(self):
         head = getattr(self, "_head", None)
@@ -498,7 +499,7 @@ class TorchQNet(_Streamed):
         """Attach a dense layer 512 -> width (1..1024) on the trunk's a4 (qlx.WideHead; fp32 nets only, one per net) and
         return it.  forward(..., head=True) then returns (q, z), z float32 [n, width]; a loss of either or both
         backpropagates through one backward; step() steps the head's Wh and bh with the ten variables, each clipped by a
-        norm of its own; head_grads() shows their gradients.  The head's get / set are its persistence."""
+        norm of its own; head_grads() shows their gradients.  save_head / load_head are its persistence."""
         if self.h is None:
             raise QlError("the object is closed")
         self._head = qlx.WideHead(self._m, width, seed)
@@ -654,6 +655,87 @@ class TorchQNet(_Streamed):
                   lambda: _L.qlx_head_dist_train_dev(head.h, C.byref(dist.c), C.byref(s), C.byref(batch), B, work[0].data_ptr(),
                                                      work[1].data_ptr(), loss.data_ptr(), None if sl is None else sl.data_ptr()))
         return loss, sl
+
+    # ---- acting with, evaluating and checkpointing the head ----
+
+    @staticmethod
+    def _epsilon(epsilon):
+        e = float(epsilon)
+        if not (math.isfinite(e) and 0.0 <= e <= 1.0):
+            raise ValueError("epsilon must be finite and in 0..1")
+        return e
+
+    def _select_outputs(self, n, want, out):
+        """({name: tensor} with 'actions' always in it, the names asked for) or ValueError before anything is launched"""
+        names = (want,) if isinstance(want, str) else tuple(want)
+        out = dict(out or {})
+        if not names or set(names) - set(_WANT) or set(out) - set(names):
+            raise ValueError(f"want must name some of {_WANT}, and out only what want names")
+        spec = dict(q=(torch.float32, (n, 3)), actions=(torch.uint8, (n,)), max_q=(torch.float32, (n,)))
+        res = {k: (_arg(f"out[{k!r}]", out[k], self.device, *spec[k]) if k in out else
+                   torch.empty(spec[k][1], dtype=spec[k][0], device=self.device)) for k in set(names) | {"actions"}}
+        return res, names
+
+    def select(self, z, dist, epsilon, seed, step, want="actions", out=None):
+        """Epsilon-greedy actions of head outputs z float32 [n, 3 * atoms] read as `dist`, in one launch
+        (qlx_head_select_dev): row r is random when epsilon > 0 and epsilon > a float64 draw of the stream (seed, r, step,
+        qlx.P_ACT_DEV), then uniform over the three actions, else the first argmax of the values.  `want` and `out` as in
+        head_values; 'max_q' and 'q' are the greedy values whatever was drawn.  With epsilon 0 this is head_values."""
+        head = self._dist(dist)
+        if not isinstance(z, torch.Tensor) or z.dim() != 2:
+            raise ValueError("z must be a 2-d tensor")
+        n = z.shape[0]
+        if not 0 < n <= self.reserved:
+            raise ValueError(f"n must be in 1..{self.reserved} (the reserve)")
+        zt = _arg("z", z.detach(), self.device, torch.float32, (n, dist.width))
+        eps = self._epsilon(epsilon)
+        res, names = self._select_outputs(n, want, out)
+        ptr = [res[k].data_ptr() if k in res else None for k in ("actions", "max_q", "q")]
+        self._run(None, None, (zt,) + tuple(res.values()),
+                  lambda: _L.qlx_head_select_dev(head.h, C.byref(dist.c), zt.data_ptr(), n, eps, seed, step, *ptr))
+        return res[want] if isinstance(want, str) else tuple(res[k] for k in names)
+
+    def act(self, dist, epsilon, seed, step, obs=None, *, env=None, replay=None, indices=None, which="s", layout="nchw_time",
+            want="actions", out=None):
+        """The acting step in one call (qlx_head_act_dev): the head's forward over the states, then select() on its output.
+        The [reserve, 3 * atoms] work tensor that holds Z is allocated once per net and width."""
+        head = self._dist(dist)
+        s, n, ins = self._source(obs, env, replay, indices, which, layout)
+        if not 0 < n <= self.reserved:
+            raise ValueError(f"n must be in 1..{self.reserved} (the reserve)")
+        eps = self._epsilon(epsilon)
+        res, names = self._select_outputs(n, want, out)
+        work = self._act_work.get(dist.width)
+        if work is None:
+            work = self._act_work[dist.width] = torch.empty((self.reserved, dist.width), dtype=torch.float32, device=self.device)
+        ptr = [res[k].data_ptr() if k in res else None for k in ("actions", "max_q", "q")]
+        self._run(env, replay, ins + tuple(res.values()) + (work,),
+                  lambda: _L.qlx_head_act_dev(head.h, C.byref(dist.c), C.byref(s), n, eps, seed, step, *ptr, work.data_ptr()))
+        return res[want] if isinstance(want, str) else tuple(res[k] for k in names)
+
+    def evaluate(self, evaluator, dist=None):
+        """The summary of a qlx.Evaluator run of this net's policy: with `dist` the attached head's (Evaluator.run_head: the
+        argmax of the head's values), without it the built-in 512 -> 3 head's (Evaluator.run).  The run is a host call on
+        the net's stream: it waits for torch's current stream first and has finished when it returns."""
+        if not isinstance(evaluator, qlx.Evaluator):
+            raise ValueError("evaluator must be a qlx.Evaluator")
+        if evaluator.h is None or self.h is None:
+            raise QlError("the object is closed")
+        head = None if dist is None else self._dist(dist)
+        with self._ordered():
+            return evaluator.run(self._m) if head is None else evaluator.run_head(head, dist.c)
+
+    def save_head(self, path):
+        """the attached head's weights, Adam slots and iterations into `path` (qlx_head_write_checkpoint); the ten model
+        variables go through model.write_checkpoint"""
+        head = self._need_head()
+        with self._ordered():
+            return head.write_checkpoint(path)
+
+    def load_head(self, path):
+        head = self._need_head()
+        with self._ordered():
+            head.read_checkpoint(path)
 
     @property
     def model(self):

@@ -8,8 +8,14 @@ created, so the two arms are two evaluators of one process, run alternately (on,
 sweep alternates its values the same way.  One JSON line per (precision, model, arm) with every wall time, and one
 summary line per comparison; nothing is asserted.
 
+--head quantile:51 | categorical:51 measures instead the evaluator on a wide head of the fp32 model, three
+arms alternated run by run: "builtin" (Evaluator.run, the 512 -> 3 head), "head" (Evaluator.run_head, the fused
+k_dist_select) and "head_split" (an evaluator created under QLX_EVAL_HEAD_FUSED=0: k_dist_values, then k_eval_select).
+"zero" is the same constant policy on the head (Wh = 0, bh favouring action 0: the long tail), "random" a seeded head on
+the seed-2 model (another policy than the built-in head's, so compare the time per vector step, us_per_vector_step).
+
   python scripts/eval_bench.py [--pairs 5] [--envs 1024] [--max-steps 10000] [--precisions f32,bf16]
-                               [--models zero,random] [--polls 1,8,32] [--out FILE]
+                               [--models zero,random] [--polls 1,8,32] [--head KIND:ATOMS] [--out FILE]
 """
 import argparse
 import json
@@ -45,7 +51,7 @@ def make_evaluator(compact, poll, args):
 
 def timed(ev, model):
     t0 = time.perf_counter()
-    s = ev.run(model)
+    s = model(ev) if callable(model) else ev.run(model)   # (a callable: a --head arm's own run)
     return time.perf_counter() - t0, s
 
 
@@ -66,6 +72,63 @@ def alternate(arms, model, pairs):
     return out
 
 
+def alternate_runs(arms, pairs):
+    """arms: {name: (evaluator, run)} with run(evaluator) -> summary"""
+    by_ev = {k: ev for k, (ev, _) in arms.items()}
+    out = {k: dict(wall_s=[]) for k in arms}
+    for k, (ev, run) in arms.items():
+        _, s = timed(ev, run)
+        out[k].update(vector_steps=int(s["vector_steps"]), forward_samples=int(s["forward_samples"]),
+                      env_steps=int(s["env_steps"]), mean_return=s["mean_return"], mean_length=s["mean_length"])
+    for _ in range(pairs):
+        for k, (ev, run) in arms.items():
+            out[k]["wall_s"].append(timed(ev, run)[0])
+    for k, o in out.items():
+        w = o["wall_s"]
+        o.update(median_s=statistics.median(w), min_s=min(w), max_s=max(w),
+                 env_steps_per_s=o["env_steps"] / statistics.median(w),
+                 us_per_vector_step=[1e6 * x / o["vector_steps"] for x in (statistics.median(w), min(w), max(w))])
+    for ev in set(by_ev.values()):
+        ev.close()
+    return out
+
+
+def head_bench(args, emit):
+    kind_name, atoms = args.head.split(":")
+    N = int(atoms)
+    if kind_name == "quantile":
+        dist = qlx.Dist(qlx.DIST_QUANTILE, N, 0.0, 0.0)
+        first = np.float32([1] * N + [0] * 2 * N)            # values exactly [1, 0, 0]
+    else:
+        dist = qlx.Dist(qlx.DIST_CATEGORICAL, N, -10.0, 10.0)
+        up = np.linspace(-40, 40, N, dtype=np.float32)       # action 0: the mass on the highest atoms, 1 and 2: the lowest
+        first = np.concatenate([up, up[::-1], up[::-1]])
+    for kind in args.models.split(","):
+        model = make_model(kind, qlx.PREC_F32)
+        head = qlx.WideHead(model, 3 * N, seed=4)
+        if kind == "zero":
+            head.set(0, np.zeros((qlx.HEAD_IN, 3 * N), np.float32))
+            head.set(1, first)
+        fused = make_evaluator(True, 0, args)
+        os.environ["QLX_EVAL_HEAD_FUSED"] = "0"   # read once, at create
+        try:
+            split = make_evaluator(True, 0, args)
+        finally:
+            del os.environ["QLX_EVAL_HEAD_FUSED"]
+        builtin = make_evaluator(True, 0, args)
+        on_head = lambda ev: ev.run_head(head, dist)   # noqa: E731
+        res = alternate_runs({"builtin": (builtin, lambda ev: ev.run(model)), "head": (fused, on_head),
+                              "head_split": (split, on_head)}, args.pairs)
+        for k, o in res.items():
+            emit(dict(kind="head_ab", head=args.head, model=kind, arm=k, **o))
+        med = {k: o["us_per_vector_step"][0] for k, o in res.items()}
+        emit(dict(kind="head_ab_summary", head=args.head, model=kind, us_per_vector_step=med,
+                  fused_saves_us=med["head_split"] - med["head"], head_costs_us=med["head"] - med["builtin"],
+                  fused_separated=res["head"]["max_s"] < res["head_split"]["min_s"]))
+        head.close()
+        model.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=5)
@@ -74,6 +137,7 @@ def main():
     ap.add_argument("--precisions", default="f32,bf16")
     ap.add_argument("--models", default="zero,random")
     ap.add_argument("--polls", default="1,8,32")
+    ap.add_argument("--head", default=None, help="quantile:N or categorical:N: the evaluator on a wide head (fp32)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     sink = open(args.out, "w") if args.out else None
@@ -85,6 +149,11 @@ def main():
             sink.write(line + "\n")
             sink.flush()
 
+    if args.head:
+        head_bench(args, emit)
+        if sink:
+            sink.close()
+        return
     polls = [int(p) for p in args.polls.split(",") if p]
     for prec_name in args.precisions.split(","):
         precision = qlx.PREC_BF16 if prec_name == "bf16" else qlx.PREC_F32

@@ -13,6 +13,9 @@
       the replay ring: quantile N = 51 and 200, categorical N = 51; per case forward(head=True) + the loss in torch +
       backward() + step() against train_dist(), alternated call by call, median [min..max] of 30 after 5 warm-ups, beside
       `grad`'s update without a head; `--kernels N` only runs N of each for a kernel trace (k_dist_loss_* / k_dist_values)
+  python scripts/torch_qnet_bench.py head_act [--ns 256,8192]   acting with a distributional head, on an env's
+      ring: act() against forward(head=True) + head_values() + the torch epsilon mix (rand, randint, where), quantile and
+      categorical N = 51 per n, alternated call by call, median [min..max] of 30 after 5 warm-ups
   python scripts/torch_qnet_bench.py pack   [--n 1024]     the two staging kernels, to be run under a kernel trace:
       rocprofv3 --kernel-trace --stats -d DIR -- python scripts/torch_qnet_bench.py pack --n 8192
       (k_pack_states: the dense source of q(); k_pack_obs: the host call qlx_model_predict on the same states)
@@ -319,6 +322,38 @@ def dist(args):
     env.close()
 
 
+def head_act(args):
+    if not torch.cuda.is_available():
+        sys.exit("torch_qnet_bench.py head_act: no GPU")
+    N, eps = 51, 0.1
+    print(f"acting with a 3 x {N} head, f32, epsilon {eps}, on the env's ring (median [min..max] of {args.reps} after {args.warmup}):")
+    for n in (int(x) for x in args.ns.split(",")):
+        env, _ = played_env(n, 5)
+        lay = "nchw_time"
+        for d in (QT.Quantile(N), QT.Categorical(N, -10.0, 10.0)):
+            net = QT.TorchQNet("f32", env=env, reserve=n)
+            net.attach_head(3 * N, seed=N)
+            step = [0]
+
+            def three_calls(net=net, d=d):
+                with torch.no_grad():
+                    _, z = net.forward(env=env, layout=lay, head=True)
+                    greedy = net.head_values(z, d, want="actions")
+                explore = torch.rand(n, device=DEV) < eps
+                return torch.where(explore, torch.randint(0, 3, (n,), device=DEV, dtype=torch.uint8), greedy)
+
+            def one_call(net=net, d=d):
+                step[0] += 1
+                return net.act(d, eps, 7, step[0], env=env, layout=lay)
+
+            t, f = time_alternated((three_calls, one_call), args.reps, args.warmup)
+            name = type(d).__name__.lower()
+            print(f"  n = {n:5d} {name + ', forward + head_values + torch mix':48s} {fmt(t)}")
+            print(f"  n = {n:5d} {name + ', act()':48s} {fmt(f)}   {statistics.median(t) - statistics.median(f):+.1f} us saved")
+            net.sync()
+        env.close()
+
+
 def pack(args):
     n = args.n
     net = QT.TorchQNet("bf16", reserve=n)
@@ -336,7 +371,7 @@ def pack(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("act", "update", "grad", "head", "dist", "pack"))
+    ap.add_argument("what", choices=("act", "update", "grad", "head", "dist", "head_act", "pack"))
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--n", type=int, default=1024)
@@ -344,13 +379,14 @@ def main():
     ap.add_argument("--reps", type=int, default=None, help="default 20, dist: 30")
     ap.add_argument("--warmup", type=int, default=None, help="default 3, dist: 5")
     ap.add_argument("--widths", default="4,153,600", help="head: the head widths, comma separated")
+    ap.add_argument("--ns", default="256,8192", help="head_act: the env counts, comma separated")
     ap.add_argument("--kernels", type=int, default=0, help="grad, head, dist: run this many of each path untimed (kernel trace)")
     args = ap.parse_args()
     if args.reps is None:
-        args.reps = 30 if args.what == "dist" else 20
+        args.reps = 30 if args.what in ("dist", "head_act") else 20
     if args.warmup is None:
-        args.warmup = 5 if args.what == "dist" else 3
-    {"act": act, "update": update, "grad": grad, "head": head, "dist": dist, "pack": pack}[args.what](args)
+        args.warmup = 5 if args.what in ("dist", "head_act") else 3
+    {"act": act, "update": update, "grad": grad, "head": head, "dist": dist, "head_act": head_act, "pack": pack}[args.what](args)
 
 
 if __name__ == "__main__":

@@ -15,8 +15,13 @@ cross-entropy of a categorical head on [--v-min, --v-max]), backward, clip and A
 replay's batch tensors as they are.  --c51 without --fused writes that loss in torch.  --per draws prioritized batches and
 feeds the per-sample loss back as the priority (either path).
 
+--act-fused acts through TorchQNet.act(): the head's forward, its values, the argmax and the epsilon draw
+(Philox, by env and step) in one call, in place of forward(head=True) + head_values() + torch.rand / torch.where.  --eval N
+plays one episode in each of N fresh envs with the trained head's greedy policy at the end (qlx.Evaluator through
+TorchQNet.evaluate) and prints the summary.
+
   python scripts/torch_qrdqn_example.py [--envs 256] [--updates 300] [--batch 64] [--quantiles 51] [--n-step 3] [--dueling]
-                                        [--fused] [--c51 [--v-min -10] [--v-max 10]] [--per]
+                                        [--fused] [--c51 [--v-min -10] [--v-max 10]] [--per] [--act-fused] [--eval N]
 """
 import argparse
 import os
@@ -77,9 +82,12 @@ def main():
     ap.add_argument("--v-min", type=float, default=-10.0)
     ap.add_argument("--v-max", type=float, default=10.0)
     ap.add_argument("--per", action="store_true", help="prioritized batches; the per-sample loss is the priority")
+    ap.add_argument("--act-fused", action="store_true", help="act() for acting: forward, values, argmax and epsilon draw in one call")
+    ap.add_argument("--eval", type=int, default=0, metavar="N", help="evaluate the head's greedy policy on N fresh envs at the end")
+    ap.add_argument("--eval-max-steps", type=int, default=2000)
     args = ap.parse_args()
-    if args.dueling and (args.fused or args.c51 or args.per):
-        ap.error("--dueling goes with none of --fused, --c51 and --per")
+    if args.dueling and (args.fused or args.c51 or args.per or args.act_fused or args.eval):
+        ap.error("--dueling goes with none of --fused, --c51, --per, --act-fused and --eval")
 
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -113,11 +121,14 @@ def main():
     t0 = time.perf_counter()
     while updates < args.updates:
         eps = max(0.1, 1.0 - updates / max(1, args.updates))
-        with torch.no_grad():
-            _, z_env = online.forward(env=env, layout=lay, head=True)   # acting on the env's ring: nothing is copied
-            greedy = online.head_values(z_env, dist, want="actions") if args.fused else values(z_env).argmax(dim=1).to(torch.uint8)
-        explore = torch.rand(args.envs, device=dev) < eps
-        actions = torch.where(explore, torch.randint(0, 3, (args.envs,), device=dev, dtype=torch.uint8), greedy)
+        if args.act_fused:   # one call, no torch op: the draws are Philox streams by (seed, env, step)
+            actions = online.act(dist, eps, 7, steps, env=env, layout=lay)
+        else:
+            with torch.no_grad():
+                _, z_env = online.forward(env=env, layout=lay, head=True)   # acting on the env's ring: nothing is copied
+                greedy = online.head_values(z_env, dist, want="actions") if args.fused else values(z_env).argmax(dim=1).to(torch.uint8)
+            explore = torch.rand(args.envs, device=dev) < eps
+            actions = torch.where(explore, torch.randint(0, 3, (args.envs,), device=dev, dtype=torch.uint8), greedy)
         rewards, dones = env.step(actions)
         rb.add(env, actions, rewards, dones)
         env.reset(dones)
@@ -187,6 +198,15 @@ def main():
     kind += (", fused update" if args.fused else ", loss in torch") + (", prioritized" if args.per else "")
     print(f"done ({kind}): {updates} updates, {steps} vector steps x {args.envs} envs in {dt:.2f} s = "
           f"{steps * args.envs / dt:,.0f} env-steps/s (acting net, replay and updates included), last loss {float(last_loss):.5f}")
+    if args.eval:
+        import qlx
+        ev = qlx.Evaluator(args.eval, episodes_per_env=1, max_steps_per_episode=args.eval_max_steps)
+        s = online.evaluate(ev, dist)
+        print(f"evaluation (greedy, {args.eval} envs x 1 episode, at most {args.eval_max_steps} steps): mean return "
+              f"{s['mean_return']:.3f} [{s['min_return']:.0f}, {s['max_return']:.0f}], mean length {s['mean_length']:.1f}, "
+              f"mean max-Q {s['mean_max_q']:.4f}, actions {s['action_counts'].tolist()}, {s['vector_steps']} vector steps, "
+              f"{s['forward_samples']} forward rows")
+        ev.close()
     env.close()   # closes the replay and the nets that share its stream first
 
 
